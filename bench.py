@@ -5,6 +5,14 @@ A "step" = one full pass of the chunking hot path (candidate scan -> chain
 resolve -> Chunk{offset,length} list in HBM) over the rank's synthetic input,
 which is already resident in HBM when the timed region starts.
 
+A plain run (`--gpus N --steps K --warmup W`) sets up, settles and warms the
+device, times the K steps of `value`, writes the last step's outputs if
+`--dump-outputs DIR` is given, and prints the line.  Everything else below
+(the config 4 / 5 sub-objects, sustained and synchronous-latency legs, the
+achievable read rate, host path, oracle parity, sweeps, the other chunkers,
+`cpu_baseline`) runs only with `--full`, where the `--no-*` options drop
+single legs.
+
 Workloads:
   * `value` (default `--workload stream`, every N): BASELINE configs[1] /
     config 2 -- one 1 GiB stream of splitmix64(seed=1+rank) bytes per GPU,
@@ -31,8 +39,8 @@ duration measured with HIP events around that launch on the engine's stream,
 over the synchronous calls of latency_leg (rank 0, N=1), where each scan has
 the chip to itself: the headline's two-stream schedule starts each scan while
 the previous resolve still holds CUs, so its event span includes that wait
-(reported beside it as `kernel_ms_in_pipeline`; at N > 1 the roofline uses
-it).
+(reported beside it as `kernel_ms_in_pipeline`; at N > 1, and without
+`--full`, the roofline uses it).
 `roofline.traffic` comes from a PMC file under profiles/ only when that
 file's recorded source digest equals this build's (chunkfs_amd.build).
 `cpu_baseline` times the oracle's scalar C restatement (oracle/cdc_oracle.c)
@@ -59,6 +67,13 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--warmup", type=int, default=10)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run every other leg (sustained / synchronous latency, achievable "
+                        "read rate, host path, oracle parity, sweeps, other chunkers, configs 3 / 4 / 5, CPU "
+                        "baseline); the --no-* / --hash / --cpu-* / --config* options below select among them")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last one computed as DIR/<name>.npy (float64): "
+                        "chunks = the (offset, length) list in HBM, first = each stream's first row in it")
     p.add_argument("--settle-ms", type=float, default=60.0,
                    help="device warm-up before the warmup steps: untimed steps of the workload for this long "
                         "(clocks and the two-stream schedule settle over the first ~20 ms of load); 0 = none")
@@ -294,6 +309,35 @@ def timed_steps(eng, w, steps, warmup, world, red_dev, settle_ms=0.0):
         dist.barrier()
         el = sharding.max_over_ranks(el, red_dev)
     return el, first, tims
+
+
+DUMP_BUDGET = 60_000_000  # bytes of .npy data per run, over every rank (kept under 64 MB)
+
+
+def dump_outputs(path, w, first, rank, world):
+    """--dump-outputs: what the last timed step handed its caller, as float64
+    .npy files (offsets and lengths are < 2^53, so exact): `first` (the
+    returned first[n+1]) and `chunks` (rows [0, first[n]) of the Chunk{offset,
+    length} list in HBM).  A list larger than this rank's share of DUMP_BUDGET
+    is cut to a fixed seeded sample of its rows (ascending; their indices in
+    `chunks_rows`).  Rank r > 0 writes <name>_rank<r>.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    fa = np.asarray(first, dtype=np.float64)
+    np.save(os.path.join(path, f"first{sfx}.npy"), fa)
+    if w.out is None:  # (stub engine: no chunk list)
+        return
+    n = int(first[-1])
+    rows_max = max(1, (DUMP_BUDGET // world - fa.nbytes) // 24)  # 16 B per row + 8 B per kept index
+    if n <= rows_max:
+        chunks = w.out[:n].cpu().numpy()
+    else:
+        import torch
+        rows = np.sort(np.random.default_rng(12345).choice(n, size=rows_max, replace=False))
+        chunks = w.out[torch.from_numpy(rows).to(w.out.device)].cpu().numpy()
+        np.save(os.path.join(path, f"chunks_rows{sfx}.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, f"chunks{sfx}.npy"), chunks.astype(np.float64))
 
 
 def latency_leg(eng, w, reps=20):
@@ -1046,9 +1090,11 @@ def main(argv=None):
     if args.settle_ms > 0:
         _SETTLE.append((eng, w, args.settle_ms))
     elapsed, first, tims = timed_steps(eng, w, args.steps, args.warmup, world, red_dev, args.settle_ms)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, w, first, rank, world)
 
     bytes_rank = sum(shard.lens)
-    read_gbs, read_ms = eng.read_bw(w) if shard.lens and shard.lens[0] else (None, None)
+    read_gbs, read_ms = eng.read_bw(w) if args.full and shard.lens and shard.lens[0] else (None, None)
     total_bytes = sharding.sum_over_ranks(bytes_rank, red_dev) * args.steps
     value = sharding.aggregate_gibps(total_bytes, elapsed)
     tims = tims or [dict(scan_ms=0.0, total_ms=0.0, resolve_ms=0.0, fixup_iterations=0, timed=0)]  # (none timed)
@@ -1061,13 +1107,14 @@ def main(argv=None):
 
     extras = {}
     pipe_scan_ms = scan_avg_ms
-    if rank == 0 and world == 1 and not args.stub and shard.lens and shard.lens[0]:
+    solo = args.full and rank == 0 and world == 1 and not args.stub  # the N=1 legs of --full
+    if solo and shard.lens and shard.lens[0]:
         extras["sustained"] = sustained_leg(eng, w, ms_per_step)
         extras["latency_sync"] = latency_leg(eng, w)
         if extras["latency_sync"]["scan_ms_mean"]:
             scan_avg_ms = extras["latency_sync"]["scan_ms_mean"]  # the scan alone (module docstring)
             achieved = bytes_rank / (scan_avg_ms * 1e-3) / 1e9
-    if rank == 0 and world == 1 and not args.stub:
+    if solo:
         if args.hash and shard.lens[0]:
             n0 = int(first[1]) - int(first[0])
             dig = torch.empty((max(n0, 1), 32), dtype=torch.uint8, device=dev)
@@ -1114,12 +1161,12 @@ def main(argv=None):
             ok &= int(got.shape == ref.shape and bool((got == ref).all()))
         extras["parity_all_ranks"] = bool(sharding.min_over_ranks(ok, red_dev)) if world > 1 else bool(ok)
 
-    if not args.no_config4 and args.workload == "stream":
+    if args.full and not args.no_config4 and args.workload == "stream":
         del w
         c4 = config4_leg(args, eng, rank, world, red_dev)
         if rank == 0:
             extras["config4"] = c4
-    if not args.no_config5 and not args.stub and args.workload == "stream":
+    if args.full and not args.no_config5 and not args.stub and args.workload == "stream":
         c5 = config5_leg(args, eng, rank, world, red_dev)
         if rank == 0:
             extras["config5"] = c5

@@ -50,9 +50,9 @@ def test_abi_version_matches_header():
     assert f"abi {m.group(1)}" in _lib.lib().cdc_version().decode()
 
 
-def test_header_compiles_as_c():
+def test_header_compiles_as_c(tmp_path):
     src = '#include "chunkfs_amd.h"\nint main(void){cdc_chunk_t c={0,0};(void)c;return sizeof(cdc_chunk_t)==16?0:1;}\n'
-    exe = "/tmp/_abi_c_test"
+    exe = str(tmp_path / "_abi_c_test")
     subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
                     "-x", "c", "-", "-o", exe], input=src.encode(), check=True)
     assert subprocess.call([exe]) == 0

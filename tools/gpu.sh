@@ -9,7 +9,7 @@
 #   tools/gpu.sh pmc TAG                      scan PMC passes (tools/pmc.sh)
 mkdir -p gpurun_out && export TMPDIR=/tmp
 cmd=$1; T=$2; shift 2
-HEAD="--cpu-seconds 0 --no-host-path --no-sweep --no-algos --no-config4 --no-config5"
+HEAD="--full --cpu-seconds 0 --no-host-path --no-sweep --no-algos --no-config4 --no-config5"
 case $cmd in
 tests)
   timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread "$@" \

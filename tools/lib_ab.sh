@@ -4,7 +4,7 @@
 # "main" = the in-tree library).
 mkdir -p gpurun_out
 T=$1; REPS=$2; shift 2
-H="--cpu-seconds 0 --no-host-path --no-algos --no-config4 --no-config5"
+H="--full --cpu-seconds 0 --no-host-path --no-algos --no-config4 --no-config5"
 for rep in $(seq 1 $REPS); do
   for v in "$@"; do
     n=$(basename $(dirname $v)); [ $v = main ] && n=main

@@ -6,7 +6,7 @@ TAG=${1:-r02}
 OUT=gpurun_out/sha_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python3 bench.py --hash --steps 2 --warmup 1 --cpu-seconds 0 --no-parity --no-host-path --no-sweep"
+CMD="python3 bench.py --full --hash --steps 2 --warmup 1 --cpu-seconds 0 --no-parity --no-host-path --no-sweep"
 timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- $CMD \
     > $OUT/trace.log 2>&1 || { echo "trace rc=$?"; exit 1; }
 timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES SQ_INSTS_SALU SQ_BUSY_CYCLES --kernel-include-regex sha256 \

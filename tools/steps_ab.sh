@@ -2,7 +2,7 @@
 # Headline ms/step of the driver's command shape (--steps 20 --warmup 5) and
 # a longer run, two-stream default vs one stream (diagnostics).
 mkdir -p gpurun_out
-H="--cpu-seconds 0 --no-host-path --no-sweep --no-algos --no-config4 --no-config5 --no-parity"
+H="--full --cpu-seconds 0 --no-host-path --no-sweep --no-algos --no-config4 --no-config5 --no-parity"
 T=${1:-r06s}
 for rep in 1 2; do
 for v in "CHUNKFS_AMD_X=1" "CHUNKFS_AMD_OVERLAP=0"; do
