@@ -435,11 +435,12 @@ class StreamWriter:
 def host_stats(chunker):
     """cdc_debug_host_stats: chunk_data calls, upload s, total s; streaming
     write chunking s and segments; one-launch small-stream calls and how many
-    of them fell back to the regular pipeline."""
-    v = (ctypes.c_double * 7)()
-    check(lib().cdc_debug_host_stats(chunker._h, v, 7))
+    of them fell back to the regular pipeline; chunk lists that failed the
+    host guard at first read (guard_trips, expected 0)."""
+    v = (ctypes.c_double * 8)()
+    check(lib().cdc_debug_host_stats(chunker._h, v, 8))
     return {"calls": int(v[0]), "upload_s": v[1], "total_s": v[2], "write_chunk_s": v[3], "write_segments": int(v[4]),
-            "small_calls": int(v[5]), "small_fallbacks": int(v[6])}
+            "small_calls": int(v[5]), "small_fallbacks": int(v[6]), "guard_trips": int(v[7])}
 
 
 def host_placement(chunker):

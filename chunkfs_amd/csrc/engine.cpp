@@ -227,6 +227,7 @@ struct Engine::WalkWorker {
     cdc_chunk_t *out = nullptr;
     size_t cap = 0;
     uint64_t *first = nullptr;
+    hipEvent_t after = nullptr;  // recorded on the caller's stream at submit: the batch's input is complete there
     int64_t rc = 0;
     std::string err;
 
@@ -238,8 +239,15 @@ struct Engine::WalkWorker {
             if (has_job) {  // (a stop request waits for the batch in hand)
                 has_job = false;
                 lk.unlock();
-                const int64_t r =
-                    ctx->chunk_batch_device(ptrs.size(), ptrs.data(), lens.data(), out, cap, first, nullptr);
+                // the context's stream runs nothing of this batch before the
+                // caller's stream reached the submit
+                int64_t r = CDC_OK;
+                if (hipStreamWaitEvent(ctx->own_stream_, after, 0) != hipSuccess) {
+                    set_error("walk batch: hipStreamWaitEvent on the caller's stream failed");
+                    r = CDC_EDEVICE;
+                }
+                if (r == CDC_OK)
+                    r = ctx->chunk_batch_device(ptrs.size(), ptrs.data(), lens.data(), out, cap, first, nullptr);
                 std::string e = r < 0 ? std::string(last_error()) : std::string();
                 lk.lock();
                 rc = r;
@@ -261,6 +269,7 @@ struct Engine::WalkWorker {
         }
         cv.notify_all();
         if (th.joinable()) th.join();
+        if (after) (void)hipEventDestroy(after);
         delete ctx;
     }
 };
@@ -467,7 +476,7 @@ int64_t Engine::drain_implicit() {
 // default), once that context's previous batch is done; a failure of that batch fails this
 // call (after the other context is drained), as FastCDC's collection does.
 int64_t Engine::walk_submit(size_t n, const uint8_t *const *d_streams, const uint64_t *lens, cdc_chunk_t *d_out,
-                            size_t out_cap, uint64_t *first) {
+                            size_t out_cap, uint64_t *first, hipStream_t s) {
     const int c = (int)(wk_seq_ % (uint64_t)walk_ctx_);
     if (!ww_[c]) {
         Engine *e = nullptr;
@@ -482,6 +491,7 @@ int64_t Engine::walk_submit(size_t n, const uint8_t *const *d_streams, const uin
         std::unique_ptr<WalkWorker> w(new WalkWorker());
         w->ctx = e;
         w->device = device_;
+        HIP_TRY(hipEventCreateWithFlags(&w->after, hipEventDisableTiming));
         WalkWorker *wp = w.get();
         w->th = std::thread([wp] { wp->loop(); });
         ww_[c] = std::move(w);
@@ -498,6 +508,8 @@ int64_t Engine::walk_submit(size_t n, const uint8_t *const *d_streams, const uin
             set_error(msg);
             return rc;
         }
+        // (the context's previous batch is done: its wait on this event is long past)
+        HIP_TRY(hipEventRecord(w.after, s));
         w.ptrs.assign(d_streams, d_streams + n);
         w.lens.assign(lens, lens + n);
         w.out = d_out;
@@ -585,7 +597,7 @@ int64_t Engine::batch_device(size_t n, const uint8_t *const *d_streams, const ui
     // FastCDC multi-megabyte batches are pipelined; everything else runs to
     // completion here, after the batches in flight.
     if (async && is_walk() && walk_async_ && n > 0 && bytes > kSmallBatch)
-        return walk_submit(n, d_streams, lens, d_out, out_cap, first);
+        return walk_submit(n, d_streams, lens, d_out, out_cap, first, s);
     const bool pipe = algo_ == CDC_ALGO_FASTCDC && n > 0 && bytes > kSmallBatch;
     if (!pipe && fb_any_) {
         const int64_t r = drain_implicit();

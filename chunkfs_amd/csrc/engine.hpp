@@ -103,7 +103,8 @@ class Engine {
     int64_t write_finish(std::vector<uint64_t> &spans, double *seconds);
     int64_t write_drain(uint64_t *out, size_t cap);
     // Host-path statistics: calls, upload s, total s of chunk_host; chunking s
-    // and segments of the current / last streaming write.
+    // and segments of the current / last streaming write; small-kernel calls
+    // and fallbacks; chunk_host's guard trips.
     int host_stats(double *v, size_t n) const;
     int64_t host_placement_json(char *out, size_t cap);
     // SHA-256 of chunks of one device-resident stream (Sha256Hasher::hash).
@@ -173,8 +174,10 @@ class Engine {
     // each on its own host worker thread, so one batch's walks and fix-up
     // rounds overlap the next batch's bitmap pass on the device (a walk call
     // keeps host logic between its kernels: the round loop).
+    // The batch is ordered after the work already on `s` (the caller's stream):
+    // an event recorded there, which the context's stream waits for.
     int64_t walk_submit(size_t n, const uint8_t *const *d_streams, const uint64_t *lens, cdc_chunk_t *d_out,
-                        size_t out_cap, uint64_t *first);
+                        size_t out_cap, uint64_t *first, hipStream_t s);
     int64_t walk_drain();  // fast_drain's part for these batches
     struct WalkWorker;
     static constexpr int kWalkCtxMax = 4;
@@ -346,6 +349,7 @@ class Engine {
     } wr_;
     struct HostStats {
         uint64_t calls = 0;
+        uint64_t guard_trips = 0;  // chunk lists that did not tile their buffer at first read (chunk_host)
         double upload_s = 0, total_s = 0;
     } host_;
     uint8_t *d_data_ = nullptr;

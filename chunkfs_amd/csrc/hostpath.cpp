@@ -437,6 +437,31 @@ int64_t Engine::chunk_host(const uint8_t *data, size_t len, cdc_chunk_t *out, si
         count = chunk_batch_device(1, &p, &l, reinterpret_cast<cdc_chunk_t *>(d_hout_), need, first, own_stream_);
         small_skip_ = false;
         if (count < 0) return count;
+        // The done word the collection spins on says the resolve's last block
+        // is through; the list is read only once the stream itself has retired
+        // (calls above 4 MiB by default, every call with the small kernel off).
+        HIP_TRY(hipStreamSynchronize(own_stream_));
+    }
+    // Host guard, both branches: a chunk list tiles the call's bytes -- offsets
+    // contiguous from 0, lengths summing to len.  A list that does not is read
+    // again after a stream sync (counted: cdc_debug_host_stats' last slot, which
+    // the suite asserts stays 0), and refused if it is still wrong.
+    auto tiles = [&]() {
+        const volatile cdc_chunk_t *c = h_out_;  // (the device writes it: read afresh each time)
+        uint64_t at = 0;
+        for (int64_t i = 0; i < count; ++i) {
+            if (c[i].offset != at) return false;
+            at += c[i].length;
+        }
+        return at == (uint64_t)len;
+    };
+    if (!tiles()) {
+        host_.guard_trips += 1;
+        HIP_TRY(hipStreamSynchronize(own_stream_));
+        if (!tiles()) {
+            set_error("cdc_chunk_data: the chunk list does not tile the buffer (internal error)");
+            return CDC_EDEVICE;
+        }
     }
     const size_t copy = (size_t)count < cap ? (size_t)count : cap;
     if (digests && copy) {
@@ -640,9 +665,9 @@ int64_t Engine::host_placement_json(char *out, size_t cap) {
 }
 
 int Engine::host_stats(double *v, size_t n) const {
-    const double s[7] = {(double)host_.calls, host_.upload_s, host_.total_s, wr_.chunk_s, (double)wr_.segments,
-                         (double)small_calls_, (double)small_fallbacks_};
-    for (size_t i = 0; i < n && i < 7; ++i) v[i] = s[i];
+    const double s[8] = {(double)host_.calls, host_.upload_s, host_.total_s, wr_.chunk_s, (double)wr_.segments,
+                         (double)small_calls_, (double)small_fallbacks_, (double)host_.guard_trips};
+    for (size_t i = 0; i < n && i < 8; ++i) v[i] = s[i];
     return CDC_OK;
 }
 

@@ -153,8 +153,17 @@ int64_t cdc_chunk_batch_device(cdc_handle_t *h, size_t n,
  * round trip between them, their results collected later: the scans on
  * hip_stream, each resolve on a second stream of the handle behind its scan,
  * beside the next scan (CHUNKFS_AMD_OVERLAP=0 keeps both on hip_stream);
- * cdc_batch_sync orders hip_stream after the resolves.  d_streams' bytes and
- * d_out must stay untouched until cdc_batch_sync.
+ * cdc_batch_sync orders hip_stream after the resolves.
+ * Ordering, every algorithm: the batch reads d_streams' bytes after all work
+ * enqueued on hip_stream (NULL: the handle's own stream) before this call --
+ * input written by kernels or copies on hip_stream needs no host wait before
+ * the submit.  FastCDC's scans run on hip_stream itself; a Rabin / Ultra /
+ * Leap / Seq batch runs on a context's stream, which waits for an event
+ * recorded on hip_stream at the submit.  Work on other streams is the
+ * caller's to order.  d_streams' bytes and d_out must stay untouched from the
+ * submit until cdc_batch_sync (work enqueued on hip_stream after the submit is
+ * ordered after a FastCDC batch's scan only, and after nothing of a walk
+ * batch).
  * Consecutive async batches of one handle must use one hip_stream (another
  * stream first completes the batches in flight).  Rabin / Ultra / Leap / Seq
  * batches of more than 8 MiB alternate between two internal contexts of the

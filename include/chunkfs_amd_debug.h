@@ -29,7 +29,9 @@ int64_t cdc_debug_copy(cdc_handle_t *h, int what, void *out, size_t max_bytes);
  * seconds, then the chunking seconds and segment count of the current or
  * last streaming write (cdc_write_*), then the FastCDC batches taken by the
  * one-launch small-stream kernel (small.hip) and how many of them fell back
- * to the regular pipeline (a record / start budget exceeded). */
+ * to the regular pipeline (a record / start budget exceeded), then the
+ * cdc_chunk_data calls whose chunk list did not tile the buffer when first
+ * read and was read again after a stream synchronisation (expected 0). */
 int cdc_debug_host_stats(const cdc_handle_t *h, double *v, size_t n);
 /* Kernel times of the FastCDC batch `back` calls before the last one (0 = the
  * last; up to 63 back): scan_ms, resolve_ms, total_ms of t (the other fields

@@ -4,8 +4,10 @@ Batches of more than 8 MiB are enqueued back to back with no host wait, each
 with its own host staging block (three in rotation) and device table slot
 (four); results are collected later.  Where the sizes allow (avg 8 KiB and up
 at max <= 64 KiB) each batch's resolve runs on a second stream beside the
-next batch's scan (the overlap kernel set, fastcdc_ovl.hip).  Every batch's chunks must equal the
-oracle's, whatever the interleaving: multi-stream batches,
+next batch's scan, with the regular kernels (fastcdc.hip) by default; the
+overlap kernel set (fastcdc_ovl.hip) only with CHUNKFS_AMD_OVERLAP=1, and
+CHUNKFS_AMD_OVERLAP=0 keeps both on one stream.  Every batch's chunks must
+equal the oracle's, whatever the interleaving: multi-stream batches,
 ragged and empty streams, different outputs per batch, bursts ended by
 cdc_batch_sync or by a synchronous call, and small batches that complete
 inside the call.  Parity vs the fastcdc crate is unpinned (GEAR placeholder,
