@@ -14,6 +14,8 @@ include/chunkfs_amd.h (libchunkfs_amd.so, hand-written HIP for gfx950):
                                               unpinned: cdc-chunkers 0.1.3 absent)
     SuperChunker                              raises NotImplementedError
     ChunkStorage::write  system/storage.rs    write_spans()
+    Database (digest set) system/database.rs  DedupIndex
+    Database + retrieve / read_file_complete  ChunkStore
 
 Every call runs on the GPU.  There is no CPU fallback: without the built
 library or a gfx950 device the constructors raise.
@@ -34,6 +36,7 @@ __all__ = [
     "KB", "MB", "GB", "SEG_SIZE", "Chunk", "SizeParams", "Chunker", "FastChunker",
     "FSChunker", "RabinChunker", "SuperChunker", "UltraChunker", "LeapChunker",
     "SeqChunker", "OperationMode", "SeqConfig", "CdcError", "write_spans", "StreamWriter", "version",
+    "DedupIndex", "ChunkStore",
 ]
 
 
@@ -487,6 +490,112 @@ class DedupIndex:
         d["cdc_dedup_ratio"] = d["bytes_written"] / d["unique_bytes"] if d["unique_bytes"] else float("nan")
         d["average_chunk_size"] = d["unique_bytes"] // d["unique_chunks"] if d["unique_chunks"] else 0
         return d
+
+
+def _ptr(p):
+    return None if p is None else ctypes.c_void_p(int(p))
+
+
+class ChunkStore:
+    """The reference's key -> data Database (database.rs:10-36, 74-87, first
+    insert wins) with ChunkStorage::retrieve (storage.rs:141-157) and
+    FileSystem::read_file_complete (system/mod.rs:149-160) on one GPU: a dedup
+    index plus an HBM arena of `arena_bytes` holding each first-seen chunk.
+    A refused call (CdcError) changes nothing.  Not thread-safe."""
+
+    def __init__(self, max_chunks, arena_bytes, device=0):
+        h = ctypes.c_void_p()
+        check(lib().cdc_store_create(device, max_chunks, arena_bytes, ctypes.byref(h)))
+        self._h = h
+        self.device = device
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            lib().cdc_store_destroy(h)
+            self._h = None
+
+    def put_device(self, d_data, data_len, d_chunks, d_digests, n, d_new=None, stream=None):
+        """Database::insert of n (digest, chunk of d_data) pairs (device pointers),
+        in chunk order.  Returns the number of new digests; d_new (optional
+        u8[n]) marks them."""
+        return check(lib().cdc_store_put_device(self._h, _ptr(d_data), data_len, _ptr(d_chunks),
+                                                _ptr(d_digests), n, _ptr(d_new), _ptr(stream)))
+
+    def put_batch_device(self, d_ptrs, lens, first, d_chunks, d_digests, d_new=None, stream=None):
+        """The same for the output of chunk_batch_device + sha256_batch_device:
+        stream i's chunks are d_chunks[first[i] .. first[i+1]), offsets relative
+        to d_ptrs[i]."""
+        ptrs = np.ascontiguousarray(np.asarray(d_ptrs, dtype=np.uint64))
+        lens_a = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64))
+        fa = np.ascontiguousarray(np.asarray(first, dtype=np.uint64))
+        assert lens_a.size == ptrs.size and fa.size == ptrs.size + 1
+        return check(lib().cdc_store_put_batch_device(
+            self._h, int(ptrs.size), ctypes.c_void_p(ptrs.ctypes.data), ctypes.c_void_p(lens_a.ctypes.data),
+            ctypes.c_void_p(fa.ctypes.data), _ptr(d_chunks), _ptr(d_digests), _ptr(d_new), _ptr(stream)))
+
+    def get_device(self, d_digests, n, d_out, out_cap, d_spans=None, stream=None):
+        """ChunkStorage::retrieve(..).concat(): the chunks of n digests, in request
+        order, back to back in d_out.  Returns the total byte count; a return >
+        out_cap means nothing was written (out_cap = 0 sizes a read).  Raises
+        CdcError(CDC_ENOTFOUND) if a digest is absent."""
+        return check(lib().cdc_store_get_device(self._h, _ptr(d_digests), n, _ptr(d_out), out_cap,
+                                                _ptr(d_spans), _ptr(stream)))
+
+    def contains_device(self, d_digests, n, d_found=None, stream=None):
+        """Database::contains for n digests: how many are stored; d_found
+        (optional u8[n]) marks them."""
+        return check(lib().cdc_store_contains_device(self._h, _ptr(d_digests), n, _ptr(d_found), _ptr(stream)))
+
+    def clear(self):
+        check(lib().cdc_store_clear(self._h))
+
+    def stats(self):
+        s = _lib.cdc_store_stats_t()
+        check(lib().cdc_store_stats(self._h, ctypes.byref(s)))
+        d = {f: getattr(s.index, f) for f, _ in _lib.cdc_index_stats_t._fields_}
+        d["arena_used"], d["arena_capacity"] = s.arena_used, s.arena_capacity
+        d["cdc_dedup_ratio"] = d["bytes_written"] / d["unique_bytes"] if d["unique_bytes"] else float("nan")
+        d["average_chunk_size"] = d["unique_bytes"] // d["unique_chunks"] if d["unique_chunks"] else 0
+        return d
+
+    # -- host conveniences over the calls above --------------------------------
+    def write(self, chunker, data):
+        """One file write: chunk and hash `data` (host bytes) with `chunker`, put
+        every chunk.  Returns ((n, 2) chunks, (n, 32) digests, (n,) bool new):
+        keep the digests, they are the file's spans for read()."""
+        import torch
+        chunks, dig = chunker.chunk_and_hash(data)
+        _, nbytes, arr = _as_buffer(data)
+        n = len(chunks)
+        if n == 0:
+            return chunks, dig, np.zeros(0, dtype=bool)
+        dev = f"cuda:{self.device}"
+        d_data = torch.from_numpy(arr.copy()).to(dev)
+        d_dig = torch.from_numpy(np.ascontiguousarray(dig)).to(dev)
+        d_chunks = torch.from_numpy(np.ascontiguousarray(chunks).view(np.int64)).to(dev)
+        d_new = torch.empty(n, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        self.put_device(d_data.data_ptr(), nbytes, d_chunks.data_ptr(), d_dig.data_ptr(), n, d_new.data_ptr())
+        return chunks, dig, d_new.cpu().numpy().astype(bool)
+
+    def read(self, digests):
+        """FileSystem::read_file_complete: the bytes of the chunks named by
+        `digests` ((n, 32) uint8), concatenated, as a host uint8 array."""
+        import torch
+        dig = np.ascontiguousarray(np.asarray(digests, dtype=np.uint8)).reshape(-1, 32)
+        n = len(dig)
+        if n == 0:
+            return np.zeros(0, dtype=np.uint8)
+        dev = f"cuda:{self.device}"
+        d_dig = torch.from_numpy(dig).to(dev)
+        torch.cuda.synchronize(dev)
+        total = self.get_device(d_dig.data_ptr(), n, None, 0)
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        got = self.get_device(d_dig.data_ptr(), n, out.data_ptr(), total)
+        assert got == total
+        return out[:total].cpu().numpy()
 
 
 def version():

@@ -15,6 +15,7 @@ CDC_EINVAL = -1
 CDC_ENOMEM = -2
 CDC_EDEVICE = -3
 CDC_ENOTSUP = -4
+CDC_ENOTFOUND = -5
 
 ALGO = {"fast": 0, "fixed": 1, "rabin": 2, "super": 3, "ultra": 4, "leap": 5, "seq": 6}
 
@@ -28,6 +29,8 @@ EXPORTS = [
     "cdc_sha256_chunks_device", "cdc_sha256_batch_device", "cdc_chunk_and_hash",
     "cdc_index_create", "cdc_index_destroy", "cdc_index_clear", "cdc_index_insert_device",
     "cdc_index_stats",
+    "cdc_store_create", "cdc_store_destroy", "cdc_store_clear", "cdc_store_stats", "cdc_store_put_device",
+    "cdc_store_put_batch_device", "cdc_store_get_device", "cdc_store_contains_device",
     "cdc_fill_splitmix64_device", "cdc_version", "cdc_abi_version",
 ]
 # include/chunkfs_amd_debug.h (diagnostics, not part of the drop-in boundary)
@@ -49,6 +52,11 @@ class cdc_chunk_t(ctypes.Structure):
 class cdc_index_stats_t(ctypes.Structure):
     _fields_ = [("chunks_written", ctypes.c_uint64), ("bytes_written", ctypes.c_uint64),
                 ("unique_chunks", ctypes.c_uint64), ("unique_bytes", ctypes.c_uint64)]
+
+
+class cdc_store_stats_t(ctypes.Structure):
+    _fields_ = [("index", cdc_index_stats_t), ("arena_capacity", ctypes.c_uint64),
+                ("arena_used", ctypes.c_uint64)]
 
 
 class cdc_timing_t(ctypes.Structure):
@@ -158,6 +166,22 @@ def lib():
     L.cdc_index_insert_device.restype = ctypes.c_int64
     L.cdc_index_stats.argtypes = [P, ctypes.POINTER(cdc_index_stats_t)]
     L.cdc_index_stats.restype = ctypes.c_int
+    L.cdc_store_create.argtypes = [ctypes.c_int, sz, sz, ctypes.POINTER(P)]
+    L.cdc_store_create.restype = ctypes.c_int
+    L.cdc_store_destroy.argtypes = [P]
+    L.cdc_store_destroy.restype = None
+    L.cdc_store_clear.argtypes = [P]
+    L.cdc_store_clear.restype = ctypes.c_int
+    L.cdc_store_stats.argtypes = [P, ctypes.POINTER(cdc_store_stats_t)]
+    L.cdc_store_stats.restype = ctypes.c_int
+    L.cdc_store_put_device.argtypes = [P, P, sz, P, P, sz, P, P]
+    L.cdc_store_put_device.restype = ctypes.c_int64
+    L.cdc_store_put_batch_device.argtypes = [P, sz, P, P, P, P, P, P, P]
+    L.cdc_store_put_batch_device.restype = ctypes.c_int64
+    L.cdc_store_get_device.argtypes = [P, P, sz, P, sz, P, P]
+    L.cdc_store_get_device.restype = ctypes.c_int64
+    L.cdc_store_contains_device.argtypes = [P, P, sz, P, P]
+    L.cdc_store_contains_device.restype = ctypes.c_int64
     L.cdc_fill_splitmix64_device.argtypes = [P, sz, ctypes.c_uint64, P]
     L.cdc_fill_splitmix64_device.restype = ctypes.c_int
     L.cdc_debug_pipeline.argtypes = [P]

@@ -29,8 +29,9 @@ extern "C" {
  *    may grow; fields are only ever appended); cdc_abi_version().
  * 3: cdc_timing_t.path / .timed appended; cdc_chunk_batch_device_async,
  *    cdc_batch_sync.
- * 4: cdc_sha256_batch_device. */
-#define CHUNKFS_AMD_ABI_VERSION 4
+ * 4: cdc_sha256_batch_device.
+ * 5: cdc_store_* (device chunk store), CDC_ENOTFOUND. */
+#define CHUNKFS_AMD_ABI_VERSION 5
 
 /* Chunk{offset,length} -- reference src/lib.rs:43-47 (usize fields; u64 here). */
 typedef struct cdc_chunk {
@@ -55,6 +56,7 @@ typedef enum cdc_algo {
 #define CDC_ENOMEM (-2)  /* device or host allocation failed */
 #define CDC_EDEVICE (-3) /* HIP runtime error, or no usable gfx950 device */
 #define CDC_ENOTSUP (-4) /* algorithm not implemented */
+#define CDC_ENOTFOUND (-5) /* a requested digest is not in the store (reference: ErrorKind::NotFound) */
 
 typedef struct cdc_handle cdc_handle_t;
 
@@ -318,6 +320,94 @@ int64_t cdc_index_insert_device(cdc_index_t *ix, const uint8_t *d_digests,
                                 const cdc_chunk_t *d_chunks, size_t n,
                                 uint8_t *d_new, void *hip_stream);
 int cdc_index_stats(const cdc_index_t *ix, cdc_index_stats_t *out);
+
+/* ---- Chunk store ----------------------------------------------------------------
+ * The reference's key -> data Database (src/system/database.rs:10-36, 74-87:
+ * insert / get / get_multi / contains, the FIRST insert of a key wins),
+ * ChunkStorage::retrieve (src/system/storage.rs:141-157) and
+ * FileSystem::read_file_complete / read_from_file (src/system/mod.rs:149-160:
+ * look up every span's hash, concatenate), on one GPU: a dedup index as above
+ * plus an HBM arena that holds the bytes of each first-seen chunk.
+ *
+ * Stream ordering: every call runs on hip_stream (NULL = the store's own
+ * non-blocking stream) and synchronises it before returning, as
+ * cdc_index_insert_device does.  Input written by earlier work on hip_stream
+ * needs no host wait.  One store is NOT thread-safe; different stores may be
+ * used concurrently.
+ *
+ * A refused call changes nothing.  put first runs a small kernel over the chunk
+ * list and checks on the host, before it touches the table or the arena:
+ *   every chunk lies inside its buffer (offset + length <= data_len / lens[i],
+ *     computed without overflow), else CDC_EINVAL;
+ *   unique_chunks + n <= max_chunks, else CDC_ENOMEM;
+ *   arena_used + sum of round_up(length, 16) over ALL n chunks <= arena_capacity,
+ *     else CDC_ENOMEM
+ * -- "as if every chunk were new", the index's own rule.  After a refused put,
+ * get or contains the stats equal those before and every stored digest is
+ * still retrievable.  Result-dependent errors are the index's: a full table or
+ * too many 64-bit key collisions return its error (CDC_ENOMEM).
+ *
+ * Lookup compares the full 32-byte digest and goes on probing past a slot whose
+ * 64-bit key matches but whose digest differs (the index places such a digest
+ * further along the probe sequence); it stops at an empty slot or after
+ * `slots` probes.
+ *
+ * Arena layout: stored chunks start at 16-byte multiples.  The new chunks of a
+ * put are laid out in chunk order -- an exclusive scan of the padded lengths
+ * over the `new` flags, starting at arena_used -- so the layout is
+ * deterministic.  Padding bytes are unspecified.  Length-0 chunks are legal:
+ * stored with no bytes, returned as an empty span.  Offsets and lengths are 64
+ * bits throughout. */
+typedef struct cdc_store cdc_store_t;
+
+typedef struct cdc_store_stats {
+    cdc_index_stats_t index;  /* same meaning as cdc_index_stats */
+    uint64_t arena_capacity;  /* bytes */
+    uint64_t arena_used;      /* bytes, including the 16-byte padding of each stored chunk */
+} cdc_store_stats_t;
+
+/* Store on `device` for up to max_chunks distinct digests and arena_bytes of
+ * chunk data (neither grows later). */
+int cdc_store_create(int device, size_t max_chunks, size_t arena_bytes, cdc_store_t **out);
+void cdc_store_destroy(cdc_store_t *st);
+/* clear_database (storage.rs:236-240): empties the table, arena_used = 0. */
+int cdc_store_clear(cdc_store_t *st);
+int cdc_store_stats(const cdc_store_t *st, cdc_store_stats_t *out);
+
+/* Database::insert of n (digest, chunk bytes) pairs in chunk order; chunk i is
+ * d_data[d_chunks[i].offset .. +length) (DEVICE arrays; d_data at any
+ * alignment).  The first insert of a digest wins, within the batch and across
+ * calls; only first occurrences are copied into the arena.  d_new (nullable,
+ * DEVICE u8[n]) as in cdc_index_insert_device.  Returns the number of new
+ * digests. */
+int64_t cdc_store_put_device(cdc_store_t *st, const uint8_t *d_data, size_t data_len,
+                             const cdc_chunk_t *d_chunks, const uint8_t *d_digests,
+                             size_t n, uint8_t *d_new, void *hip_stream);
+
+/* The same for the output of cdc_chunk_batch_device + cdc_sha256_batch_device:
+ * d_streams / lens / first are HOST arrays (n_streams, n_streams, n_streams + 1
+ * entries; first[0] = 0), chunk offsets relative to each stream, n =
+ * first[n_streams].  Global chunk order = stream order. */
+int64_t cdc_store_put_batch_device(cdc_store_t *st, size_t n_streams,
+                                   const uint8_t *const *d_streams, const uint64_t *lens,
+                                   const uint64_t *first, const cdc_chunk_t *d_chunks,
+                                   const uint8_t *d_digests, uint8_t *d_new, void *hip_stream);
+
+/* ChunkStorage::retrieve(...).concat() / Database::get_multi: the chunks of
+ * d_digests[0..n) (DEVICE, 32 bytes each), in request order, back to back in
+ * the DEVICE buffer d_out (any alignment).  d_spans (nullable, DEVICE
+ * cdc_chunk_t[n]) receives each one's {offset in d_out, length}.  Returns the
+ * total byte count (snprintf convention: a return > out_cap means NOTHING was
+ * written to d_out or d_spans; out_cap = 0 sizes a read).  CDC_ENOTFOUND if
+ * any digest is absent (nothing written). */
+int64_t cdc_store_get_device(cdc_store_t *st, const uint8_t *d_digests, size_t n,
+                             uint8_t *d_out, size_t out_cap, cdc_chunk_t *d_spans,
+                             void *hip_stream);
+
+/* Database::contains for n digests: d_found[i] (DEVICE u8[n]) = 1/0.  Returns
+ * how many were found. */
+int64_t cdc_store_contains_device(cdc_store_t *st, const uint8_t *d_digests, size_t n,
+                                  uint8_t *d_found, void *hip_stream);
 
 /* ---- Synthetic data -----------------------------------------
  * Fill a DEVICE buffer with the splitmix64 stream: little-endian u64 words,

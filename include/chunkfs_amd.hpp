@@ -9,6 +9,7 @@
 //   FSChunker                       chunkers/fixed_size.rs  chunkfs_amd::FSChunker
 //   Rabin/Ultra/Leap/SeqChunker     chunkers/{rabin,ultra,leap,seq}.rs  same names
 //   ChunkStorage::write spans       system/storage.rs:78-103  Chunker::write_spans
+//   Database + ChunkStorage::retrieve  system/database.rs, storage.rs:141-157  chunkfs_amd::Store
 //
 // The reference panics on invalid sizes; here constructors throw
 // chunkfs_amd::Error (carrying the CDC_E* code and cdc_last_error()).
@@ -185,5 +186,53 @@ class SeqChunker : public Chunker {
 
 // ChunkerRef (src/lib.rs:89): shared handle to one chunker.
 using ChunkerRef = std::shared_ptr<Chunker>;
+
+// Device chunk store: the key -> data Database (system/database.rs:10-36,
+// 74-87, first insert wins), ChunkStorage::retrieve (storage.rs:141-157) and
+// read_file_complete (system/mod.rs:149-160).  All pointers named d_* are
+// DEVICE pointers; a refused call throws and changes nothing.  Not thread-safe.
+class Store {
+  public:
+    Store(size_t max_chunks, size_t arena_bytes, int device = 0) {
+        check(cdc_store_create(device, max_chunks, arena_bytes, &st_));
+    }
+    ~Store() { cdc_store_destroy(st_); }
+    Store(const Store &) = delete;
+    Store &operator=(const Store &) = delete;
+
+    // Database::insert of n (digest, chunk) pairs; returns the number of new digests.
+    int64_t put_device(const uint8_t *d_data, size_t data_len, const cdc_chunk_t *d_chunks, const uint8_t *d_digests,
+                       size_t n, uint8_t *d_new = nullptr, void *hip_stream = nullptr) {
+        return check(cdc_store_put_device(st_, d_data, data_len, d_chunks, d_digests, n, d_new, hip_stream));
+    }
+    // The same for the output of cdc_chunk_batch_device + cdc_sha256_batch_device.
+    int64_t put_batch_device(size_t n_streams, const uint8_t *const *d_streams, const uint64_t *lens,
+                             const uint64_t *first, const cdc_chunk_t *d_chunks, const uint8_t *d_digests,
+                             uint8_t *d_new = nullptr, void *hip_stream = nullptr) {
+        return check(cdc_store_put_batch_device(st_, n_streams, d_streams, lens, first, d_chunks, d_digests, d_new,
+                                                hip_stream));
+    }
+    // retrieve(..).concat(): total bytes; > out_cap means nothing was written.
+    // Throws Error with code CDC_ENOTFOUND if a digest is absent.
+    int64_t get_device(const uint8_t *d_digests, size_t n, uint8_t *d_out, size_t out_cap,
+                       cdc_chunk_t *d_spans = nullptr, void *hip_stream = nullptr) {
+        return check(cdc_store_get_device(st_, d_digests, n, d_out, out_cap, d_spans, hip_stream));
+    }
+    // Database::contains: how many of the n digests are stored.
+    int64_t contains_device(const uint8_t *d_digests, size_t n, uint8_t *d_found = nullptr,
+                            void *hip_stream = nullptr) {
+        return check(cdc_store_contains_device(st_, d_digests, n, d_found, hip_stream));
+    }
+    void clear() { check(cdc_store_clear(st_)); }
+    cdc_store_stats_t stats() const {
+        cdc_store_stats_t s{};
+        check(cdc_store_stats(st_, &s));
+        return s;
+    }
+    cdc_store_t *handle() { return st_; }
+
+  private:
+    cdc_store_t *st_ = nullptr;
+};
 
 }  // namespace chunkfs_amd

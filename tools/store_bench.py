@@ -1,0 +1,151 @@
+#!/usr/bin/env python3
+"""Chunk-store throughput on one GPU: put and get against the device's own copy.
+
+Workload: one splitmix64 device stream (1 GiB by default), FastCDC
+4096/8192/16384, every chunk unique.  Timed warm, with HIP events on one
+stream:
+
+  (a) put_batch_device of the whole stream into an empty store
+      (precheck + index insert + scans + the copy into the arena);
+  (b) get_device of the whole file (lookup + scans + the copy out);
+  (c) hipMemcpyAsync device-to-device of the same bytes, in the same process
+      -- the yardstick: the device's own copy of the same data.
+
+Also timed, to separate the copy kernel from the bookkeeping around it:
+contains_device (the lookup alone) and get_device with out_cap = 0 (lookup +
+scans, no copy); (b) minus the latter is the copy kernel plus the spans.  The
+per-kernel split of put comes from a profiler's kernel trace of
+`store_bench.py --iters 2 --warmup 1` (kernel names: copy_kernel,
+precheck_kernel, scan_*_kernel, lookup_kernel, claim/verify/mark_kernel).
+
+Prints one JSON line; --out also writes it to a file.
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _hip_runtime():
+    """The HIP runtime already mapped into this process (torch's or the system's)."""
+    with open("/proc/self/maps") as f:
+        for line in f:
+            if "libamdhip64" in line:
+                return ctypes.CDLL(line.split()[-1])
+    raise RuntimeError("no HIP runtime is loaded")
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--bytes", type=int, default=1 << 30)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--seed", type=int, default=2024)
+    ap.add_argument("--out", default=None, help="also write the JSON result to this file")
+    a = ap.parse_args()
+
+    import numpy as np
+    import torch
+    import chunkfs_amd as c
+    from chunkfs_amd import _lib, build
+
+    if not torch.cuda.is_available():
+        raise SystemExit("store_bench: no GPU (there is no CPU path to measure)")
+    n = a.bytes
+    ch = c.FastChunker(c.SizeParams(4096, 8192, 16384))
+    buf = torch.empty(n, dtype=torch.uint8, device="cuda")
+    out = torch.empty(n, dtype=torch.uint8, device="cuda")
+    cap = ch.batch_max_chunks([n])
+    chunks = torch.empty((cap, 2), dtype=torch.int64, device="cuda")
+    s = torch.cuda.Stream()
+    sp = s.cuda_stream
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().cdc_fill_splitmix64_device(ctypes.c_void_p(buf.data_ptr()), n, a.seed, ctypes.c_void_p(sp)))
+    first = ch.chunk_batch_device([buf.data_ptr()], [n], chunks.data_ptr(), cap, stream=sp)
+    k = int(first[1])
+    dig = torch.empty((k, 32), dtype=torch.uint8, device="cuda")
+    found = torch.empty(k, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    ch.sha256_batch_device([buf.data_ptr()], first, chunks.data_ptr(), dig.data_ptr(), stream=sp)
+    store = c.ChunkStore(k, n + 16 * k)
+
+    hip = _hip_runtime()
+    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
+    hip.hipMemcpyAsync.restype = ctypes.c_int
+    HIP_MEMCPY_D2D = 3
+
+    def timed(fn, before=None):
+        ms = []
+        for it in range(a.warmup + a.iters):
+            if before:
+                before()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(s)
+            fn()
+            e1.record(s)
+            e1.synchronize()
+            if it >= a.warmup:
+                ms.append(e0.elapsed_time(e1))
+        return ms
+
+    def do_put():
+        got = store.put_batch_device([buf.data_ptr()], [n], first, chunks.data_ptr(), dig.data_ptr(), stream=sp)
+        assert got == k, "the splitmix64 stream must chunk into unique chunks"
+
+    def do_get():
+        assert store.get_device(dig.data_ptr(), k, out.data_ptr(), n, stream=sp) == n
+
+    def do_size():
+        assert store.get_device(dig.data_ptr(), k, None, 0, stream=sp) == n
+
+    def do_contains():
+        assert store.contains_device(dig.data_ptr(), k, found.data_ptr(), stream=sp) == k
+
+    def do_memcpy():
+        rc = hip.hipMemcpyAsync(out.data_ptr(), buf.data_ptr(), n, HIP_MEMCPY_D2D, sp)
+        assert rc == 0, f"hipMemcpyAsync: {rc}"
+
+    t_put = timed(do_put, before=store.clear)
+    out.zero_()
+    t_get = timed(do_get)
+    same = bool(torch.equal(out, buf))  # the file read back is the file written
+    t_size = timed(do_size)
+    t_contains = timed(do_contains)
+    t_memcpy = timed(do_memcpy)
+    if not same:
+        raise SystemExit("store_bench: get_device did not return the bytes put_batch_device stored")
+
+    gib = n / (1 << 30)
+    med = lambda v: float(np.median(v))  # noqa: E731
+
+    def rate(v):
+        return gib / (med(v) * 1e-3)
+
+    copy_ms = med(t_get) - med(t_size)
+    res = {
+        "tool": "store_bench", "bytes": n, "chunks": k, "iters": a.iters, "warmup": a.warmup,
+        "device": torch.cuda.get_device_name(0), "source_digest": build.source_digest(),
+        "put_ms": med(t_put), "get_ms": med(t_get), "memcpy_ms": med(t_memcpy),
+        "put_ms_min_max": [min(t_put), max(t_put)], "get_ms_min_max": [min(t_get), max(t_get)],
+        "memcpy_ms_min_max": [min(t_memcpy), max(t_memcpy)],
+        "put_GiBps": rate(t_put), "get_GiBps": rate(t_get), "memcpy_GiBps": rate(t_memcpy),
+        "put_vs_memcpy": med(t_memcpy) / med(t_put), "get_vs_memcpy": med(t_memcpy) / med(t_get),
+        "contains_ms": med(t_contains), "get_size_only_ms": med(t_size),
+        "get_copy_ms": copy_ms, "get_copy_GiBps": gib / (copy_ms * 1e-3) if copy_ms > 0 else None,
+        "readback_equal": same,
+    }
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
