@@ -114,10 +114,7 @@ int Engine::create(cdc_algo_t algo, uint32_t min, uint32_t avg, uint32_t max,
         fp.mask_l_sh = fp.mask_l << fp.tshift;
         if (const char *d = std::getenv("CHUNKFS_AMD_DIAG")) fp.diag = (uint32_t)std::atoi(d);
         if (const char *v = std::getenv("CHUNKFS_AMD_EVENT_EVERY")) e->event_every_ = std::max(1, std::atoi(v));
-        if (const char *v = std::getenv("CHUNKFS_AMD_OVERLAP")) {  // (A/B; default 2)
-            e->ovl_on_ = std::atoi(v) != 0;
-            e->ovl_std_ = std::atoi(v) != 1;  // 1: the overlap kernel set (fastcdc_ovl.hip)
-        }
+        if (const char *v = std::getenv("CHUNKFS_AMD_OVERLAP")) e->two_stream_on_ = std::atoi(v) != 0;  // (A/B; default on)
         uint32_t l2 = ceil_log2(max);
         e->span_log2_ = l2 > kMinSpanLog2 ? l2 : kMinSpanLog2;
         {
@@ -147,10 +144,6 @@ int Engine::create(cdc_algo_t algo, uint32_t min, uint32_t avg, uint32_t max,
         if (cap > 256) cap = 256;
         e->cap_ = (uint32_t)cap;
         e->smax_ = (uint32_t)(span / ((min / 2) * 2) + 2);
-        // The overlap set's resolve windows hold 384 records (11 spans): keep
-        // it to sizes whose windows expect <= 256 (avg >= 8 KiB at max <= 64
-        // KiB); denser records would send windows to the slow global path.
-        if (11 * (span >> (pc < 63 ? pc : 63)) > 256 && !e->ovl_std_) e->ovl_on_ = false;
         // Small-stream path (small.hip): its per-lane and per-block record
         // budgets assume sparse hits, ~2^-10 per position or rarer.
         const uint32_t pmin = (uint32_t)std::min(__builtin_popcountll(fp.mask_s), __builtin_popcountll(fp.mask_l));
@@ -397,7 +390,7 @@ int Engine::ensure_workspace(uint64_t spans, size_t n) {
     }
     const size_t o_starts = take(S * smax * 8);  // chunk starts beyond the LDS-resident ones
     const size_t o_first = take((N + 1) * 8);
-    const uint64_t nb = std::max(p3::resolve_blocks(S), p3::ovl::resolve_blocks(S)) + 2;
+    const uint64_t nb = p3::resolve_blocks(S) + 2;
     const size_t o_desc = take(6 * nb * 8);
     (void)hipFree(ws_);
     ws_ = nullptr;
@@ -608,7 +601,7 @@ int64_t Engine::batch_device(size_t n, const uint8_t *const *d_streams, const ui
         // reads are recorded on every event_every_-th batch only -- each
         // event costs the stream ~4 us, r05t)
         const int64_t r = fast_submit(n, d_streams, lens, d_out, out_cap, first, bytes, s,
-                                      !async || fb_seq_ % event_every_ == 0, async && ovl_on_);
+                                      !async || fb_seq_ % event_every_ == 0, async && two_stream_on_);
         if (r < 0 || async) return r;
         return fast_drain();
     }
@@ -689,12 +682,12 @@ int64_t Engine::batch_device(size_t n, const uint8_t *const *d_streams, const ui
 // the resolve launches; no host wait.  The host collects it (fast_collect)
 // when its stats block is needed again or at fast_drain().
 int64_t Engine::fast_submit(size_t n, const uint8_t *const *d_streams, const uint64_t *lens, cdc_chunk_t *d_out,
-                            size_t out_cap, uint64_t *first, uint64_t bytes, hipStream_t s, bool timed, bool ovl) {
-    if (fb_any_ && (s != fb_stream_ || ovl != fb_ovl_)) {  // one pipeline per stream (and kernel set)
+                            size_t out_cap, uint64_t *first, uint64_t bytes, hipStream_t s, bool timed, bool two_stream) {
+    if (fb_any_ && (s != fb_stream_ || two_stream != fb_two_stream_)) {  // one pipeline per stream (pair)
         const int64_t r = drain_implicit();
         if (r < 0) return r;
     }
-    if (ovl && !res_stream_) {
+    if (two_stream && !res_stream_) {
         HIP_TRY(hipStreamCreateWithFlags(&res_stream_, hipStreamNonBlocking));
         for (auto &ev : scan_ev_) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&res_ev_, hipEventDisableTiming));
@@ -795,7 +788,7 @@ int64_t Engine::fast_submit(size_t n, const uint8_t *const *d_streams, const uin
     FastBatch &rec = fb_[seq % 3];
     rec = FastBatch{};  // (live only once every launch is enqueued, below)
     rec.resolved = true;
-    rec.ovl = ovl;
+    rec.two_stream = two_stream;
     rec.slot = slot;
     rec.h = hb;
     rec.n = n;
@@ -807,7 +800,7 @@ int64_t Engine::fast_submit(size_t n, const uint8_t *const *d_streams, const uin
     tev_timed_[seq % kTimeRing] = timed;
     rec.timed = timed;
     if (timed) HIP_TRY(hipEventRecord(ev[0], s));
-    if (!ovl) {
+    if (!two_stream) {
         if (spans)
             HIP_TRY(p3::launch_scan(st, fp_, d_gear_, f.cand, cp, zero_copy ? h_tails : f.d_tails, f.n_tails,
                                     num_cus_, s));
@@ -816,26 +809,19 @@ int64_t Engine::fast_submit(size_t n, const uint8_t *const *d_streams, const uin
         if (timed) HIP_TRY(hipEventRecord(ev[2], s));
     } else {
         // The resolve goes to the second stream behind this scan's event, so
-        // it runs beside the NEXT batch's scan (the overlap set fits one
-        // resolve block next to each CU's scan block).  Resolves stay in order
+        // it runs beside the NEXT batch's scan.  Resolves stay in order
         // on that stream (the look-back descriptors and the spilled chunk
         // starts are shared).  No wait guards the device slot: its previous
         // user, batch seq - kSlots, is complete -- batch seq - kHostSlots was
         // collected above (or by a drain), and resolves retire in order.
         static_assert(kSlots > kHostSlots, "device slots must outlast the host blocks");
-        if (spans && ovl_std_)
+        if (spans)
             HIP_TRY(p3::launch_scan(st, fp_, d_gear_, f.cand, cp, zero_copy ? h_tails : f.d_tails, f.n_tails,
                                     num_cus_, s));
-        else if (spans)
-            HIP_TRY(p3::ovl::launch_scan(st, fp_, d_gear_, f.cand, cp, zero_copy ? h_tails : f.d_tails, f.n_tails,
-                                         num_cus_, s));
         if (timed) HIP_TRY(hipEventRecord(ev[1], s));
         HIP_TRY(hipEventRecord(scan_ev_[slot], s));
         HIP_TRY(hipStreamWaitEvent(res_stream_, scan_ev_[slot], 0));
-        if (spans && ovl_std_)
-            HIP_TRY(p3::launch_resolve(st, fp_, d_gear_, f.cand, ch3_, cp, rs, d_out, out_cap, res_stream_));
-        else if (spans)
-            HIP_TRY(p3::ovl::launch_resolve(st, fp_, d_gear_, f.cand, ch3_, cp, rs, d_out, out_cap, res_stream_));
+        if (spans) HIP_TRY(p3::launch_resolve(st, fp_, d_gear_, f.cand, ch3_, cp, rs, d_out, out_cap, res_stream_));
         if (timed) HIP_TRY(hipEventRecord(ev[2], res_stream_));
         // (an untimed batch's own end marker on the resolve stream, where an
         // event costs the scans nothing: a slow collection waits for this
@@ -847,7 +833,7 @@ int64_t Engine::fast_submit(size_t n, const uint8_t *const *d_streams, const uin
     fast_batches_ = fb_seq_;
     fb_any_ = true;
     fb_stream_ = s;
-    fb_ovl_ = ovl;
+    fb_two_stream_ = two_stream;
     cand_ = f.cand;
     last_spans_ = spans;
     return 0;
@@ -869,7 +855,7 @@ int64_t Engine::fast_drain() {
         if (r && !rc) rc = r;
         if (q == last && !rc) total = (int64_t)b.first[b.n];
     }
-    if (fb_ovl_) {
+    if (fb_two_stream_) {
         // later work on the caller's stream is ordered after the resolves
         if (!rc && hipEventRecord(res_ev_, res_stream_) == hipSuccess)
             (void)hipStreamWaitEvent(fb_stream_, res_ev_, 0);
@@ -895,15 +881,15 @@ int Engine::fast_collect(int k) {
         const volatile uint64_t *done = h_misc + p3::kStatDone;
         // (two streams: a batch's resolve runs after the NEXT batch's scan, so
         // its done word comes about a step later)
-        const uint64_t us = b.ovl ? std::min<uint64_t>(4000, std::max<uint64_t>(200, b.bytes / 1000000))
-                                  : std::min<uint64_t>(2000, std::max<uint64_t>(100, b.bytes / 2000000));
+        const uint64_t us = b.two_stream ? std::min<uint64_t>(4000, std::max<uint64_t>(200, b.bytes / 1000000))
+                                         : std::min<uint64_t>(2000, std::max<uint64_t>(100, b.bytes / 2000000));
         const auto budget = std::chrono::microseconds(us);
         const auto t_spin = std::chrono::steady_clock::now();
         while (*done == ~0ull && std::chrono::steady_clock::now() - t_spin < budget) __builtin_ia32_pause();
     }
     if (h_misc[p3::kStatDone] == ~0ull) {  // (slow batch or a failure: wait for the stream itself)
         if (b.timed) HIP_TRY(hipEventSynchronize(tev_[b.seq % kTimeRing][2]));
-        else if (b.ovl) HIP_TRY(hipEventSynchronize(res_done_[b.seq % 3]));
+        else if (b.two_stream) HIP_TRY(hipEventSynchronize(res_done_[b.seq % 3]));
         else HIP_TRY(hipStreamSynchronize(fb_stream_));
     }
     b.live = false;
@@ -915,15 +901,13 @@ int Engine::fast_collect(int k) {
     if (fp_.diag & 64) {  // resolve block spans (100 MHz stamps -> us)
         const uint64_t *d = h_misc + p3::kStatDiag0;
         const uint64_t s0 = ~d[0], s1 = d[1], e1 = d[2], e0 = ~d[3];
-        const double blocks =
-            (double)(b.ovl && !ovl_std_ ? p3::ovl::resolve_blocks(b.spans) : p3::resolve_blocks(b.spans));
+        const double blocks = (double)p3::resolve_blocks(b.spans);
         std::fprintf(stderr, "resolve blocks, us: scan's last block end -> first start %.2f  starts spread %.2f  "
                              "first start -> first end %.2f  -> last end %.2f  longest block %.2f  mean block %.2f\n",
                      ((double)s0 - (double)d[6]) / 100.0, (s1 - s0) / 100.0, (e0 - s0) / 100.0, (e1 - s0) / 100.0,
                      d[4] / 100.0, d[5] / 100.0 / (blocks ? blocks : 1.0));
     } else if (fp_.diag & 128) {
-        const double waves = b.ovl && !ovl_std_ ? (double)p3::ovl::resolve_blocks(b.spans) * 4
-                                                : (double)p3::resolve_blocks(b.spans) * 8;
+        const double waves = (double)p3::resolve_blocks(b.spans) * 8;
         std::fprintf(stderr, (fp_.diag & 8192) ? "resolve link passes, us per wave (records: issue trunc link; "
                                                  "virtual: issue trunc link; -; -):"
                                                : "resolve phases, us per wave (meta recs settle+wait virtual-links "
@@ -1411,10 +1395,8 @@ int Engine::init_walk(const uint32_t *seq) {
            : (wp.seq_len <= 63 ? 1u : 0u);
     if (const char *b = std::getenv("CHUNKFS_AMD_WALK_BYTES"))
         if (std::atoi(b) != 0) wp.nbm = 0;
-    // Wave-cooperative walks (walk.hip wwalk_kernel, one wave per segment)
-    // for every rule in bitmap mode.  CHUNKFS_AMD_WAVE=0 disables.
-    wp.wave = wp.nbm ? 1u : 0u;
-    if (const char *v = std::getenv("CHUNKFS_AMD_WAVE")) wp.wave = wp.wave && std::atoi(v) != 0;
+    // Bitmap mode walks with a wave per segment (walk.hip wwalk_kernel), byte
+    // mode with a lane per segment (walk_kernel).
     // Lane walks: 32 KiB segments whatever the average (profiles/r02ak).
     // Wave walks: 128 KiB (Rabin, Leap) / 256 KiB segments, 8 avg warm-up
     // (profiles/r03_walk/r03w_walk_seg_sweep.txt: a wave walks thousands of
@@ -1425,14 +1407,14 @@ int Engine::init_walk(const uint32_t *seq) {
     // SeqCDC 16, LeapCDC 24 (its chains merge slowest; the fix-up rounds a
     // shorter warm-up leaves cost more than the walk it saves,
     // profiles/r03_walk/r03ab_walk_warm_ahead_sweep.txt).
-    uint64_t warm_mult = !wp.wave ? (algo_ == CDC_ALGO_SEQ ? 16 : 8)
+    uint64_t warm_mult = !wp.nbm ? (algo_ == CDC_ALGO_SEQ ? 16 : 8)
                        : algo_ == CDC_ALGO_RABIN ? 8 : algo_ == CDC_ALGO_LEAP ? 24 : 16;
     // Segments: lane walks 32 KiB whatever the average (profiles/r02ak).  Wave
     // walks: at least 128 KiB (Rabin) / 256 KiB and at least the warm-up, so
     // that the warm-up stays a fraction of each wave's walk (a wave walks
     // thousands of positions per step; r03w_walk_seg_sweep.txt), up to 4 MiB.
-    seg_log2_ = !wp.wave ? 15 : algo_ == CDC_ALGO_RABIN ? 17 : 18;
-    if (wp.wave) {
+    seg_log2_ = !wp.nbm ? 15 : algo_ == CDC_ALGO_RABIN ? 17 : 18;
+    if (wp.nbm) {
         const uint32_t wl = ceil_log2(warm_mult * avg_);
         if (wl > seg_log2_) seg_log2_ = wl < 22 ? wl : 22;
     }
@@ -1461,26 +1443,6 @@ int Engine::init_walk(const uint32_t *seq) {
     if (const char *f = std::getenv("CHUNKFS_AMD_BITS_FINE")) wp.bits_fine = std::atoi(f) != 0 ? 1u : 0u;
     if (const char *f = std::getenv("CHUNKFS_AMD_WALK_FUSED")) walk_fused_ = std::atoi(f) != 0;
     wp.cap = (uint32_t)((1ull << seg_log2_) / min_ + 2);
-    // Link mode (Rabin, UltraCDC, LeapCDC): candidate lists of ~4x
-    // the expected count per segment -- Rabin hits 2^-round(log2 avg) per
-    // position, UltraCDC mask_l hits ~2^-11 (Hamming distance 16..19 of 64),
-    // LeapCDC eligible-window runs ~2^-round(log2(avg - min));
-    // CHUNKFS_AMD_LINKS=0 disables.  (SeqCDC's candidates -- completed runs --
-    // are too dense: it keeps direct walks.)
-    // Default on where it measured faster (1 GiB, 4/8/16 KiB: UltraCDC 223 ->
-    // 252 GiB/s; Rabin 573 -> 520 and LeapCDC 153 -> 143 lose).
-    const bool linkable = algo_ == CDC_ALGO_RABIN || algo_ == CDC_ALGO_ULTRA || algo_ == CDC_ALGO_LEAP;
-    wp.links = algo_ == CDC_ALGO_ULTRA ? 1u : 0u;
-    if (const char *l = std::getenv("CHUNKFS_AMD_LINKS")) wp.links = std::atoi(l) != 0 && linkable;
-    {
-        const uint32_t dens = algo_ == CDC_ALGO_RABIN ? cdc_log2_round(avg_) : algo_ == CDC_ALGO_ULTRA ? 10u : lb;
-        const uint64_t expect = ((1ull << seg_log2_) >> dens) + 1;
-        uint64_t cc = 16;
-        while (cc < 4 * expect && cc < 1024) cc <<= 1;
-        wp.ccap = (uint32_t)cc;
-    }
-    if (!wp.nbm) wp.links = 0;  // links are computed over the bitmaps
-    if (wp.wave) wp.links = 0;  // the wave walks replace link mode
     wp.seg_words = (uint32_t)((1ull << seg_log2_) / 64);
     wp.piece_log2 = seg_log2_ < 15 ? seg_log2_ : 15;  // data-parallel passes: 32 KiB pieces
     wp.bm = nullptr;
@@ -1554,18 +1516,13 @@ int Engine::ensure_walk_workspace(uint64_t segs, size_t n) {
     const size_t oN = take(S * 4), oL = take(S * (size_t)wp_.cap * 8), oB = take((nb + 1) * 8);
     const size_t oF = take((N + 1) * 8), oG = take((4 + 4 * walk::kMaxFixRounds) * 8), oGo = take(16);
     const size_t oBM = take(S * (size_t)wp_.seg_words * wp_.nbm * 8);  // predicate bitmaps
-    const bool jt = algo_ == CDC_ALGO_LEAP && wp_.wave;
+    const bool jt = algo_ == CDC_ALGO_LEAP && wp_.nbm;
     const size_t oJT = take(jt ? S * (size_t)wp_.seg_words * 24 : 0);  // LeapCDC word tables
     const size_t oJ8 = take(jt ? S * (size_t)wp_.seg_words * 6 : 0);   // and 512-position block tables
     bool rsum = walk::bits_write_summary(wp_);  // quiet runs (CHUNKFS_AMD_QUIET=0: off, A/B)
     if (const char *q = std::getenv("CHUNKFS_AMD_QUIET")) rsum = rsum && std::atoi(q) != 0;
     const size_t oRS = take(rsum ? S * (size_t)wp_.seg_words / 8 * (algo_ == CDC_ALGO_RABIN ? 2 : 1) : 0);  // quiet-run summary
     const size_t oQS = take(rsum ? S : 0);  // and per segment
-    const size_t cc = wp_.links ? wp_.ccap : 0;                          // link mode
-    const size_t oCN = take(S * 4), oCP = take(S * cc * 4), oLN = take(S * cc * 8), oLI = take(S * cc * 4);
-    const size_t vc = wp_.links ? S * 8 : 0;
-    const size_t oVC = take((2 * walk::kVirtRounds + 2) * 8), oVP = take(vc * 8), oVS = take(vc * 4),
-                 oVN = take(vc * 8), oVI = take(vc * 4);
     const size_t o_ptrs = take(N * 8), o_lens = take(N * 8), o_sb = take((N + 1) * 8);
     (void)hipFree(wws_);
     wws_ = nullptr;
@@ -1593,16 +1550,6 @@ int Engine::ensure_walk_workspace(uint64_t segs, size_t n) {
     wp_.jt8 = jt ? reinterpret_cast<uint16_t *>(b + oJ8) : nullptr;
     wp_.rsum = rsum ? reinterpret_cast<uint64_t *>(b + oRS) : nullptr;
     wp_.qseg = rsum ? reinterpret_cast<uint8_t *>(b + oQS) : nullptr;
-    wp_.ccnt = reinterpret_cast<uint32_t *>(b + oCN);
-    wp_.cpos = reinterpret_cast<uint32_t *>(b + oCP);
-    wp_.lnext = reinterpret_cast<uint64_t *>(b + oLN);
-    wp_.lidx = reinterpret_cast<uint32_t *>(b + oLI);
-    wp_.vcap = (uint32_t)vc;
-    wp_.vcnt = reinterpret_cast<unsigned long long *>(b + oVC);
-    wp_.vpos = reinterpret_cast<uint64_t *>(b + oVP);
-    wp_.vseg = reinterpret_cast<uint32_t *>(b + oVS);
-    wp_.vnext = reinterpret_cast<uint64_t *>(b + oVN);
-    wp_.vidx = reinterpret_cast<uint32_t *>(b + oVI);
     d_ptrs_ = reinterpret_cast<const uint8_t **>(b + o_ptrs);
     d_lens_ = reinterpret_cast<uint64_t *>(b + o_lens);
     d_span_base_ = reinterpret_cast<uint64_t *>(b + o_sb);
@@ -1620,7 +1567,7 @@ int Engine::run_walk(const StreamTable &st, cdc_chunk_t *d_out, size_t n, uint64
     // the call: then no init launch here)
     if (!walk_flags_clean_) HIP_TRY(walk::launch_flags_init(wst_.flags, R, s));
     walk_flags_clean_ = false;
-    static const bool diag = std::getenv("CHUNKFS_AMD_WALKDIAG") != nullptr;  // phase times + candidates
+    static const bool diag = std::getenv("CHUNKFS_AMD_WALKDIAG") != nullptr;  // phase times
     auto lap = [&](const char *what) -> int {
         if (!diag) return CDC_OK;
         static auto t_last = std::chrono::steady_clock::now();
@@ -1634,21 +1581,6 @@ int Engine::run_walk(const StreamTable &st, cdc_chunk_t *d_out, size_t n, uint64
     (void)lap("start");
     HIP_TRY(walk::launch_bits(st, wp_, s));
     (void)lap("bits");
-    HIP_TRY(walk::launch_links(st, wp_, s));
-    (void)lap("links");
-    if (diag && wp_.links) {
-        std::vector<uint32_t> cn(st.total_spans);
-        HIP_TRY(hipMemcpy(cn.data(), wp_.ccnt, cn.size() * 4, hipMemcpyDeviceToHost));
-        uint64_t tot = 0, ovf = 0, mx = 0;
-        for (uint32_t c : cn) {
-            tot += c;
-            ovf += c > wp_.ccap;
-            mx = c > mx ? c : mx;
-        }
-        std::fprintf(stderr, "  walkdiag candidates %llu (%.2f per segment, max %llu, cap %u, overflowed %llu of %zu)\n",
-                     (unsigned long long)tot, (double)tot / cn.size(), (unsigned long long)mx, wp_.ccap,
-                     (unsigned long long)ovf, cn.size());
-    }
     HIP_TRY(walk::launch_walk(st, wp_, wst_, s));
     (void)lap("walk");
     HIP_TRY(hipEventRecord(ev_[1], s));

@@ -162,9 +162,9 @@ class Engine {
     // batch's results, drain every batch in flight.
     int64_t batch_device(size_t n, const uint8_t *const *d_streams, const uint64_t *lens, cdc_chunk_t *d_out,
                          size_t out_cap, uint64_t *first, hipStream_t stream, bool async);
-    // ovl: the overlap kernel set (fastcdc_ovl.hip), the resolve on res_stream_.
+    // two_stream: the resolve on res_stream_.
     int64_t fast_submit(size_t n, const uint8_t *const *d_streams, const uint64_t *lens, cdc_chunk_t *d_out,
-                        size_t out_cap, uint64_t *first, uint64_t bytes, hipStream_t s, bool timed, bool ovl);
+                        size_t out_cap, uint64_t *first, uint64_t bytes, hipStream_t s, bool timed, bool two_stream);
     int fast_collect(int rec);
     int64_t fast_drain();
     int64_t drain_implicit();  // fast_drain for another call: its result is kept for batch_sync
@@ -268,7 +268,7 @@ class Engine {
     // scan + resolve enqueued at submit, collected (done word, first[]) by the
     // submit three later or by fast_drain.
     struct FastBatch {
-        bool live = false, resolved = false, timed = true, ovl = false;
+        bool live = false, resolved = false, timed = true, two_stream = false;
         int slot = 0;                // device slot
         uint64_t *h = nullptr;       // host staging block (slot seq % kHostSlots)
         size_t n = 0;
@@ -281,21 +281,18 @@ class Engine {
     uint64_t fb_seq_ = 0;           // batches submitted
     hipStream_t fb_stream_ = nullptr;  // the stream of the batches in flight
     bool fb_any_ = false;           // a batch is in flight
-    bool fb_ovl_ = false;           // ... with their resolves on res_stream_
-    // Async batches on two streams (default, CHUNKFS_AMD_OVERLAP=2): batch k's
+    bool fb_two_stream_ = false;    // ... with their resolves on res_stream_
+    // Async batches on two streams (default, CHUNKFS_AMD_OVERLAP=1): batch k's
     // resolve on res_stream_ behind scan_ev_[slot k], batch k+1's scan on the
     // caller's stream right behind scan k.  A resolve block (148 KiB of LDS)
     // and a scan block (136 KiB) never share a CU, so nothing co-resides: the
     // next scan's blocks take each CU as its resolve block retires -- the
     // kernel-to-kernel gaps and the resolve's ragged end leave the step
     // (0.2557 vs 0.2744 ms sustained, profiles/r06/r06p_*).  res_ev_ orders the
-    // caller's stream after the resolves at a drain.  CHUNKFS_AMD_OVERLAP=1:
-    // the same with the overlap kernel set (fastcdc_ovl.hip, where its resolve
-    // windows fit), which co-resides and measured slower (0.33 vs 0.278 ms:
-    // the issue-bound scan slowed from 0.217 to 0.296 ms, profiles/r06/r06a_*);
-    // 0: one stream.
-    bool ovl_on_ = true;
-    bool ovl_std_ = true;   // the regular kernel set on the two streams
+    // caller's stream after the resolves at a drain.  CHUNKFS_AMD_OVERLAP=0:
+    // one stream.  (A second kernel set sized to co-reside measured slower,
+    // 0.33 vs 0.278 ms per step, profiles/r06/r06a_*, and was removed.)
+    bool two_stream_on_ = true;
     hipStream_t res_stream_ = nullptr;
     hipEvent_t scan_ev_[kSlots] = {};
     hipEvent_t res_ev_ = nullptr;

@@ -10,15 +10,20 @@
 // Kernels, one launch each, all on the handle's stream:
 //   *bits_kernel   per-position predicate bitmaps (data-parallel pass)
 //   jtab_kernel    LeapCDC: per-word orbit tables
-//   wwalk_kernel   wave per segment: warm-up walk, then the segment's starts
-//                  (bitmap mode; walk_kernel = lane per segment, byte mode and
-//                  the CHUNKFS_AMD_WAVE=0 A/B path)
+//   qseg_kernel    per segment: wholly quiet in which kinds (quiet runs)
+//   wwalk_kernel   wave per segment over the bitmaps: warm-up walk, then the
+//                  segment's starts and round 0's snapshots
 //   wfix_kernel    re-walk where entry != predecessor exit, running ahead
-//                  into unscheduled successors (fix_kernel: lane version)
+//                  into unscheduled successors
 //   wserial_kernel wave per stream: in-order re-walk from the lowest changed
-//                  segment (serial_kernel: lane per stream)
-//   sum/scan/emit  block sums of N -> block prefix -> per-segment prefix and
-//                  the Chunk{offset,length} output; first[] per stream
+//                  segment
+//   walk_kernel / fix_kernel / serial_kernel
+//                  the same three with a lane per segment (stream) reading
+//                  the bytes: byte mode only (wp.nbm == 0)
+//   snap / flags_init            a round's snapshots; the flag blocks
+//   sum / prefix / emit / first  block sums of N -> block prefix -> per-segment
+//                  prefix and the Chunk{offset,length} output; first[] per stream
+//   finish_kernel  sum / prefix / first in one block behind the first group
 #include "walk.hpp"
 
 #include "../../include/chunkfs_amd_cdc_params.h"
@@ -134,78 +139,12 @@ struct Reader {
         ensure(p, p);
         return raw(p);
     }
-    // Bitmap mode: word widx (8-byte aligned in the stream's bitmap bytes).
-    __device__ __forceinline__ uint64_t word(uint64_t widx) {
-        ensure(widx * 8, widx * 8 + 7);
-        return *reinterpret_cast<const uint64_t *>(slot + (widx * 8 - w0));
-    }
-    // n (1..64) bits of bitmap b from position p, bit j = position p + j.
-    __device__ __forceinline__ uint64_t bits(uint32_t nbm, uint32_t b, uint64_t p, uint32_t n) {
-        const uint64_t k = p >> 6;
-        const uint32_t sh = (uint32_t)(p & 63);
-        uint64_t v;
-        if (sh + n <= 64) {
-            v = word(k * nbm + b) >> sh;
-        } else {
-            ensure(k * nbm * 8, ((k + 1) * nbm + b) * 8 + 7);
-            const uint64_t lo = *reinterpret_cast<const uint64_t *>(slot + ((k * nbm + b) * 8 - w0));
-            const uint64_t hi = *reinterpret_cast<const uint64_t *>(slot + (((k + 1) * nbm + b) * 8 - w0));
-            v = (lo >> sh) | (hi << (64 - sh));
-        }
-        return n == 64 ? v : v & ((1ull << n) - 1);
-    }
     __device__ __forceinline__ uint64_t at8(uint64_t p) {
         ensure(p, p + 7);
         uint64_t v = 0;
 #pragma unroll
         for (int j = 0; j < 8; ++j) v |= (uint64_t)raw(p + j) << (8 * j);
         return v;
-    }
-};
-
-// Bitmap reader straight from global memory (L1 / L2), for the link kernels'
-// one-chunk walks: an aligned window of 8 words (4 x 16-byte loads issued
-// together) stays in registers.  Same interface as Reader's bitmap
-// accessors; words past the end read 0.
-struct GReader {
-    const uint64_t *w;
-    uint64_t nw;              // words of the stream's bitmaps
-    uint64_t ck = ~0ull;      // first word of the cached window (multiple of 8)
-    uint64_t c[8];
-
-    __device__ void init(const uint64_t *base, uint64_t nwords) {
-        w = base;
-        nw = nwords;
-        ck = ~0ull;
-    }
-    __device__ __forceinline__ uint64_t word(uint64_t i) {
-        const uint64_t k = i & ~7ull;
-        if (k != ck) {
-            ck = k;
-            if (k + 8 <= nw) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const uint4 v = *reinterpret_cast<const uint4 *>(w + k + 2 * q);
-                    c[2 * q] = ((uint64_t)v.y << 32) | v.x;
-                    c[2 * q + 1] = ((uint64_t)v.w << 32) | v.z;
-                }
-            } else {
-#pragma unroll
-                for (int q = 0; q < 8; ++q) c[q] = k + q < nw ? w[k + q] : 0;
-            }
-        }
-        uint64_t v = c[0];
-#pragma unroll
-        for (int q = 1; q < 8; ++q)
-            if ((i & 7) == (uint64_t)q) v = c[q];
-        return v;
-    }
-    __device__ __forceinline__ uint64_t bits(uint32_t nbm, uint32_t b, uint64_t p, uint32_t n) {
-        const uint64_t k = p >> 6;
-        const uint32_t sh = (uint32_t)(p & 63);
-        uint64_t v = word(k * nbm + b) >> sh;
-        if (sh + n > 64) v |= word((k + 1) * nbm + b) << (64 - sh);
-        return n == 64 ? v : v & ((1ull << n) - 1);
     }
 };
 
@@ -318,234 +257,32 @@ __device__ uint64_t cut_seq(Reader &r, uint64_t s, uint64_t n, const WalkParams 
     return end;
 }
 
-// ---- the same rules over the predicate bitmaps (bits_kernel) ---------------
-// Rabin (min >= 48): every tested digest is a full 48-byte window, so a hit is
-// the bitmap bit; the cut is the first hit in [s+min-1, s+end-1], plus one.
-template <class R>
-__device__ uint64_t cut_rabin_bits(R &r, uint64_t s, uint64_t n, const WalkParams &wp) {
-    if (n <= wp.min) return n;
-    const uint64_t end = n < wp.max ? n : wp.max;
-    const uint64_t lo = s + wp.min - 1, hi = s + end - 1;
-    for (uint64_t k = lo >> 6; k <= (hi >> 6); ++k) {
-        uint64_t w = r.word(k);
-        if (k == (lo >> 6)) w &= ~0ull << (lo & 63);
-        if (k == (hi >> 6) && (hi & 63) != 63) w &= (2ull << (hi & 63)) - 1;
-        if (w) return k * 64 + (uint64_t)__builtin_ctzll(w) - s + 1;
-    }
-    return end;
-}
-
-// UltraCDC over bitmaps 0 (dist & MASK_S == 0), 1 (dist & MASK_L == 0) and
-// 2 (the 8 bytes at q repeat the 8 before).  64 positions at a time while no
-// block start repeats and no position hits, else block by block as cut_ultra.
-template <class R>
-__device__ uint64_t cut_ultra_bits(R &r, uint64_t s, uint64_t n, const WalkParams &wp) {
-    if (n <= wp.min) return n;
-    uint64_t normal = wp.avg, end = n;
-    if (n >= wp.max) end = wp.max;
-    else if (n <= normal) normal = n;
-    uint32_t lec = 0;
-    uint64_t i = wp.min;
-    while (i + 8 <= end) {
-        if (i + 64 <= end && (i >= normal || i + 56 < normal)) {
-            const uint64_t e = r.bits(3, 2, s + i, 64) & 0x0101010101010101ull;
-            const uint64_t m = r.bits(3, i >= normal ? 1 : 0, s + i, 64);
-            if ((e | m) == 0) {
-                lec = 0;
-                i += 64;
-                continue;
-            }
-            // The blocks before the first event neither repeat nor hit: skip
-            // to the event's block (lec is 0 after them, as block by block).
-            const uint32_t b = (uint32_t)__builtin_ctzll(e | m) >> 3;
-            if (b) {
-                lec = 0;
-                i += 8 * b;
-            }
-        }
-        if (r.bits(3, 2, s + i, 1)) {
-            if (++lec >= CDC_ULTRA_LEST) return i + 8;
-            i += 8;
-            continue;
-        }
-        lec = 0;
-        const uint64_t m = r.bits(3, i >= normal ? 1 : 0, s + i, 8);
-        if (m) return i + (uint64_t)__builtin_ctzll(m);
-        i += 8;
-    }
-    return end;
-}
-
-// LeapCDC over bitmaps 0 (primary) and 1 (secondary): the 22 primary windows
-// of candidate c are bits c-22 .. c-1, the failing one nearest to c decides
-// the leap; then the two secondary windows c-23, c-24.
-template <class R>
-__device__ uint64_t cut_leap_bits(R &r, uint64_t s, uint64_t n, const WalkParams &wp) {
-    if (n <= wp.min) return n;
-    const uint64_t end = n < wp.max ? n : wp.max;
-    uint64_t c = wp.min;
-    // The two primary words around the candidate stay in registers while the
-    // leaps (~21 positions each) move through them.
-    uint64_t kc = ~0ull, wa = 0, wb = 0;
-    while (c <= end) {
-        const uint64_t p = s + c - CDC_LEAP_PRIMARY;
-        const uint64_t k = p >> 6;
-        if (k != kc) {
-            wa = r.word(k * 2);
-            wb = r.word(k * 2 + 2);
-            kc = k;
-        }
-        const uint32_t sh = (uint32_t)(p & 63);
-        const uint64_t v = sh ? (wa >> sh) | (wb << (64 - sh)) : wa;
-        const uint64_t z = ~v & ((1ull << CDC_LEAP_PRIMARY) - 1);
-        if (z) {  // window k = 21 - j failed, j = the highest zero bit
-            const uint32_t j = 63u - (uint32_t)__builtin_clzll(z);
-            c += CDC_LEAP_WINDOWS - (CDC_LEAP_PRIMARY - 1 - j);
-            continue;
-        }
-        if (!r.bits(2, 1, s + c - 23, 1)) { c += CDC_LEAP_WINDOWS - 22; continue; }
-        if (!r.bits(2, 1, s + c - 24, 1)) { c += CDC_LEAP_WINDOWS - 23; continue; }
-        return c;
-    }
-    return end;
-}
-
-// Index of the n-th (1-based) set bit of z, popc(z) >= n >= 1: a halving
-// search on popcounts (6 steps) instead of clearing n-1 bits one by one.
-__device__ __forceinline__ uint32_t select_bit(uint64_t z, uint32_t n) {
-    uint32_t pos = 0, c = (uint32_t)__popc((uint32_t)z);
-    if (c < n) { n -= c; z >>= 32; pos += 32; }
-    c = (uint32_t)__popc((uint32_t)z & 0xFFFFu);
-    if (c < n) { n -= c; z >>= 16; pos += 16; }
-    c = (uint32_t)__popc((uint32_t)z & 0xFFu);
-    if (c < n) { n -= c; z >>= 8; pos += 8; }
-    c = (uint32_t)__popc((uint32_t)z & 0xFu);
-    if (c < n) { n -= c; z >>= 4; pos += 4; }
-    c = (uint32_t)__popc((uint32_t)z & 0x3u);
-    if (c < n) { n -= c; z >>= 2; pos += 2; }
-    if (((uint32_t)z & 1u) < n) pos += 1;
-    return pos;
-}
-
-// SeqCDC over bitmap 0 (pair p in the mode's direction), up to 64 positions
-// per step: a = positions where a run of seq_len in-sequence pairs completes
-// (the run carried in from the previous step included), tB = the pair at which
-// the opposing count reaches jump_trigger; the earlier event decides.
-template <class R>
-__device__ uint64_t cut_seq_bits(R &r, uint64_t s, uint64_t n, const WalkParams &wp) {
-    if (n <= wp.min) return n;
-    const uint64_t end = n < wp.max ? n : wp.max;
-    uint32_t cnt = 0, opp = 0;
-    uint64_t i = wp.min;
-    while (i < end) {
-        const uint32_t k = (uint32_t)min(end - i, (uint64_t)64);
-        const uint64_t km = k == 64 ? ~0ull : (1ull << k) - 1;
-        const uint64_t y = r.bits(1, 0, s + i, k);
-        const uint64_t prev = cnt >= 64 ? ~0ull : cnt ? ~0ull << (64 - cnt) : 0ull;
-        uint64_t a = y;
-        for (uint32_t q = 1; q < wp.seq_len; ++q) a &= (y << q) | (prev >> (64 - q));
-        a &= km;
-        uint64_t z = ~y & km;
-        const uint32_t need = wp.seq_trig - opp;
-        const uint32_t tB = (uint32_t)__popcll(z) >= need ? select_bit(z, need) : 64u;
-        const uint32_t tA = a ? (uint32_t)__builtin_ctzll(a) : 64u;
-        if (tA < tB) return i + tA + 1;
-        if (tB < 64) {
-            opp = 0;
-            cnt = 0;
-            i += tB + wp.seq_jump;
-            continue;
-        }
-        opp += (uint32_t)__popcll(~y & km);
-        const uint64_t zz = ~y & km;
-        cnt = zz ? k - 1 - (63u - (uint32_t)__builtin_clzll(zz)) : min(cnt + k, 1u << 30);
-        i += k;
-    }
-    return end;
-}
-
-template <int kAlgo, bool kBits>
+template <int kAlgo>
 __device__ __forceinline__ uint64_t cut(Reader &r, uint64_t s, uint64_t len, const WalkParams &wp, const Tabs &T) {
-    if constexpr (kBits) {
-        if constexpr (kAlgo == 2) return cut_rabin_bits(r, s, len - s, wp);
-        else if constexpr (kAlgo == 4) return cut_ultra_bits(r, s, len - s, wp);
-        else if constexpr (kAlgo == 6) return cut_seq_bits(r, s, len - s, wp);
-        else return cut_leap_bits(r, s, len - s, wp);
-    } else {
-        if constexpr (kAlgo == 2) return cut_rabin(r, s, len - s, wp, T);
-        else if constexpr (kAlgo == 4) return cut_ultra(r, s, len - s, wp);
-        else if constexpr (kAlgo == 5) return cut_leap(r, s, len - s, wp, T);
-        else return cut_seq(r, s, len - s, wp);
-    }
-}
-
-// Where a walk stands: the stream's first segment (gbase), the segment
-// size, and the candidate slot of the current start (link mode; kNoCand when
-// unknown or not a candidate).
-struct Hop {
-    uint64_t gbase;
-    uint32_t sl2;
-    uint32_t ci;
-};
-
-// Candidate slot of stream offset c (link mode), or kNoCand: a binary search
-// in its segment's ascending list; overflowed segments have no links.
-__device__ __forceinline__ uint32_t find_cand(const WalkParams &wp, const Hop &hp, uint64_t c) {
-    const uint64_t h = hp.gbase + (c >> hp.sl2);
-    const uint32_t n = wp.ccnt[h];
-    if (n > wp.ccap) return kNoCand;
-    const uint32_t *P = wp.cpos + h * wp.ccap;
-    const uint32_t x = (uint32_t)(c & ((1ull << hp.sl2) - 1));
-    uint32_t a = 0, b = n;
-    while (a < b) {
-        const uint32_t m = (a + b) >> 1;
-        if (P[m] < x) a = m + 1; else b = m;
-    }
-    return a < n && P[a] == x ? (uint32_t)(h * wp.ccap + a) : kNoCand;
-}
-
-// The next chunk start after one starting at c: the precomputed link when c
-// is a candidate (link mode), else the rule walked from c.
-template <int kAlgo, bool kBits>
-__device__ __forceinline__ uint64_t advance(Reader &r, uint64_t c, uint64_t len, Hop &hp, const WalkParams &wp,
-                                            const Tabs &T) {
-    if (wp.links && c < len) {
-        if (hp.ci == kNoCand) hp.ci = find_cand(wp, hp, c);
-        if (hp.ci != kNoCand) {
-            uint64_t nx;
-            if (hp.ci & kVirt) {
-                const uint32_t v = hp.ci & ~kVirt;
-                nx = wp.vnext[v];
-                hp.ci = wp.vidx[v];
-            } else {
-                nx = wp.lnext[hp.ci];
-                hp.ci = wp.lidx[hp.ci];
-            }
-            return nx;
-        }
-    }
-    hp.ci = kNoCand;
-    return c + cut<kAlgo, kBits>(r, c, len, wp, T);
+    if constexpr (kAlgo == 2) return cut_rabin(r, s, len - s, wp, T);
+    else if constexpr (kAlgo == 4) return cut_ultra(r, s, len - s, wp);
+    else if constexpr (kAlgo == 5) return cut_leap(r, s, len - s, wp, T);
+    else return cut_seq(r, s, len - s, wp);
 }
 
 // Walk from chunk start c (< seg_end) to the first start >= seg_end,
-// recording the starts in the segment's list.
-template <int kAlgo, bool kBits>
-__device__ void walk_from(uint64_t c, uint64_t g, uint64_t seg_end, uint64_t len, Reader &r,
-                          const WalkParams &wp, const Tabs &T, const WalkState &ws, Hop &hp) {
+// recording the starts in the segment's list; returns that exit.  (The round
+// snapshots Es / Xs are not touched: round 0's are walk_kernel's to write.)
+template <int kAlgo>
+__device__ uint64_t walk_from(uint64_t c, uint64_t g, uint64_t seg_end, uint64_t len, Reader &r,
+                              const WalkParams &wp, const Tabs &T, const WalkState &ws) {
     ws.E[g] = c;
-    ws.Es[g] = c;  // (round 0's snapshot: launch_fix skips its snap_kernel)
     uint32_t cnt = 0;
     uint64_t *list = ws.list + g * wp.cap;
     while (c < seg_end) {
         if (cnt < wp.cap) list[cnt] = c;
         ++cnt;
-        c = advance<kAlgo, kBits>(r, c, len, hp, wp, T);
+        c += cut<kAlgo>(r, c, len, wp, T);
     }
     ws.X[g] = c;
-    ws.Xs[g] = c;
     ws.N[g] = cnt;
     if (cnt > wp.cap) atomicAdd(&ws.flags[1], 1ull);
+    return c;
 }
 
 // Re-walk of segment g from x (a fix-up): the new chain usually meets the
@@ -556,10 +293,9 @@ __device__ void walk_from(uint64_t c, uint64_t g, uint64_t seg_end, uint64_t len
 // whether the exit X changed (only then can successors be affected).
 constexpr uint32_t kNew = 8;
 
-template <int kAlgo, bool kBits>
+template <int kAlgo>
 __device__ bool rewalk(uint64_t x, uint64_t g, uint64_t seg_end, uint64_t len, Reader &r, const WalkParams &wp,
-                       const Tabs &T, const WalkState &ws, uint64_t *nb, Hop &hp) {
-    hp.ci = kNoCand;
+                       const Tabs &T, const WalkState &ws, uint64_t *nb) {
     uint64_t *list = ws.list + g * wp.cap;
     const uint32_t n_old = ws.N[g];
     const uint32_t lim = min(n_old, wp.cap);
@@ -582,7 +318,7 @@ __device__ bool rewalk(uint64_t x, uint64_t g, uint64_t seg_end, uint64_t len, R
             return false;
         }
         nb[m++] = c;
-        c = advance<kAlgo, kBits>(r, c, len, hp, wp, T);
+        c += cut<kAlgo>(r, c, len, wp, T);
     }
     if (c >= seg_end) {  // the whole segment in <= kNew starts, no meeting point
         for (uint32_t k = 0; k < m; ++k) list[k] = nb[k];
@@ -591,22 +327,7 @@ __device__ bool rewalk(uint64_t x, uint64_t g, uint64_t seg_end, uint64_t len, R
         ws.X[g] = c;
         return c != x_old;
     }
-    hp.ci = kNoCand;
-    walk_from<kAlgo, kBits>(x, g, seg_end, len, r, wp, T, ws, hp);
-    return ws.X[g] != x_old;
-}
-
-
-// Byte mode reads the stream; bitmap mode reads the stream's bitmap words.
-template <bool kBits>
-__device__ __forceinline__ void init_reader(Reader &r, const StreamTable &st, const WalkParams &wp, uint32_t si,
-                                            uint64_t len, uint8_t *slot) {
-    if constexpr (kBits) {
-        const uint64_t *b = wp.bm + st.span_base[si] * (uint64_t)wp.seg_words * wp.nbm;
-        r.init(reinterpret_cast<const uint8_t *>(b), ((len + 63) >> 6) * 8ull * wp.nbm, slot);
-    } else {
-        r.init(st.ptrs[si], len, slot);
-    }
+    return walk_from<kAlgo>(x, g, seg_end, len, r, wp, T, ws) != x_old;
 }
 
 __device__ __forceinline__ void load_tabs(uint64_t *sh, const uint64_t *g) {
@@ -614,7 +335,8 @@ __device__ __forceinline__ void load_tabs(uint64_t *sh, const uint64_t *g) {
     __syncthreads();
 }
 
-template <int kAlgo, bool kBits>
+// Round 0, byte mode: a lane per segment.
+template <int kAlgo>
 __global__ __launch_bounds__(kWalkBlock) void walk_kernel(const StreamTable st, const WalkParams wp,
                                                           const WalkState ws) {
     __shared__ uint64_t tab[768];
@@ -629,30 +351,17 @@ __global__ __launch_bounds__(kWalkBlock) void walk_kernel(const StreamTable st, 
     const uint64_t len = st.lens[si];
     const uint64_t seg_end = min(off + (1ull << st.span_log2), len);
     Reader r;
-    init_reader<kBits>(r, st, wp, si, len, win + threadIdx.x * kSlot);
-    Hop hp{st.span_base[si], st.span_log2, kNoCand};
+    r.init(st.ptrs[si], len, win + threadIdx.x * kSlot);
     // Warm-up start: `warm` bytes back, on the max-length grid of the stream
-    // (so runs of max-length cuts from the stream start are in phase); in
-    // link mode the first candidate at or after it, so that the warm-up is a
-    // few hops over links instead of a walk.
+    // (so runs of max-length cuts from the stream start are in phase).
     uint64_t c = 0;
     if (off != 0) {
         c = off > wp.warm ? off - wp.warm : 0;
         c = c / wp.max * wp.max;
-        if (wp.links) {
-            const uint64_t h = hp.gbase + (c >> hp.sl2);
-            const uint32_t n = wp.ccnt[h];
-            if (n >= 1 && n <= wp.ccap) {
-                const uint64_t cc = (c & ~((1ull << hp.sl2) - 1)) + wp.cpos[h * wp.ccap];
-                if (cc < off) {
-                    c = cc;
-                    hp.ci = (uint32_t)(h * wp.ccap);
-                }
-            }
-        }
-        while (c < off) c = advance<kAlgo, kBits>(r, c, len, hp, wp, T);
+        while (c < off) c += cut<kAlgo>(r, c, len, wp, T);
     }
-    walk_from<kAlgo, kBits>(c, g, seg_end, len, r, wp, T, ws, hp);
+    ws.Es[g] = c;  // (round 0's snapshots: launch_fix skips its snap_kernel)
+    ws.Xs[g] = walk_from<kAlgo>(c, g, seg_end, len, r, wp, T, ws);
 }
 
 // One Jacobi round.  Segment g is scheduled when its entry differs from its
@@ -662,7 +371,8 @@ __global__ __launch_bounds__(kWalkBlock) void walk_kernel(const StreamTable st, 
 // meet, the stream ends, a scheduled successor, or wp.ahead segments: chains
 // that take several segments to merge (SeqCDC's jumps) settle in one launch
 // instead of one round per segment.  Scheduling reads only the snapshots, so a
-// run-ahead write of E[g+1] never makes lane g+1 re-walk concurrently.
+// run-ahead write of E[g+1] never makes lane g+1 re-walk concurrently; only
+// walk_kernel (round 0) and snap_kernel write them, never a re-walk.
 
 // A fix-up round runs only while the previous one changed exits and those
 // were not mostly quiet-run re-walks (the host applies the same rule and hands
@@ -672,7 +382,7 @@ __device__ __forceinline__ bool round_stops(const unsigned long long *gate) {
     return gate && round_verdict(gate[0], gate[3] >> 32) != kRoundGoOn;
 }
 
-template <int kAlgo, bool kBits>
+template <int kAlgo>
 __global__ __launch_bounds__(kWalkBlock) void fix_kernel(const StreamTable st, const WalkParams wp,
                                                          const WalkState ws) {
     if (round_stops(ws.gate)) return;  // the previous round settled everything (or went quiet)
@@ -692,13 +402,12 @@ __global__ __launch_bounds__(kWalkBlock) void fix_kernel(const StreamTable st, c
     const uint64_t len = st.lens[si];
     const uint64_t span = 1ull << st.span_log2;
     Reader r;
-    init_reader<kBits>(r, st, wp, si, len, win + threadIdx.x * kSlot);
-    Hop hp{st.span_base[si], st.span_log2, kNoCand};
+    r.init(st.ptrs[si], len, win + threadIdx.x * kSlot);
     uint64_t gg = g;
     for (uint32_t k = 0;; ++k) {
         const uint64_t seg_end = min(off + span, len);
         atomicAdd(&ws.flags[3], 1ull);  // segments re-walked (statistics)
-        if (!rewalk<kAlgo, kBits>(x, gg, seg_end, len, r, wp, T, ws, nbuf + threadIdx.x * kNew, hp)) break;
+        if (!rewalk<kAlgo>(x, gg, seg_end, len, r, wp, T, ws, nbuf + threadIdx.x * kNew)) break;
         if (seg_end >= len) break;  // the stream's last segment: no successor
         if (k + 1 >= wp.ahead || ws.Es[gg + 1] != ws.Xs[gg]) {
             atomicAdd(&ws.flags[0], 1ull);  // a successor needs another round
@@ -711,7 +420,7 @@ __global__ __launch_bounds__(kWalkBlock) void fix_kernel(const StreamTable st, c
     }
 }
 
-template <int kAlgo, bool kBits>
+template <int kAlgo>
 __global__ __launch_bounds__(kWalkBlock) void serial_kernel(const StreamTable st, const WalkParams wp,
                                                             const WalkState ws) {
     __shared__ uint64_t tab[768];
@@ -734,21 +443,21 @@ __global__ __launch_bounds__(kWalkBlock) void serial_kernel(const StreamTable st
         const uint64_t off = (g - g0) << st.span_log2;
         const uint64_t seg_end = min(off + (1ull << st.span_log2), len);
         if (!ready) {
-            init_reader<kBits>(r, st, wp, (uint32_t)si, len, win + threadIdx.x * kSlot);
+            r.init(st.ptrs[si], len, win + threadIdx.x * kSlot);
             ready = true;
         }
-        Hop hp{g0, st.span_log2, kNoCand};
-        (void)rewalk<kAlgo, kBits>(x, g, seg_end, len, r, wp, T, ws, nbuf + threadIdx.x * kNew, hp);
+        (void)rewalk<kAlgo>(x, g, seg_end, len, r, wp, T, ws, nbuf + threadIdx.x * kNew);
     }
 }
 
-// ---- wave-cooperative walks (Rabin, UltraCDC; bitmap mode) ------------------
+// ---- wave-cooperative walks (bitmap mode, every rule) -----------------------
 // One wave per segment, its 64 lanes on ONE chain: a step reads 64 position-
 // words of the bitmaps (4096 positions, coalesced, straight from L2 / HBM)
 // and finds the first event with ballots and a lane scan, so a chain moves
-// thousands of positions per step and the lanes never diverge.  (The lane-
-// per-segment walks above advance 64 positions per lane step, and 64 lanes at
-// unrelated points of their chains pay for each other's cut bookkeeping.)
+// thousands of positions per step and the lanes never diverge.  (Lane-per-
+// segment walks over the bitmaps advanced 64 positions per lane step, and 64
+// lanes at unrelated points of their chains paid for each other's cut
+// bookkeeping: removed, profiles/r03_walk/r03s_*, r03t_*.)
 // Every chain value (start, cut) is wave-uniform.
 
 // One stream's bitmaps: position-word k of bitmap b at w[k * nbm + b];
@@ -1173,7 +882,7 @@ __device__ uint64_t wcut_seq(const WBm &B, uint64_t s, uint64_t n, const WalkPar
 // Candidate C at offset x (0..63) of word w: its 24 windows end at C-1 ..
 // C-24, all inside words w-1 (lo) and w (hi) of the primary (p*) and
 // secondary (s*) bitmaps.  Returns the leap (1..24), or 0 when C is accepted
-// (cut_leap_bits: the nearest failing primary window at field bit j leaps
+// (cut_leap's rule: the nearest failing primary window at field bit j leaps
 // 3 + j; then the secondary windows C-23, C-24 leap 2, 1).
 static_assert(CDC_LEAP_WINDOWS == CDC_LEAP_PRIMARY + 2, "two secondary windows");
 
@@ -1194,7 +903,7 @@ __device__ __forceinline__ uint32_t leap_step(uint64_t plo, uint64_t phi, uint64
 // over the word's 64 candidates (unrolled, no divergence):
 //  1. forward: the next candidate after each one.  With the last primary
 //     failing window lz before x kept incrementally, a primary failure leaps
-//     to lz + 25 (the leap 3 + j of cut_leap_bits), else the secondary windows
+//     to lz + 25 (the leap 3 + j of leap_step), else the secondary windows
 //     x-23, x-24 leap 2 / 1, else x is accepted.  Packed 4 per VGPR.
 //  2. backward: the orbit result of each candidate, res[x] = accepted (64 + x),
 //     the entry into the next word (next - 64), or res[next], kept in the
@@ -1289,7 +998,7 @@ __global__ __launch_bounds__(256) void jtab_kernel(const StreamTable st, const W
     }
 }
 
-// cut_leap_bits for one wave: leaps within the start candidate's word (its
+// cut_leap over the bitmaps for one wave: leaps within the start candidate's word (its
 // four bitmap words loaded once), then the orbit through word tables up to the
 // next 512-position block boundary, block tables while a whole block is at or
 // before the bound E, and word tables up to E's word (an accepted position
@@ -1459,10 +1168,7 @@ __global__ __launch_bounds__(256) void wwalk_kernel(const StreamTable st, const 
 // a re-walk without a meeting point does not walk the segment twice (SeqCDC's
 // fix-up rounds per GiB at 4/8/16 KiB: 8 held starts 0.37 ms, 128: 0.29;
 // profiles/r03_walk/r03as_rewalk_held_starts.log).
-#ifndef CDC_WNEW  // (experiment builds, tools/build_variants.py)
-#define CDC_WNEW 128
-#endif
-constexpr uint32_t kWNew = CDC_WNEW;
+constexpr uint32_t kWNew = 128;
 static_assert(kWNew <= 128, "two registers of held starts");
 
 // Moves list[j .. lim) to list[m ..) (entries at or past cap dropped), 64 at a
@@ -2108,46 +1814,19 @@ __global__ __launch_bounds__(kWalkBlock) void bits_kernel(const StreamTable st, 
 // 1327, 32 x 16 (conflict-free, one block per CU) 1165
 // (profiles/r03_walk/r03ah_rabin_bits_variants.txt).  Lane l hashes 1/64 of its wave's segment from a
 // 48-byte warm-up (as bits_kernel<2>), the digest as two dwords.
-#ifndef CDC_RABIN_REPS  // (experiment builds, tools/build_variants.py)
-#define CDC_RABIN_REPS 16
-#endif
-#ifndef CDC_RABIN_WAVES
-#define CDC_RABIN_WAVES 8
-#endif
-// Skewed replicas (CDC_RABIN_SKEW=1): entry e's 16 replicas at e * 136 bytes
-// (17 slots), so the bank of a lookup depends on the entry too -- lanes l and
-// l+16 share a replica and used to collide on every lookup (bank = 2r only:
-// 48 % of LDS cycles were conflicts, profiles/r04_walk/r04f_pmc_walk.txt);
-// with the skew they collide when their entries agree mod 16.
-#ifndef CDC_RABIN_SKEW
-#define CDC_RABIN_SKEW 0  // measured slower: 1262 vs 1346 GiB/s (profiles/r05/r05g_rabin_*.log)
-#endif
-// The leaving byte's term after the shift (CDC_RABIN_OUT2=1): d' = ((d << 8) |
-// in) ^ mod[top(d)] ^ out2[leaving], out2[b] = b x^(8W) mod P (= x^8 out[b]),
-// so the out lookup is off the digest's dependency chain and both table
-// values fold in with one v_xor3 per half: 7 VALU per byte for the digest
-// instead of 11 (the round-4 PMC had the pass VALU-issue-bound at 14.7 per byte).
-#ifndef CDC_RABIN_OUT2
-#define CDC_RABIN_OUT2 0  // measured slower: rbits 0.58-0.60 vs 0.55-0.57 ms (profiles/r05/r05q_*)
-#endif
-// A wave hashes 2^CDC_RABIN_GROUP_LOG2 consecutive pieces of one segment as
-// one range (2 KiB per lane at 32 KiB pieces instead of 512 B): the 48-byte
-// warm-up each lane re-hashes before its range drops from 9.4 % to 2.3 % of
-// the bytes.
-#ifndef CDC_RABIN_GROUP_LOG2
-#define CDC_RABIN_GROUP_LOG2 0  // measured slower at 2: rbits 0.60 vs 0.55-0.57 ms (profiles/r05/r05q_*)
-#endif
-static_assert(CDC_RABIN_GROUP_LOG2 <= 2, "rbits_kernel: a lane's quiet bits are one 32-bit word (<= 2 KiB per lane)");
-__host__ __device__ __forceinline__ uint32_t rabin_group_log2(const StreamTable &st, const WalkParams &wp) {
-    const uint32_t k = st.span_log2 - wp.piece_log2;
-    return k < CDC_RABIN_GROUP_LOG2 ? k : CDC_RABIN_GROUP_LOG2;
-}
+// Measured slower and removed: skewed replicas (entry e's 16 replicas at
+// e * 136 bytes, so lanes l and l + 16 collide only when their entries agree
+// mod 16) 1262 vs 1346 GiB/s (profiles/r05/r05g_rabin_*.log); the leaving
+// byte's term folded in after the shift from a table x^8 out[b] (off the
+// digest's dependency chain) rbits 0.58-0.60 vs 0.55-0.57 ms, and a wave
+// hashing 4 consecutive pieces as one range (less warm-up re-hashing) 0.60 ms
+// (profiles/r05/r05q_*).
 // (Its input loads re-fetch: FETCH_SIZE 1.76x of the input, the halves of a
 // 128-byte line being asked for one iteration apart by 1024 lanes per CU.
 // Non-temporal second halves made it 1.90x and the pass slower, and a whole
 // line per iteration needs 169 VGPRs: profiles/r05/r05y_*.)
-constexpr int kRabinReps = CDC_RABIN_REPS;
-constexpr int kRabinWaves = CDC_RABIN_WAVES;  // pieces per block (64 KiB of tables shared by 8 waves)
+constexpr int kRabinReps = 16;
+constexpr int kRabinWaves = 8;  // pieces per block (64 KiB of tables shared by 8 waves)
 
 typedef const __attribute__((address_space(3))) uint64_t lds_w64;
 typedef const __attribute__((address_space(3))) char lds_wchar;
@@ -2158,40 +1837,21 @@ __global__ __launch_bounds__(64 * kRabinWaves) void rbits_kernel(const StreamTab
     // (out: the leaving byte) or one v_lshl_or (mod: the digest's top byte).
     // (Two interleaved chains per lane -- more independent lookups in flight
     // -- need ~2x the registers and spilled at the 128 VGPRs of 16 waves / CU.)
-#if CDC_RABIN_SKEW
-    constexpr uint32_t kStride = 136;  // bytes per entry (17 slots of 8: 16 replicas + a skew slot)
-    __shared__ uint64_t rt[2 * 256 * 17];  // mod table, then out table
-    static_assert(kRabinReps == 16, "rbits_kernel: 16 replicas per table");
-    for (int i = threadIdx.x; i < 2 * 256 * 17; i += 64 * kRabinWaves) {
-        const int t = i / (256 * 17), e = (i % (256 * 17)) / 17;
-        rt[i] = wp.tabs[(t ? 256 : 0) + e];
-    }
-#else
     __shared__ uint64_t rt[256 * 32];
     static_assert(kRabinReps == 16, "rbits_kernel: 16 replicas per table");
     for (int i = threadIdx.x; i < 256 * 32; i += 64 * kRabinWaves) {
         const int e = i >> 5, k = i & 31;
-        uint64_t v = wp.tabs[(k < 16 ? 0 : 256) + e];
-        if (CDC_RABIN_OUT2 && k >= 16) v = (v << 8) ^ wp.tabs[v >> wp.rabin_shift];  // x^8 out[e] mod P
-        rt[i] = v;
+        rt[i] = wp.tabs[(k < 16 ? 0 : 256) + e];
     }
-#endif
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63;
     Piece pc;
-    const uint32_t grp = rabin_group_log2(st, wp);
-    if (!piece_of(st, wp, ((uint64_t)blockIdx.x * kRabinWaves + wave_id()) << grp, pc)) return;
-#if CDC_RABIN_SKEW
-    const uint32_t om = (lane & 15) * 8, oo = 256 * kStride + om;  // this lane's mod / out replica
-#else
+    if (!piece_of(st, wp, (uint64_t)blockIdx.x * kRabinWaves + wave_id(), pc)) return;
     const uint32_t om = (lane & 15) * 8, oo = 128 + om;  // this lane's mod / out replica
-#endif
     lds_wchar *tb = (lds_wchar *)rt;
     const uint64_t len = st.lens[pc.si];
     const uint8_t *base = st.ptrs[pc.si];
-    // bytes per lane (a multiple of 64; the group's pieces are consecutive in
-    // the segment, in bytes and in bitmap words)
-    const uint64_t w = (1ull << (wp.piece_log2 + grp)) >> 6;
+    const uint64_t w = (1ull << wp.piece_log2) >> 6;  // bytes per lane (a multiple of 64)
     const uint64_t p0 = pc.off + lane * w;
     uint32_t qm = 0, qa = 0;  // bit i: word i of the lane's range has no hit / only hits (quiet runs)
     if (p0 < len) {
@@ -2203,29 +1863,14 @@ __global__ __launch_bounds__(64 * kRabinWaves) void rbits_kernel(const StreamTab
     #pragma unroll
             for (int j = 0; j < 16; ++j) {
                 const uint32_t ow = word_of(old, j >> 2), cw = word_of(cur, j >> 2);
-#if CDC_RABIN_SKEW
-                const uint32_t ao = __umul24((ow >> (8 * (j & 3))) & 0xFFu, kStride) + oo;
-#else
                 const uint32_t ao = __builtin_amdgcn_perm(oo, ow, 0x0c0c0004u | ((uint32_t)(j & 3) << 8));
-#endif
                 const uint64_t o = *reinterpret_cast<lds_w64 *>(tb + ao);
-#if CDC_RABIN_OUT2 && !CDC_RABIN_SKEW
-                // o = out2[leaving byte], folded in after the shift (off the chain)
-                const uint64_t m = *reinterpret_cast<lds_w64 *>(tb + (((hi >> tsh) << 8) | om));
-                hi = __builtin_amdgcn_alignbit(hi, lo, 24) ^ (uint32_t)(m >> 32) ^ (uint32_t)(o >> 32);
-                // (lo << 8) | the entering byte, one v_perm
-                lo = __builtin_amdgcn_perm(lo, cw, 0x06050400u | (uint32_t)(j & 3)) ^ (uint32_t)m ^ (uint32_t)o;
-#else
                 lo ^= (uint32_t)o;
                 hi ^= (uint32_t)(o >> 32);
-#if CDC_RABIN_SKEW
-                const uint64_t m = *reinterpret_cast<lds_w64 *>(tb + (__umul24(hi >> tsh, kStride) + om));
-#else
                 const uint64_t m = *reinterpret_cast<lds_w64 *>(tb + (((hi >> tsh) << 8) | om));
-#endif
                 hi = __builtin_amdgcn_alignbit(hi, lo, 24) ^ (uint32_t)(m >> 32);
+                // (lo << 8) | the entering byte, one v_perm
                 lo = __builtin_amdgcn_perm(lo, cw, 0x06050400u | (uint32_t)(j & 3)) ^ (uint32_t)m;
-#endif
                 if (test) bits |= min(lo & rmask, 1u) << (sh + j);
             }
         };
@@ -2386,158 +2031,6 @@ __global__ __launch_bounds__(256) void lbits_kernel(const StreamTable st, const 
         const uint64_t full = __ballot((prw & sew) == ~0ull);
         if (wp.rsum && lane == 0) wp.rsum[(pc.wbase >> 6) + it] = full;
     }
-}
-
-// ---- link mode (Rabin, UltraCDC, LeapCDC) ---------------------------------------
-// Candidates: the positions where a chunk can start after a cut that is not a
-// max / end / LEST cut, whatever the previous chunk's start -- so every such
-// cut lands on one:
-//   Rabin  q = p + 1 for a window hit at p (cut_rabin_bits returns i + 1);
-//   Ultra  a mask_s or mask_l hit at q (cut_ultra_bits returns i + j there);
-//   Leap   its 22 primary windows (ending at q-1 .. q-22) and 2 secondary
-//          windows (q-23, q-24) eligible (cut_leap_bits returns c only
-//          then): runs of 22 set bits by doubling over two words.
-// Each lane produces the candidate mask of one 64-position word.
-template <int kAlgo>
-__device__ __forceinline__ uint64_t cand_word(const uint64_t *bm, uint64_t K) {
-    if constexpr (kAlgo == 2) {  // Rabin, one bitmap
-        const uint64_t h1 = bm[K], h0 = K ? bm[K - 1] : 0;
-        return (h1 << 1) | (h0 >> 63);
-    } else if constexpr (kAlgo == 4) {  // Ultra: mask_s | mask_l
-        return bm[K * 3] | bm[K * 3 + 1];
-    } else {  // Leap
-        const uint64_t p1 = bm[K * 2], s1 = bm[K * 2 + 1];
-        const uint64_t p0 = K ? bm[K * 2 - 2] : 0, s0 = K ? bm[K * 2 - 1] : 0;
-        typedef unsigned __int128 u128;
-        const u128 V = ((u128)p1 << 64) | p0, W = ((u128)s1 << 64) | s0;
-        const u128 e2 = V & (V << 1), e4 = e2 & (e2 << 2), e8 = e4 & (e4 << 4), e16 = e8 & (e8 << 8);
-        const u128 e22 = e16 & (e4 << 16) & (e2 << 20);  // bit b: primary bits b-21 .. b all set
-        return (uint64_t)(e22 >> 63) & (uint64_t)(W >> 41) & (uint64_t)(W >> 40);
-    }
-}
-
-template <int kAlgo>
-__global__ __launch_bounds__(kWalkBlock) void cand_kernel(const StreamTable st, const WalkParams wp) {
-    constexpr uint32_t kNbm = kAlgo == 2 ? 1 : kAlgo == 4 ? 3 : 2;
-    // lowest position a cut can reach: min >= 1 (Rabin), >= 8 (Ultra), >= 32 (Leap)
-    constexpr uint64_t kLow = kAlgo == 2 ? 1 : kAlgo == 4 ? 8 : 32;
-    const uint64_t g = blockIdx.x;
-    uint32_t si;
-    uint64_t off;
-    locate(st, g, si, off);
-    const uint64_t len = st.lens[si];
-    const uint64_t gbase = st.span_base[si];
-    const uint64_t *bm = wp.bm + gbase * (uint64_t)wp.seg_words * kNbm;  // the stream's bitmaps
-    const uint64_t w0 = (off >> 6);                                       // stream word of the segment's start
-    const uint32_t lane = threadIdx.x;
-    uint32_t total = 0;
-    uint32_t *out = wp.cpos + g * wp.ccap;
-    for (uint32_t r = 0; r < wp.seg_words / 64; ++r) {
-        const uint64_t K = w0 + (uint64_t)r * 64 + lane;  // this lane's stream word
-        uint64_t m = 0;
-        if (K * 64 < len) {
-            m = cand_word<kAlgo>(bm, K);
-            const uint64_t q0 = K * 64;  // position of bit 0
-            if (q0 < kLow) m &= ~0ull << (kLow - q0);
-            if (len - q0 < 64) m &= (1ull << (len - q0)) - 1;  // q < len
-        }
-        // ordered compaction: an exclusive prefix of the lanes' counts
-        const uint32_t c = (uint32_t)__popcll(m);
-        uint32_t x = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(x, o);
-            if (lane >= (uint32_t)o) x += y;
-        }
-        uint32_t slot = total + x - c;
-        for (uint64_t mm = m; mm; mm &= mm - 1, ++slot)
-            if (slot < wp.ccap) out[slot] = (uint32_t)(((uint64_t)r * 64 + lane) * 64 + __builtin_ctzll(mm));
-        total += (uint32_t)__shfl(x, 63);
-    }
-    if (lane == 0) wp.ccnt[g] = total;
-}
-
-// The rule's next start after a chunk starting at c, over the global bitmaps.
-template <int kAlgo>
-__device__ __forceinline__ uint64_t link_next(const WalkParams &wp, uint64_t gbase, uint64_t c, uint64_t len) {
-    constexpr uint32_t kNbm = kAlgo == 2 ? 1 : kAlgo == 4 ? 3 : 2;
-    GReader r;
-    r.init(wp.bm + gbase * (uint64_t)wp.seg_words * kNbm, ((len + 63) >> 6) * kNbm);
-    if constexpr (kAlgo == 2) return c + cut_rabin_bits(r, c, len - c, wp);
-    else if constexpr (kAlgo == 4) return c + cut_ultra_bits(r, c, len - c, wp);
-    else return c + cut_leap_bits(r, c, len - c, wp);
-}
-
-// Slot of a link's next start nx: its candidate slot, else a new virtual
-// entry (to be linked by round `round`), else kNoCand (stream end, the
-// budget or the rounds spent: the walk then walks the rule from there).
-__device__ __forceinline__ uint32_t next_slot(const WalkParams &wp, uint32_t sl2, uint64_t gbase, uint64_t nx,
-                                              uint64_t len, uint32_t round) {
-    if (nx >= len) return kNoCand;
-    const Hop hp{gbase, sl2, kNoCand};
-    const uint32_t ci = find_cand(wp, hp, nx);
-    if (ci != kNoCand || round >= kVirtRounds) return ci;
-    const unsigned long long v = atomicAdd(&wp.vcnt[0], 1ull);
-    if (v >= wp.vcap) return kNoCand;
-    wp.vpos[v] = nx;
-    wp.vseg[v] = (uint32_t)gbase;
-    return kVirt | (uint32_t)v;
-}
-
-// Lane per candidate slot (k-major: the 64 lanes of a wave share k, so the
-// waves of high k retire at once): the next chunk start after a chunk
-// starting at the candidate, and that start's slot.
-template <int kAlgo>
-__global__ __launch_bounds__(256) void link_kernel(const StreamTable st, const WalkParams wp) {
-    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const uint64_t S = st.total_spans;
-    const uint64_t k = t / S, g = t - k * S;
-    if (k >= wp.ccap) return;
-    const uint32_t n = wp.ccnt[g];
-    if (n > wp.ccap || k >= n) return;
-    uint32_t si;
-    uint64_t off;
-    locate(st, g, si, off);
-    const uint64_t len = st.lens[si];
-    const uint64_t gbase = st.span_base[si];
-    const uint64_t slot = g * wp.ccap + k;
-    const uint64_t nx = link_next<kAlgo>(wp, gbase, off + wp.cpos[slot], len);
-    wp.lnext[slot] = nx;
-    wp.lidx[slot] = next_slot(wp, st.span_log2, gbase, nx, len, 0);
-}
-
-// Round r of the virtual links: the entries allocated before it and after
-// round r-1 started (vcnt[1 + r] .. vcnt[2 + r], snapshots by vmark_kernel).
-template <int kAlgo>
-__global__ __launch_bounds__(256) void vlink_kernel(const StreamTable st, const WalkParams wp, uint32_t round) {
-    const uint64_t v = wp.vcnt[1 + round] + (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const uint64_t end = min(wp.vcnt[2 + round], (unsigned long long)wp.vcap);
-    if (v >= end) return;
-    const uint64_t gbase = wp.vseg[v];
-    uint32_t si;
-    uint64_t off;
-    locate(st, gbase, si, off);
-    const uint64_t len = st.lens[si];
-    const uint64_t nx = link_next<kAlgo>(wp, gbase, wp.vpos[v], len);
-    wp.vnext[v] = nx;
-    wp.vidx[v] = next_slot(wp, st.span_log2, gbase, nx, len, round + 1);
-}
-
-// Snapshot of the allocation counter: the end of virtual round r.
-__global__ void vmark_kernel(const WalkParams wp, uint32_t round) { wp.vcnt[2 + round] = wp.vcnt[0]; }
-
-template <int kAlgo>
-hipError_t links_dispatch(const StreamTable &st, const WalkParams &wp, hipStream_t s) {
-    hipError_t e = hipMemsetAsync(wp.vcnt, 0, (2 * kVirtRounds + 2) * sizeof(unsigned long long), s);
-    if (e != hipSuccess) return e;
-    cand_kernel<kAlgo><<<(unsigned)st.total_spans, kWalkBlock, 0, s>>>(st, wp);
-    const uint64_t threads = st.total_spans * (uint64_t)wp.ccap;
-    link_kernel<kAlgo><<<(unsigned)((threads + 255) / 256), 256, 0, s>>>(st, wp);
-    for (uint32_t r = 0; r < kVirtRounds; ++r) {  // round r links the entries allocated by round r - 1
-        vmark_kernel<<<1, 1, 0, s>>>(wp, r);
-        vlink_kernel<kAlgo><<<(unsigned)((wp.vcap + 255) / 256), 256, 0, s>>>(st, wp, r);
-    }
-    return hipGetLastError();
 }
 
 // ---- prefix and output -----------------------------------------------------
@@ -2705,24 +2198,24 @@ __global__ __launch_bounds__(kFinishThreads) void finish_kernel(const StreamTabl
             ws.flags[i] = i >= 4 && (i & 3) == 2 ? ~0ull : 0ull;
 }
 
-template <int kAlgo, bool kBits>
+template <int kAlgo>
 hipError_t walk_dispatch(int which, const StreamTable &st, const WalkParams &wp, const WalkState &ws,
                          hipStream_t s) {
     const unsigned blocks = (unsigned)((st.total_spans + kWalkBlock - 1) / kWalkBlock);
-    if (which == 0) walk_kernel<kAlgo, kBits><<<blocks, kWalkBlock, 0, s>>>(st, wp, ws);
-    else if (which == 1) fix_kernel<kAlgo, kBits><<<blocks, kWalkBlock, 0, s>>>(st, wp, ws);
-    else serial_kernel<kAlgo, kBits><<<(st.n + kWalkBlock - 1) / kWalkBlock, kWalkBlock, 0, s>>>(st, wp, ws);
+    if (which == 0) walk_kernel<kAlgo><<<blocks, kWalkBlock, 0, s>>>(st, wp, ws);
+    else if (which == 1) fix_kernel<kAlgo><<<blocks, kWalkBlock, 0, s>>>(st, wp, ws);
+    else serial_kernel<kAlgo><<<(st.n + kWalkBlock - 1) / kWalkBlock, kWalkBlock, 0, s>>>(st, wp, ws);
     return hipGetLastError();
 }
 
+// The byte-mode lane kernels (which: 0 walk, 1 fix, 2 serial).
 hipError_t dispatch(int which, const StreamTable &st, const WalkParams &wp, const WalkState &ws, hipStream_t s) {
     if (!st.total_spans) return hipSuccess;
-    const bool bits = wp.nbm != 0;
     switch (wp.algo) {
-        case 2: return bits ? walk_dispatch<2, true>(which, st, wp, ws, s) : walk_dispatch<2, false>(which, st, wp, ws, s);
-        case 4: return bits ? walk_dispatch<4, true>(which, st, wp, ws, s) : walk_dispatch<4, false>(which, st, wp, ws, s);
-        case 5: return bits ? walk_dispatch<5, true>(which, st, wp, ws, s) : walk_dispatch<5, false>(which, st, wp, ws, s);
-        case 6: return bits ? walk_dispatch<6, true>(which, st, wp, ws, s) : walk_dispatch<6, false>(which, st, wp, ws, s);
+        case 2: return walk_dispatch<2>(which, st, wp, ws, s);
+        case 4: return walk_dispatch<4>(which, st, wp, ws, s);
+        case 5: return walk_dispatch<5>(which, st, wp, ws, s);
+        case 6: return walk_dispatch<6>(which, st, wp, ws, s);
         default: return hipErrorInvalidValue;
     }
 }
@@ -2730,7 +2223,7 @@ hipError_t dispatch(int which, const StreamTable &st, const WalkParams &wp, cons
 }  // namespace
 
 bool bits_write_summary(const WalkParams &wp) {
-    if (!wp.wave || !wp.nbm || wp.piece_log2 < 12 || wp.piece_log2 > 15) return false;
+    if (!wp.nbm || wp.piece_log2 < 12 || wp.piece_log2 > 15) return false;
     switch (wp.algo) {
         case 2: return wp.rabin_mask <= 0xFFFFFFFFull && wp.rabin_shift >= 32;  // rbits_kernel
         case 4: case 5: return wp.bits_fine != 0;                               // ubits / lbits_kernel
@@ -2766,8 +2259,7 @@ hipError_t launch_bits(const StreamTable &st, const WalkParams &wp, hipStream_t 
     const uint64_t pieces = st.total_spans << (st.span_log2 - wp.piece_log2);
     const unsigned blocks = (unsigned)pieces;
     if (wp.algo == 2 && wp.rabin_mask <= 0xFFFFFFFFull && wp.rabin_shift >= 32 && wp.piece_log2 >= 12)
-        rbits_kernel<<<(unsigned)(((pieces >> rabin_group_log2(st, wp)) + kRabinWaves - 1) / kRabinWaves),
-                       64 * kRabinWaves, 0, s>>>(st, wp);
+        rbits_kernel<<<(unsigned)((pieces + kRabinWaves - 1) / kRabinWaves), 64 * kRabinWaves, 0, s>>>(st, wp);
     else if (wp.algo == 2) bits_kernel<2><<<blocks, kWalkBlock, 0, s>>>(st, wp);
     else if (wp.algo == 4 && wp.bits_fine && wp.piece_log2 >= 12)
         ubits_kernel<<<(unsigned)((pieces + 3) / 4), 256, 0, s>>>(st, wp);
@@ -2777,7 +2269,7 @@ hipError_t launch_bits(const StreamTable &st, const WalkParams &wp, hipStream_t 
     else if (wp.algo == 5) bits_kernel<5><<<blocks, kWalkBlock, 0, s>>>(st, wp);
     else if (wp.algo == 6) bits_kernel<6><<<blocks, kWalkBlock, 0, s>>>(st, wp);
     else return hipErrorInvalidValue;
-    if (wp.algo == 5 && wp.wave && wp.jt && wp.piece_log2 >= 12)  // LeapCDC word tables
+    if (wp.algo == 5 && wp.jt && wp.piece_log2 >= 12)  // LeapCDC word tables
         jtab_kernel<<<(unsigned)((pieces + 3) / 4), 256, 0, s>>>(st, wp);
     if (wp.rsum && wp.qseg) {
         const unsigned qb = (unsigned)((st.total_spans + 3) / 4);
@@ -2789,16 +2281,8 @@ hipError_t launch_bits(const StreamTable &st, const WalkParams &wp, hipStream_t 
     return hipGetLastError();
 }
 
-hipError_t launch_links(const StreamTable &st, const WalkParams &wp, hipStream_t s) {
-    if (!st.total_spans || !wp.links) return hipSuccess;
-    if (wp.algo == 2) return links_dispatch<2>(st, wp, s);
-    if (wp.algo == 4) return links_dispatch<4>(st, wp, s);
-    if (wp.algo == 5) return links_dispatch<5>(st, wp, s);
-    return hipErrorInvalidValue;
-}
-
 hipError_t launch_walk(const StreamTable &st, const WalkParams &wp, const WalkState &ws, hipStream_t s) {
-    if (wp.wave && wp.nbm && st.total_spans) {
+    if (wp.nbm && st.total_spans) {
         const unsigned blocks = (unsigned)((st.total_spans + 3) / 4);
         if (wp.algo == 2) wwalk_kernel<2><<<blocks, 256, 0, s>>>(st, wp, ws);
         else if (wp.algo == 5) wwalk_kernel<5><<<blocks, 256, 0, s>>>(st, wp, ws);
@@ -2834,7 +2318,7 @@ hipError_t launch_fix(const StreamTable &st, const WalkParams &wp, const WalkSta
     if (snap) snap_kernel<<<(unsigned)(sb < 1024 ? sb : 1024), 256, 0, s>>>(ws, st.total_spans);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (wp.wave && wp.nbm) {
+    if (wp.nbm) {
         const unsigned blocks = (unsigned)((st.total_spans + 3) / 4);
         if (wp.algo == 2) wfix_kernel<2><<<blocks, 256, 0, s>>>(st, wp, ws);
         else if (wp.algo == 5) wfix_kernel<5><<<blocks, 256, 0, s>>>(st, wp, ws);
@@ -2846,7 +2330,7 @@ hipError_t launch_fix(const StreamTable &st, const WalkParams &wp, const WalkSta
 }
 
 hipError_t launch_serial(const StreamTable &st, const WalkParams &wp, const WalkState &ws, hipStream_t s) {
-    if (wp.wave && wp.nbm && st.total_spans) {
+    if (wp.nbm && st.total_spans) {
         const unsigned blocks = (unsigned)((st.n + 3) / 4);
         if (wp.algo == 2) wserial_kernel<2><<<blocks, 256, 0, s>>>(st, wp, ws);
         else if (wp.algo == 5) wserial_kernel<5><<<blocks, 256, 0, s>>>(st, wp, ws);

@@ -3,8 +3,9 @@
 //
 // Every stream of the batch is cut into segments of 2^seg_log2 bytes (a chunk
 // may span whole segments: they then hold no start, E = X).  One wave (bitmap
-// mode; one lane in byte mode) owns one segment and runs the
-// algorithm's exact byte-serial cut rule (the same rule as oracle/cdc_oracle.c)
+// mode, wp.nbm != 0: over per-position predicate bitmaps) or one lane (byte
+// mode: over the bytes) owns one segment and runs the algorithm's exact
+// byte-serial cut rule (the same rule as oracle/cdc_oracle.c)
 // from a warm-up start `warm` bytes before the segment, recording the chunk
 // starts that fall inside it.  A chain from the warm-up start usually merges
 // with the true chain before the segment starts; the fix-up rounds re-walk
@@ -45,38 +46,16 @@ struct WalkParams {
     uint32_t cap;             // chunk starts recorded per segment
     uint64_t warm;            // warm-up bytes before a segment
     const uint64_t *tabs;     // device [768]: rabin mod[256], rabin out[256], leap hash[256]
-    // Bitmap mode (Rabin with min >= 48, Ultra, Leap): the per-position
-    // predicates of bits_kernel, nbm bitmaps interleaved per 64-bit word:
+    // Bitmap mode (Rabin with min >= 48, Ultra, Leap, Seq with seq_len <= 63):
+    // the per-position predicates of the bitmap pass, nbm bitmaps interleaved
+    // per 64-bit word:
     // word k of bitmap b of segment g at bm[(g * seg_words + k) * nbm + b].
     uint64_t *bm;
-    uint32_t nbm;             // 0 = byte mode; Rabin 1 (hit), Ultra 3 (mask_s, mask_l, 8-byte repeat), Leap 2
+    uint32_t nbm;             // 0 = byte mode (lane walks); Rabin, Seq 1, Ultra 3 (mask_s, mask_l, 8-byte repeat), Leap 2
     uint32_t seg_words;       // 64-bit words per segment and bitmap (segment bytes / 64)
     uint32_t piece_log2;      // the data-parallel passes run over pieces of 2^piece_log2 bytes (<= segment)
     uint32_t bits_fine;       // bitmap pass: lane per 64-position word (Ultra, Leap, Seq)
-    uint32_t ahead;           // fix-up round: segments one lane may re-walk (1 = plain Jacobi)
-    uint32_t wave;            // 1: wave-cooperative walk_kernel (Rabin / UltraCDC bitmap mode)
-    // Link mode (LeapCDC): the rule's candidate cut positions (content-defined:
-    // every cut that is not a max / end cut lands on one) are listed per
-    // segment, and the next chunk start after a chunk starting at each of
-    // them is computed once, a lane per candidate (link_kernel); the walks
-    // then hop over links and walk the rule only from other starts.  A
-    // segment with more than ccap candidates (low-entropy data) keeps direct
-    // walks.
-    uint32_t links;           // 1: link mode
-    uint32_t ccap;            // candidates per segment
-    uint32_t *ccnt;           // [S] candidates of each segment (> ccap: overflowed, no links)
-    uint32_t *cpos;           // [S * ccap] their segment offsets, ascending
-    uint64_t *lnext;          // [S * ccap] next chunk start (stream offset) after a chunk starting there
-    uint32_t *lidx;           // [S * ccap] candidate slot of that next start, kVirt | v, or kNoCand
-    // Virtual starts: a link's next start that is not a candidate (a max cut)
-    // gets its own link (vnext / vidx), so that a walk never walks the rule
-    // from a start a link reached; up to kVirtRounds levels deep.
-    uint32_t vcap;            // virtual entries (8 per segment; past it: kNoCand, the walk walks)
-    unsigned long long *vcnt; // [2 * kVirtRounds + 2]: entries allocated, per round: first entry of the round
-    uint64_t *vpos;           // [vcap] stream offset of the virtual start
-    uint32_t *vseg;           // [vcap] its stream's first segment (for find_cand)
-    uint64_t *vnext;          // [vcap] next start after a chunk starting there
-    uint32_t *vidx;           // [vcap] slot of that next start (candidate, kVirt | v, kNoCand)
+    uint32_t ahead;           // fix-up round: segments one wave / lane may re-walk (1 = plain Jacobi)
     // LeapCDC wave walks: per 64-position word w, the leap orbit of each
     // entry candidate 64 w + e (e < 24) through the word, jt[w * 24 + e]:
     // < 24 = its entry into word w + 1, >= 64 = accepted at 64 w + (v - 64).
@@ -101,16 +80,12 @@ struct WalkParams {
     uint8_t *qseg;
 };
 
-constexpr uint32_t kNoCand = 0xFFFFFFFFu;
-constexpr uint32_t kVirt = 0x80000000u;
-constexpr uint32_t kVirtRounds = 3;
-
 struct WalkState {
     uint64_t *E;      // [S] entry: first chunk start >= segment start
     uint64_t *X;      // [S] exit: first chunk start >= segment end (or the stream length)
     uint32_t *N;      // [S] chunk starts inside the segment
     uint64_t *list;   // [S * cap] those starts (stream offsets)
-    uint64_t *Xs;     // [S] exits snapshot of a fix-up round
+    uint64_t *Xs;     // [S] exits snapshot of a fix-up round (written by round 0's walk and snap_kernel only)
     uint64_t *Es;     // [S] entries snapshot of a fix-up round
     uint64_t *P;      // [S + 1] exclusive prefix of N (chunk index of each segment)
     uint64_t *bsum;   // [blocks + 1] per-block sums of the prefix
@@ -133,8 +108,6 @@ hipError_t launch_bits(const StreamTable &st, const WalkParams &wp, hipStream_t 
 // Zeroes the main flag block and the `rounds` round blocks after it (their
 // word 2, the lowest changed segment, to ~0): one launch instead of three fills.
 hipError_t launch_flags_init(unsigned long long *flags, uint32_t rounds, hipStream_t s);
-// Link mode: candidate lists (wave per segment), then the links (lane per candidate).
-hipError_t launch_links(const StreamTable &st, const WalkParams &wp, hipStream_t s);
 hipError_t launch_walk(const StreamTable &st, const WalkParams &wp, const WalkState &ws, hipStream_t s);
 // One Jacobi round: snapshot X and E (one launch; snap = false for round 0,
 // whose snapshot the walk itself wrote), then re-walk every segment whose

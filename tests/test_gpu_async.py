@@ -2,11 +2,10 @@
 
 Batches of more than 8 MiB are enqueued back to back with no host wait, each
 with its own host staging block (three in rotation) and device table slot
-(four); results are collected later.  Where the sizes allow (avg 8 KiB and up
-at max <= 64 KiB) each batch's resolve runs on a second stream beside the
-next batch's scan, with the regular kernels (fastcdc.hip) by default; the
-overlap kernel set (fastcdc_ovl.hip) only with CHUNKFS_AMD_OVERLAP=1, and
-CHUNKFS_AMD_OVERLAP=0 keeps both on one stream.  Every batch's chunks must
+(four); results are collected later.  Each batch's resolve runs on a second
+stream beside the next batch's scan (the default; any non-zero
+CHUNKFS_AMD_OVERLAP), and CHUNKFS_AMD_OVERLAP=0 keeps both on one stream.
+Every batch's chunks must
 equal the oracle's, whatever the interleaving: multi-stream batches,
 ragged and empty streams, different outputs per batch, bursts ended by
 cdc_batch_sync or by a synchronous call, and small batches that complete
@@ -196,9 +195,8 @@ def test_async_implicit_drain_result_held_for_batch_sync():
 @pytest.mark.parametrize("overlap", ["2", "1", "0"])
 def test_async_long_burst_overlap_on_and_off(monkeypatch, overlap):
     """Twelve back-to-back batches of varying shape (every device slot and host
-    block reused several times) on two streams with the regular kernels (the
-    default), with the overlap set, and on one stream: identical, exact
-    chunks."""
+    block reused several times) on two streams (the default; CHUNKFS_AMD_OVERLAP
+    2 and 1 are synonyms) and on one stream (0): identical, exact chunks."""
     import torch
     import chunkfs_amd as c
     monkeypatch.setenv("CHUNKFS_AMD_OVERLAP", overlap)
@@ -221,8 +219,8 @@ def test_async_long_burst_overlap_on_and_off(monkeypatch, overlap):
 
 
 def test_async_dense_sizes_take_the_standard_set():
-    """2/4/8 KiB: records too dense for the overlap set's windows; the async
-    batches run the standard kernels, still exact."""
+    """2/4/8 KiB (dense records): the async batches on two streams, still
+    exact."""
     import torch
     import chunkfs_amd as c
     sizes = (2048, 4096, 8192)

@@ -352,3 +352,101 @@ def test_quiet_summary_off_paths(monkeypatch):
         ch = cls(c.SizeParams(*sizes)) if cls else c.SeqChunker(0, c.SizeParams(*sizes))
         assert_same(ch.chunk_array(data), oracle.cdc(algo, data, *sizes), f"{algo} bits_fine=0")
         ch.close()
+
+
+# ---- byte-mode lane kernels: fix-up rounds and the in-order pass ---------------
+# 4 KiB segments with a 1-avg warm-up at 256 / 1024 / 4096: most entries are
+# wrong after round 0 and cap = 4096 / 256 + 2 = 18.  The random input is 258
+# segments, so the 64-lane blocks' run-ahead crosses block borders.
+BYTE_SIZES = (256, 1024, 4096)
+# Periodic inputs whose chains never merge under the rule, so 16 rounds of plain
+# Jacobi cannot settle them (period 61 has no content-defined cut at these
+# sizes: every chunk is max = one segment and every entry is right at once).
+# Found with a CPU model of the round schedule over oracle.cdc.
+BYTE_PERIOD = {"rabin": 116, "ultra": 5003, "leap": 8275, "seq": 5003}
+_byte_inputs = {}
+
+
+def _byte_input(key):
+    if key not in _byte_inputs:
+        if key == "random":
+            _byte_inputs[key] = oracle.splitmix64_bytes((1 << 20) + 4321, 17)
+        elif key == "const":
+            _byte_inputs[key] = make_input("const", 600000, 0xAA)
+        else:
+            _byte_inputs[key] = make_input("periodic", 600000, key)
+    return _byte_inputs[key]
+
+
+_byte_refs = {}
+
+
+def _byte_ref(algo, key, sizes, seqcfg=None):
+    k = (algo, key, sizes, seqcfg)
+    if k not in _byte_refs:
+        _byte_refs[k] = oracle.cdc(algo, _byte_input(key), *sizes, seqcfg=seqcfg)
+    return _byte_refs[k]
+
+
+def _device_chunks(ch, data):
+    """One device-resident stream through cdc_chunk_batch_device (so that
+    last_timing() describes this very walk call)."""
+    import torch
+    n = len(data)
+    b = torch.from_numpy(data.copy()).to("cuda:0")
+    cap = ch.batch_max_chunks([n])
+    out = torch.empty((cap, 2), dtype=torch.int64, device="cuda:0")
+    torch.cuda.synchronize()
+    first = ch.chunk_batch_device([b.data_ptr()], [n], out.data_ptr(), cap)
+    return out[:first[1]].cpu().numpy().astype(np.uint64)
+
+
+@pytest.mark.parametrize("algo", ALGOS)
+@pytest.mark.parametrize("ahead", ["0,64", "2,3", "16,1"])
+def test_byte_mode_fixup_schedules_exact(algo, ahead, monkeypatch):
+    """The lane-per-segment kernels (byte mode) through their fix-up rounds:
+    run-ahead from round 0 across block borders, a 3-segment run-ahead limit,
+    and plain Jacobi that runs out of rounds into the in-order pass.  A re-walk
+    must leave the round's snapshots alone (only round 0's walk and snap_kernel
+    write them); a fix-up round that rewrote its own snapshot would schedule
+    from mixed states.  Env is read at handle creation."""
+    import chunkfs_amd as c
+    monkeypatch.setenv("CHUNKFS_AMD_WALK_BYTES", "1")
+    monkeypatch.setenv("CHUNKFS_AMD_WALK", "12,1")
+    monkeypatch.setenv("CHUNKFS_AMD_AHEAD", ahead)
+    sizes = BYTE_SIZES
+    cls = {"rabin": c.RabinChunker, "ultra": c.UltraChunker, "leap": c.LeapChunker}.get(algo)
+    ch = cls(c.SizeParams(*sizes)) if cls else c.SeqChunker(0, c.SizeParams(*sizes))
+    what = f"{algo} byte mode ahead={ahead}"
+    assert_same(_device_chunks(ch, _byte_input("random")), _byte_ref(algo, "random", sizes), what + " random")
+    assert ch.last_timing()["fixup_iterations"] > 0  # the fix-up rounds did run
+    period = BYTE_PERIOD[algo]
+    assert_same(_device_chunks(ch, _byte_input(period)), _byte_ref(algo, period, sizes), what + " periodic")
+    if ahead == "16,1":
+        assert ch.last_timing()["overflow_spans"] == 1  # ... and ran out: the in-order pass finished the call
+    assert_same(_device_chunks(ch, _byte_input(61)), _byte_ref(algo, 61, sizes), what + " periodic 61")
+    assert_same(_device_chunks(ch, _byte_input("const")), _byte_ref(algo, "const", sizes), what + " const")
+    ch.close()
+
+
+def test_byte_mode_fixup_rabin_small_min(monkeypatch):
+    """Rabin with min < 48 takes the byte walks by itself."""
+    import chunkfs_amd as c
+    monkeypatch.setenv("CHUNKFS_AMD_WALK", "12,1")
+    monkeypatch.setenv("CHUNKFS_AMD_AHEAD", "2,3")
+    sizes = (16, 64, 256)
+    ch = c.RabinChunker(c.SizeParams(*sizes))
+    assert_same(_device_chunks(ch, _byte_input("random")), _byte_ref("rabin", "random", sizes), f"rabin {sizes}")
+    ch.close()
+
+
+def test_byte_mode_fixup_seq_long_run(monkeypatch):
+    """SeqCDC with seq_length > 63 takes the byte walks by itself."""
+    import chunkfs_amd as c
+    monkeypatch.setenv("CHUNKFS_AMD_WALK", "12,1")
+    monkeypatch.setenv("CHUNKFS_AMD_AHEAD", "2,3")
+    sizes = (300, 1000, 5000)
+    ch = c.SeqChunker(0, c.SizeParams(*sizes), c.SeqConfig(64, 5, 10))
+    assert_same(_device_chunks(ch, _byte_input("random")), _byte_ref("seq", "random", sizes, (0, 64, 5, 10)),
+                "seq length 64")
+    ch.close()

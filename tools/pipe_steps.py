@@ -2,7 +2,8 @@
 """Per-step wall times of back-to-back async FastCDC batches (config-2 stream,
 1 GiB): each call returns once batch k-3 is collected, so in steady state a
 call's duration is the device's step period.  Prints the mean of every 10
-calls for the two-stream default and for one stream (diagnostics).
+calls for the two-stream default (CHUNKFS_AMD_OVERLAP non-zero) and for one
+stream (0) (diagnostics).
 Usage: pipe_steps.py [steps]"""
 import os
 import sys
@@ -19,7 +20,7 @@ buf = torch.empty(n, dtype=torch.uint8, device="cuda:0")
 c.check(c.lib().cdc_fill_splitmix64_device(c.ctypes.c_void_p(buf.data_ptr()), n, 1, None))
 ptrs = np.array([buf.data_ptr()], dtype=np.uint64)
 lens = np.array([n], dtype=np.uint64)
-for ovl in ("2", "0", "2"):
+for ovl in ("1", "0", "1"):
     os.environ["CHUNKFS_AMD_OVERLAP"] = ovl
     ch = c.FastChunker(c.SizeParams(4096, 8192, 16384))
     cap = ch.batch_max_chunks([n])

@@ -3,7 +3,8 @@
 async steps of the config-2 stream on a two-stream handle after (a) 5 warmup
 steps, (b) 200 warmup steps of a ONE-stream handle + 5 of its own, (c) 200 of
 its own.  Transfer from (b) means device state (clocks), not the handle's
-streams / events.  Usage: pipe_warm.py"""
+streams / events.  (CHUNKFS_AMD_OVERLAP: 0 one stream, non-zero two.)
+Usage: pipe_warm.py"""
 import os
 import sys
 import time
@@ -49,15 +50,15 @@ def steps(ch, k):
 for rep in range(2):
     if rep == 0 and os.environ.get("CHUNKFS_AMD_NO_PREWARM"):
         print("(no prewarm)")
-    a = handle("2")
+    a = handle("1")
     steps(a, 5)
     print("rep", rep, "(a) 5 own warmup:      %.4f ms/step" % steps(a, 20), flush=True)
     one = handle("0")
     steps(one, 200)
-    b = handle("2")
+    b = handle("1")
     steps(b, 5)
     print("rep", rep, "(b) 200 one-stream + 5: %.4f ms/step" % steps(b, 20), flush=True)
-    cc = handle("2")
+    cc = handle("1")
     steps(cc, 200)
     print("rep", rep, "(c) 200 own warmup:    %.4f ms/step" % steps(cc, 20), flush=True)
     print("rep", rep, "(c') same handle again: %.4f ms/step" % steps(cc, 20), flush=True)
