@@ -16,6 +16,8 @@ include/chunkfs_amd.h (libchunkfs_amd.so, hand-written HIP for gfx950):
     ChunkStorage::write  system/storage.rs    write_spans()
     Database (digest set) system/database.rs  DedupIndex
     Database + retrieve / read_file_complete  ChunkStore
+    FileSystem / FileLayer  system/mod.rs,    FileSystem, FileHandle
+                            file_layer.rs
 
 Every call runs on the GPU.  There is no CPU fallback: without the built
 library or a gfx950 device the constructors raise.
@@ -36,7 +38,7 @@ __all__ = [
     "KB", "MB", "GB", "SEG_SIZE", "Chunk", "SizeParams", "Chunker", "FastChunker",
     "FSChunker", "RabinChunker", "SuperChunker", "UltraChunker", "LeapChunker",
     "SeqChunker", "OperationMode", "SeqConfig", "CdcError", "write_spans", "StreamWriter", "version",
-    "DedupIndex", "ChunkStore",
+    "DedupIndex", "ChunkStore", "FileSystem", "FileHandle",
 ]
 
 
@@ -596,6 +598,230 @@ class ChunkStore:
         got = self.get_device(d_dig.data_ptr(), n, out.data_ptr(), total)
         assert got == total
         return out[:total].cpu().numpy()
+
+
+class FileHandle:
+    """FileHandle (file_layer.rs:32-41): the file's name, the read cursor, the
+    write measurements and -- unless read-only -- the chunker."""
+
+    def __init__(self, fh, name, chunker):
+        self._fh, self._name, self.chunker = fh, name, chunker
+
+    def name(self):
+        return self._name
+
+    def _close(self):
+        if self._fh:
+            lib().cdc_file_close(self._fh)
+            self._fh = None
+
+    def __del__(self):
+        try:
+            self._close()
+        except Exception:
+            pass
+
+
+class FileSystem:
+    """The reference's FileSystem (system/mod.rs) for CDC chunkers, on one GPU:
+    named files over a ChunkStore, each file's span table in HBM (the device
+    file layer of include/chunkfs_amd.h).  Method names are the reference's.
+
+    One deviation: a span's offset is its true byte position in the file, so
+    appending through a re-opened handle works (the reference restarts the
+    offsets at the handle's 0, file_layer.rs:136-145).  Two quirks are kept:
+    read_from_file returns nothing, cursor stuck, when the span at the cursor is
+    longer than the segment; chunk_count_distribution leaves out the last span.
+    A refused call (CdcError) changes nothing.  Not thread-safe."""
+
+    def __init__(self, store=None, max_chunks=1 << 16, arena_bytes=256 * MB, seg_size=SEG_SIZE, device=0):
+        self.store = store if store is not None else ChunkStore(max_chunks, arena_bytes, device)
+        self.device = self.store.device
+        self.seg_size = int(seg_size)
+        h = ctypes.c_void_p()
+        check(lib().cdc_files_create(self.store._h, self.seg_size, ctypes.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            lib().cdc_files_destroy(h)  # before the store it is bound to
+            self._h = None
+
+    # -- names and handles -------------------------------------------------------
+    def _handle(self, name, chunker, fn, flag):
+        fh = ctypes.c_void_p()
+        check(fn(self._h, name.encode(), flag, ctypes.byref(fh)))
+        return FileHandle(fh, name, chunker)
+
+    def create_file(self, name, chunker, create_new=True):
+        """FileSystem::create_file (mod.rs:81-87) passes create_new = true: an
+        existing file is replaced by an empty one.  create_new=False is
+        FileLayer::create's other branch: CdcError(CDC_EEXIST) if the name exists."""
+        return self._handle(name, chunker, lib().cdc_files_create_file, 1 if create_new else 0)
+
+    def open_file(self, name, chunker):
+        return self._handle(name, chunker, lib().cdc_files_open, 0)
+
+    def open_file_readonly(self, name):
+        return self._handle(name, None, lib().cdc_files_open, 1)
+
+    def file_exists(self, name):
+        return bool(check(lib().cdc_files_exists(self._h, name.encode())))
+
+    def list_files(self):
+        need = check(lib().cdc_files_list(self._h, None, 0))
+        if need == 0:
+            return []
+        buf = ctypes.create_string_buffer(need)
+        assert check(lib().cdc_files_list(self._h, buf, need)) == need
+        return [b.decode() for b in buf.raw[:need].split(b"\0")[:-1]]
+
+    def stat(self, handle):
+        s = _lib.cdc_file_stat_t()
+        check(lib().cdc_file_stat(handle._fh, ctypes.byref(s)))
+        return {f: getattr(s, f) for f, _ in _lib.cdc_file_stat_t._fields_}
+
+    def close_file(self, handle):
+        """WriteMeasurements of the handle's writes: {chunk_time, hash_time} in seconds."""
+        st = self.stat(handle)
+        handle._close()
+        return {"chunk_time": st["chunk_seconds"], "hash_time": st["hash_seconds"]}
+
+    # -- writes ---------------------------------------------------------------------
+    def write_to_file(self, handle, data, stream=None):
+        """FileSystem::write_to_file (mod.rs:93-110): one chunk_data over the whole
+        call, SHA-256, put, append -- all on the GPU.  `data` is host bytes
+        (uploaded once) or a CUDA uint8 tensor (no host copy).  Returns the
+        number of spans appended."""
+        import torch
+        if handle.chunker is None:  # the library refuses too; this keeps the upload away
+            st = self.stat(handle)  # CDC_ENOTFOUND first, as write_to_file checks file_exists first
+            del st
+            raise CdcError(_lib.CDC_EPERM, "file handle is read-only")
+        if isinstance(data, torch.Tensor):
+            t = data.contiguous().view(torch.uint8).reshape(-1)
+            if not t.is_cuda:
+                t = t.to(f"cuda:{self.device}")
+        else:
+            _, _, arr = _as_buffer(data)
+            t = torch.from_numpy(arr.copy()).to(f"cuda:{self.device}")
+        if stream is None:
+            torch.cuda.synchronize(t.device)  # the call runs on the store's stream, not torch's
+        return check(lib().cdc_file_write_device(handle._fh, handle.chunker._h, _ptr(t.data_ptr()), t.numel(),
+                                                 _ptr(stream)))
+
+    def append_device(self, handle, d_data, data_len, d_chunks, d_digests, n, stream=None):
+        """cdc_file_append_device: spans chunked and hashed by the caller (device pointers)."""
+        return check(lib().cdc_file_append_device(handle._fh, _ptr(d_data), data_len, _ptr(d_chunks),
+                                                  _ptr(d_digests), n, _ptr(stream)))
+
+    # -- reads ----------------------------------------------------------------------
+    def read_complete_device(self, handle, d_out, out_cap, d_spans=None, stream=None):
+        return check(lib().cdc_file_read_complete_device(handle._fh, _ptr(d_out), out_cap, _ptr(d_spans),
+                                                         _ptr(stream)))
+
+    def read_device(self, handle, d_out, out_cap, stream=None):
+        return check(lib().cdc_file_read_device(handle._fh, _ptr(d_out), out_cap, _ptr(stream)))
+
+    def pread_device(self, handle, offset, length, d_out, stream=None):
+        return check(lib().cdc_file_pread_device(handle._fh, offset, length, _ptr(d_out), _ptr(stream)))
+
+    def pread_batch_device(self, requests, stream=None):
+        """cdc_files_pread_batch_device: requests = [(handle, offset, length,
+        device pointer)]; returns the byte count of each."""
+        n = len(requests)
+        reqs = (_lib.cdc_pread_t * max(n, 1))()
+        for i, (h, off, ln, dst) in enumerate(requests):
+            reqs[i].fh, reqs[i].offset, reqs[i].len, reqs[i].d_dst = h._fh.value, int(off), int(ln), int(dst)
+        got = (ctypes.c_uint64 * max(n, 1))()
+        check(lib().cdc_files_pread_batch_device(self._h, n, reqs, got, _ptr(stream)))
+        return [int(got[i]) for i in range(n)]
+
+    def _to_host(self, fn, cap):
+        import torch
+        dev = f"cuda:{self.device}"
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        got = fn(out.data_ptr(), cap)
+        assert got <= cap
+        return out[:got].cpu().numpy()
+
+    def read_file_complete(self, handle):
+        """FileSystem::read_file_complete (mod.rs:149-152) as a host uint8 array."""
+        size = self.stat(handle)["size"]
+        return self._to_host(lambda p, cap: self.read_complete_device(handle, p, cap), size)
+
+    def read_from_file(self, handle):
+        """FileSystem::read_from_file (mod.rs:157-160): at most one segment of
+        whole spans from the handle's cursor; empty at the end of the file."""
+        st = self.stat(handle)
+        return self._to_host(lambda p, cap: self.read_device(handle, p, cap), min(self.seg_size, st["size"]))
+
+    def pread(self, handle, offset, length):
+        """The bytes [offset, min(offset + length, size)) of the file."""
+        size = self.stat(handle)["size"]
+        cap = max(0, min(int(length), size - int(offset)))
+        return self._to_host(lambda p, _cap: self.pread_device(handle, offset, length if cap else 0, p), cap)
+
+    def hashes(self, handle):
+        """FileLayer::read_complete (file_layer.rs:127-133): the (n, 32) span digests."""
+        import torch
+        n = self.stat(handle)["spans"]
+        out = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=f"cuda:{self.device}")
+        torch.cuda.synchronize(out.device)
+        assert check(lib().cdc_file_hashes_device(handle._fh, _ptr(out.data_ptr()), n)) == n
+        return out[:n].cpu().numpy()
+
+    def chunk_count_distribution(self, handle):
+        """FileSystem::chunk_count_distribution (mod.rs:166-168): digest bytes ->
+        (count, length), in order of first occurrence; the file's last span is
+        left out, as file_layer.rs:193-197 does."""
+        import torch
+        dev = f"cuda:{self.device}"
+        cap = max(self.stat(handle)["spans"], 1)
+        dig = torch.empty((cap, 32), dtype=torch.uint8, device=dev)
+        cnt = torch.empty(cap, dtype=torch.int32, device=dev)
+        ln = torch.empty(cap, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        k = check(lib().cdc_file_distribution_device(handle._fh, _ptr(dig.data_ptr()), _ptr(cnt.data_ptr()),
+                                                     _ptr(ln.data_ptr()), cap, None))
+        dig, cnt, ln = dig[:k].cpu().numpy(), cnt[:k].cpu().numpy(), ln[:k].cpu().numpy()
+        return {dig[i].tobytes(): (int(cnt[i]), int(ln[i])) for i in range(k)}
+
+    def write_file_to_disk(self, name, path):
+        """FileSystem::write_file_to_disk (mod.rs:181-200): loops read_from_file;
+        fails if the path exists."""
+        handle = self.open_file_readonly(name)
+        with open(path, "xb") as f:
+            while True:
+                data = self.read_from_file(handle)
+                if data.size == 0:
+                    break
+                f.write(data.tobytes())
+        handle._close()
+
+    # -- storage statistics (storage.rs:193-231) ---------------------------------------
+    def cdc_dedup_ratio(self):
+        return self.store.stats()["cdc_dedup_ratio"]
+
+    def full_cdc_dedup_ratio(self):
+        """size_written / (unique bytes + 32 bytes of key per unique digest)."""
+        s = self.store.stats()
+        denom = s["unique_bytes"] + 32 * s["unique_chunks"]
+        return s["bytes_written"] / denom if denom else float("nan")
+
+    def average_chunk_size(self):
+        return self.store.stats()["average_chunk_size"]
+
+    def clear_database(self):
+        """FileSystem::clear_database (mod.rs:275-278): no files, an empty store,
+        every open handle invalid."""
+        check(lib().cdc_files_clear(self._h))
+
+    def scrub(self):
+        """A CDC file system has no scrubber: ErrorKind::InvalidInput (storage.rs:180-190)."""
+        raise CdcError(_lib.CDC_EINVAL, "scrub: this file system was created without a scrubber")
 
 
 def version():

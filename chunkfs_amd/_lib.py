@@ -16,6 +16,8 @@ CDC_ENOMEM = -2
 CDC_EDEVICE = -3
 CDC_ENOTSUP = -4
 CDC_ENOTFOUND = -5
+CDC_EEXIST = -6
+CDC_EPERM = -7
 
 ALGO = {"fast": 0, "fixed": 1, "rabin": 2, "super": 3, "ultra": 4, "leap": 5, "seq": 6}
 
@@ -31,6 +33,10 @@ EXPORTS = [
     "cdc_index_stats",
     "cdc_store_create", "cdc_store_destroy", "cdc_store_clear", "cdc_store_stats", "cdc_store_put_device",
     "cdc_store_put_batch_device", "cdc_store_get_device", "cdc_store_contains_device",
+    "cdc_files_create", "cdc_files_destroy", "cdc_files_clear", "cdc_files_exists", "cdc_files_list",
+    "cdc_files_create_file", "cdc_files_open", "cdc_file_close", "cdc_file_stat", "cdc_file_write_device",
+    "cdc_file_append_device", "cdc_file_read_complete_device", "cdc_file_read_device", "cdc_file_pread_device",
+    "cdc_files_pread_batch_device", "cdc_file_hashes_device", "cdc_file_distribution_device",
     "cdc_fill_splitmix64_device", "cdc_version", "cdc_abi_version",
 ]
 # include/chunkfs_amd_debug.h (diagnostics, not part of the drop-in boundary)
@@ -57,6 +63,16 @@ class cdc_index_stats_t(ctypes.Structure):
 class cdc_store_stats_t(ctypes.Structure):
     _fields_ = [("index", cdc_index_stats_t), ("arena_capacity", ctypes.c_uint64),
                 ("arena_used", ctypes.c_uint64)]
+
+
+class cdc_file_stat_t(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint64), ("spans", ctypes.c_uint64), ("cursor", ctypes.c_uint64),
+                ("chunk_seconds", ctypes.c_double), ("hash_seconds", ctypes.c_double)]
+
+
+class cdc_pread_t(ctypes.Structure):
+    _fields_ = [("fh", ctypes.c_void_p), ("offset", ctypes.c_uint64), ("len", ctypes.c_uint64),
+                ("d_dst", ctypes.c_void_p)]
 
 
 class cdc_timing_t(ctypes.Structure):
@@ -182,6 +198,40 @@ def lib():
     L.cdc_store_get_device.restype = ctypes.c_int64
     L.cdc_store_contains_device.argtypes = [P, P, sz, P, P]
     L.cdc_store_contains_device.restype = ctypes.c_int64
+    L.cdc_files_create.argtypes = [P, sz, ctypes.POINTER(P)]
+    L.cdc_files_create.restype = ctypes.c_int
+    L.cdc_files_destroy.argtypes = [P]
+    L.cdc_files_destroy.restype = None
+    L.cdc_files_clear.argtypes = [P]
+    L.cdc_files_clear.restype = ctypes.c_int
+    L.cdc_files_exists.argtypes = [P, ctypes.c_char_p]
+    L.cdc_files_exists.restype = ctypes.c_int
+    L.cdc_files_list.argtypes = [P, ctypes.c_char_p, sz]
+    L.cdc_files_list.restype = ctypes.c_int64
+    L.cdc_files_create_file.argtypes = [P, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(P)]
+    L.cdc_files_create_file.restype = ctypes.c_int
+    L.cdc_files_open.argtypes = [P, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(P)]
+    L.cdc_files_open.restype = ctypes.c_int
+    L.cdc_file_close.argtypes = [P]
+    L.cdc_file_close.restype = None
+    L.cdc_file_stat.argtypes = [P, ctypes.POINTER(cdc_file_stat_t)]
+    L.cdc_file_stat.restype = ctypes.c_int
+    L.cdc_file_write_device.argtypes = [P, P, P, sz, P]
+    L.cdc_file_write_device.restype = ctypes.c_int64
+    L.cdc_file_append_device.argtypes = [P, P, sz, P, P, sz, P]
+    L.cdc_file_append_device.restype = ctypes.c_int64
+    L.cdc_file_read_complete_device.argtypes = [P, P, sz, P, P]
+    L.cdc_file_read_complete_device.restype = ctypes.c_int64
+    L.cdc_file_read_device.argtypes = [P, P, sz, P]
+    L.cdc_file_read_device.restype = ctypes.c_int64
+    L.cdc_file_pread_device.argtypes = [P, ctypes.c_uint64, sz, P, P]
+    L.cdc_file_pread_device.restype = ctypes.c_int64
+    L.cdc_files_pread_batch_device.argtypes = [P, sz, ctypes.POINTER(cdc_pread_t), u64p, P]
+    L.cdc_files_pread_batch_device.restype = ctypes.c_int
+    L.cdc_file_hashes_device.argtypes = [P, P, sz]
+    L.cdc_file_hashes_device.restype = ctypes.c_int64
+    L.cdc_file_distribution_device.argtypes = [P, P, P, P, sz, P]
+    L.cdc_file_distribution_device.restype = ctypes.c_int64
     L.cdc_fill_splitmix64_device.argtypes = [P, sz, ctypes.c_uint64, P]
     L.cdc_fill_splitmix64_device.restype = ctypes.c_int
     L.cdc_debug_pipeline.argtypes = [P]

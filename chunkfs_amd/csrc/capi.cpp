@@ -230,7 +230,7 @@ int64_t cdc_debug_copy(cdc_handle_t *h, int what, void *out, size_t max_bytes) {
     return h->engine->debug_copy(what, out, max_bytes);
 }
 
-const char *cdc_version(void) { return "chunkfs_amd 0.7 gfx950 abi 5"; }
+const char *cdc_version(void) { return "chunkfs_amd 0.8 gfx950 abi 6"; }
 
 uint32_t cdc_abi_version(void) { return CHUNKFS_AMD_ABI_VERSION; }
 

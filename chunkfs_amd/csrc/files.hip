@@ -1,0 +1,291 @@
+// files.hip -- device file layer: per-file span tables over the chunk store.
+//
+// Mirrors the reference's FileLayer (src/system/file_layer.rs): a file is the
+// ordered span list {hash, offset, len} (file_layer.rs:9-23); write appends
+// spans (file_layer.rs:136-148), read_complete returns them all
+// (file_layer.rs:127-133), read takes whole spans from the handle's cursor
+// while their total stays within one segment (file_layer.rs:152-175), and
+// chunk_count_distribution counts the spans of each hash over all but the last
+// span (file_layer.rs:188-206).  pread -- a byte range -- is this layer's own.
+//
+// Layout: one span table per file, structure of arrays in HBM: the n + 1 byte
+// offsets (off[i + 1] - off[i] is span i's length; every search runs over
+// them), the 32-byte digests, and per span the table slot and arena offset the
+// store resolved when the span was written.  A put never moves stored bytes
+// and the store has no removal, so a read goes from span to bytes with no
+// digest lookup.
+//
+// Every read form is the same four steps with no host wait between them: one
+// thread per request resolves its span range by binary search in the offsets;
+// a scan over the span counts gives each request its first piece; one thread
+// per piece finds its request by binary search and writes the trimmed {src,
+// dst, len} and its tile count; the tile scan and the store's copy kernel
+// (store.hip) follow, the tile total read on the device.
+#include "files.hpp"
+
+namespace cdc {
+namespace {
+
+constexpr int kFlThreads = 256;
+constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
+
+inline unsigned grid_of(uint64_t n) { return (unsigned)((n + kFlThreads - 1) / kFlThreads); }
+
+// First i in [0, n) with off[i] >= x (n when there is none): the reference's
+// skip_while(span.offset < handle.offset).
+__device__ __forceinline__ uint64_t first_at_or_after(const uint64_t *__restrict__ off, uint64_t n, uint64_t x) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (off[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// Largest k in [lo, hi] with off[k] <= x; off[lo] <= x must hold.  Equal
+// offsets (length-0 spans) resolve to the last of them.
+__device__ __forceinline__ uint64_t last_at_or_before(const uint64_t *__restrict__ off, uint64_t lo, uint64_t hi,
+                                                      uint64_t x) {
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= x) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// ---- append --------------------------------------------------------------------
+// stat[0] = min over the spans of length - 1 (a length-0 span wraps to the
+// maximum and leaves it alone), stat[1] += length-0 spans: from these the host
+// bounds how many spans a byte range can touch.  One atomic per wave each.
+__global__ __launch_bounds__(kFlThreads) void span_len_kernel(const uint32_t *__restrict__ slot_of,
+                                                              const uint64_t *__restrict__ tbl_length, uint64_t n,
+                                                              uint64_t *val, unsigned long long *stat) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t least = ~0ull, zeros = 0;
+    if (i < n) {
+        const uint32_t s = slot_of[i];
+        const uint64_t len = s == kNoSlot ? 0 : tbl_length[s];  // the stored chunk's length: what a read may copy
+        val[i] = len;
+        least = len - 1;
+        zeros = len == 0;
+    }
+#pragma unroll
+    for (int k = 1; k < 64; k <<= 1) {
+        const uint64_t o = __shfl_xor(least, k);
+        least = o < least ? o : least;
+        zeros += __shfl_xor(zeros, k);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (least != ~0ull) atomicMin(&stat[0], (unsigned long long)least);
+        if (zeros) atomicAdd(&stat[1], (unsigned long long)zeros);
+    }
+}
+
+// val = exclusive scan of the span lengths, *total their sum.  Thread n writes
+// the new end offset.
+__global__ __launch_bounds__(kFlThreads) void append_kernel(SpanTable t, uint64_t n0, uint64_t size0,
+                                                            const uint32_t *__restrict__ slot_of,
+                                                            const uint64_t *__restrict__ tbl_loc,
+                                                            const uint8_t *__restrict__ digests, uint64_t n,
+                                                            const uint64_t *__restrict__ val,
+                                                            const uint64_t *__restrict__ total) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    if (i == n) {
+        t.off[n0 + n] = size0 + *total;
+        return;
+    }
+    const uint32_t s = slot_of[i];
+    t.off[n0 + i] = size0 + val[i];
+    t.slot[n0 + i] = s;
+    t.loc[n0 + i] = s == kNoSlot ? 0 : tbl_loc[s];
+    const uint4 *src = reinterpret_cast<const uint4 *>(digests + 32 * i);
+    uint4 *dst = reinterpret_cast<uint4 *>(t.digest + 32 * (n0 + i));
+    dst[0] = src[0];
+    dst[1] = src[1];
+}
+
+// ---- the range planner ---------------------------------------------------------
+// single (nullable; a call of one request): the scan over one count is the
+// count itself, so it goes straight to *single and the request's first piece is 0.
+__global__ __launch_bounds__(kFlThreads) void resolve_kernel(const ReadReq *__restrict__ req, uint64_t nreq,
+                                                             ReadPlan *plan, uint64_t *cnt, uint64_t *single,
+                                                             ReadResult *h_res) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nreq) return;
+    const ReadReq q = req[r];
+    const uint64_t n = q.n;
+    uint64_t lo = 0, hi = 0, first = 0, count = 0;
+    if (n) {
+        const uint64_t size = q.off[n];
+        if (q.kind == kReadComplete) {
+            hi = size;
+            count = n;
+        } else if (q.kind == kReadSegment) {
+            const uint64_t i0 = first_at_or_after(q.off, n, q.a);
+            if (i0 < n) {
+                lo = q.off[i0];
+                const uint64_t limit = lo + q.b < lo ? ~0ull : lo + q.b;
+                // take_while(running total <= segment): the largest k with off[k] - off[i0] <= seg.
+                const uint64_t k = last_at_or_before(q.off, i0, n, limit);
+                hi = q.off[k];
+                first = i0;
+                count = k - i0;
+            }
+        } else {
+            lo = q.a < size ? q.a : size;
+            hi = q.b > size - lo ? size : lo + q.b;
+            if (hi > lo) {
+                // lo < size = off[n]: the span that holds byte lo is the last one starting at or before it.
+                first = last_at_or_before(q.off, 0, n, lo);
+                count = last_at_or_before(q.off, first, n, hi - 1) - first + 1;
+            }
+        }
+    }
+    const uint64_t bytes = hi - lo;
+    if (bytes > q.cap) count = 0;  // too small a destination: the request copies nothing
+    plan[r] = ReadPlan{lo, hi, first};
+    if (single) {
+        cnt[r] = 0;
+        *single = count;
+    } else {
+        cnt[r] = count;
+    }
+    h_res[r] = ReadResult{bytes, first, count};
+}
+
+// pstart = exclusive scan of the span counts, *total_pieces their sum.  Threads
+// past the total write empty pieces, so the tile scan runs over max_pieces.
+__global__ __launch_bounds__(kFlThreads) void pieces_kernel(const ReadReq *__restrict__ req, uint64_t nreq,
+                                                            const ReadPlan *__restrict__ plan,
+                                                            const uint64_t *__restrict__ pstart,
+                                                            const uint64_t *__restrict__ total_pieces,
+                                                            uint64_t arena, StorePiece *pieces, uint64_t *tiles,
+                                                            uint64_t max_pieces) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= max_pieces) return;
+    StorePiece pc{0, 0, 0};
+    uint64_t t = 0;
+    if (p < *total_pieces) {
+        uint64_t a = 0, b = nreq;  // last request r with pstart[r] <= p (requests of no pieces share a start)
+        while (b - a > 1) {
+            const uint64_t mid = (a + b) >> 1;
+            if (pstart[mid] <= p) a = mid;
+            else b = mid;
+        }
+        const ReadReq q = req[a];
+        const ReadPlan pl = plan[a];
+        const uint64_t k = p - pstart[a], i = pl.first + k;
+        const uint64_t s0 = q.off[i], s1 = q.off[i + 1];
+        // Only the first and last piece of a range are trimmed.
+        const uint64_t from = s0 > pl.lo ? s0 : pl.lo, to = s1 < pl.hi ? s1 : pl.hi;
+        const uint64_t len = to > from ? to - from : 0;
+        pc.src = arena + q.loc[i] + (from - s0);
+        pc.dst = q.dst + (from - pl.lo);
+        pc.len = len;
+        t = len ? ((pc.dst & (kStoreAlign - 1)) + len + (kStoreTile - 1)) / kStoreTile : 0;
+        if (q.spans) reinterpret_cast<cdc_chunk_pod *>(q.spans)[k] = cdc_chunk_pod{from - pl.lo, len};
+    }
+    pieces[p] = pc;
+    tiles[p] = t;
+}
+
+// ---- distribution ----------------------------------------------------------------
+__global__ __launch_bounds__(kFlThreads) void dist_init_kernel(const uint32_t *__restrict__ slot, uint64_t m,
+                                                               uint32_t *cnt, uint64_t *firstpos) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t s = slot[i];
+    if (s == kNoSlot) return;
+    cnt[s] = 0;  // every writer of a slot writes the same values
+    firstpos[s] = ~0ull;
+}
+
+__global__ __launch_bounds__(kFlThreads) void dist_count_kernel(const uint32_t *__restrict__ slot, uint64_t m,
+                                                                uint32_t *cnt, uint64_t *firstpos) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t s = slot[i];
+    if (s == kNoSlot) return;
+    atomicAdd(&cnt[s], 1u);
+    atomicMin((unsigned long long *)&firstpos[s], (unsigned long long)i);
+}
+
+__global__ __launch_bounds__(kFlThreads) void dist_flag_kernel(const uint32_t *__restrict__ slot, uint64_t m,
+                                                               const uint64_t *__restrict__ firstpos, uint64_t *val) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t s = slot[i];
+    val[i] = s != kNoSlot && firstpos[s] == i ? 1 : 0;
+}
+
+__global__ __launch_bounds__(kFlThreads) void dist_compact_kernel(SpanTable t, uint64_t m,
+                                                                  const uint32_t *__restrict__ cnt,
+                                                                  const uint64_t *__restrict__ firstpos,
+                                                                  const uint64_t *__restrict__ val,
+                                                                  const uint64_t *__restrict__ total, uint64_t cap,
+                                                                  uint8_t *digests, uint32_t *counts,
+                                                                  uint64_t *lengths) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m || *total > cap) return;
+    const uint32_t s = t.slot[i];
+    if (s == kNoSlot || firstpos[s] != i) return;
+    const uint64_t j = val[i];
+    const uint4 *src = reinterpret_cast<const uint4 *>(t.digest + 32 * i);
+    uint4 *dst = reinterpret_cast<uint4 *>(digests + 32 * j);
+    dst[0] = src[0];
+    dst[1] = src[1];
+    counts[j] = cnt[s];
+    lengths[j] = t.off[i + 1] - t.off[i];
+}
+
+}  // namespace
+
+hipError_t launch_files_append(const SpanTable &t, uint64_t n0, uint64_t size0, const uint32_t *slot_of,
+                               const uint64_t *tbl_length, const uint64_t *tbl_loc, const uint8_t *d_digests,
+                               uint64_t n, uint64_t *val, uint64_t *block_sums, unsigned long long *d_stat,
+                               unsigned long long *h_total, hipStream_t s) {
+    if (!n) return hipSuccess;
+    span_len_kernel<<<grid_of(n), kFlThreads, 0, s>>>(slot_of, tbl_length, n, val, d_stat);
+    hipError_t e = launch_store_scan(val, n, block_sums, h_total, s);
+    if (e != hipSuccess) return e;
+    append_kernel<<<grid_of(n + 1), kFlThreads, 0, s>>>(t, n0, size0, slot_of, tbl_loc, d_digests, n, val,
+                                                        block_sums + store_scan_blocks(n));
+    return hipGetLastError();
+}
+
+hipError_t launch_files_read(const ReadReq *d_req, uint64_t nreq, uint64_t arena, ReadPlan *plan, uint64_t *cnt,
+                             uint64_t *rblock, StorePiece *pieces, uint64_t *tstart, uint64_t *block_sums,
+                             uint64_t max_pieces, uint64_t max_tiles, ReadResult *h_res, hipStream_t s) {
+    if (!nreq) return hipSuccess;
+    uint64_t *total_pieces = rblock + store_scan_blocks(nreq);
+    resolve_kernel<<<grid_of(nreq), kFlThreads, 0, s>>>(d_req, nreq, plan, cnt, nreq == 1 ? total_pieces : nullptr,
+                                                        h_res);
+    if (!max_pieces) return hipGetLastError();
+    hipError_t e = nreq == 1 ? hipSuccess : launch_store_scan(cnt, nreq, rblock, nullptr, s);
+    if (e != hipSuccess) return e;
+    pieces_kernel<<<grid_of(max_pieces), kFlThreads, 0, s>>>(d_req, nreq, plan, cnt, total_pieces, arena, pieces,
+                                                             tstart, max_pieces);
+    e = launch_store_scan(tstart, max_pieces, block_sums, nullptr, s);
+    if (e != hipSuccess) return e;
+    return launch_store_copy(pieces, tstart, max_pieces, max_tiles, block_sums + store_scan_blocks(max_pieces), s);
+}
+
+hipError_t launch_files_distribution(const SpanTable &t, uint64_t m, uint32_t *cnt, uint64_t *firstpos,
+                                     uint64_t *val, uint64_t *block_sums, uint8_t *d_digests, uint32_t *d_counts,
+                                     uint64_t *d_lengths, uint64_t cap, unsigned long long *h_distinct,
+                                     hipStream_t s) {
+    if (!m) return hipSuccess;
+    dist_init_kernel<<<grid_of(m), kFlThreads, 0, s>>>(t.slot, m, cnt, firstpos);
+    dist_count_kernel<<<grid_of(m), kFlThreads, 0, s>>>(t.slot, m, cnt, firstpos);
+    dist_flag_kernel<<<grid_of(m), kFlThreads, 0, s>>>(t.slot, m, firstpos, val);
+    hipError_t e = launch_store_scan(val, m, block_sums, h_distinct, s);
+    if (e != hipSuccess) return e;
+    dist_compact_kernel<<<grid_of(m), kFlThreads, 0, s>>>(t, m, cnt, firstpos, val, block_sums + store_scan_blocks(m),
+                                                          cap, d_digests, d_counts, d_lengths);
+    return hipGetLastError();
+}
+
+}  // namespace cdc

@@ -1,0 +1,83 @@
+// files.hpp -- device file layer kernels (files.hip) and their host object
+// (files_host.cpp): per-file span tables in HBM over the chunk store.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "store.hpp"
+
+namespace cdc {
+
+// One file's span table, structure of arrays in HBM.  Span i covers the bytes
+// [off[i], off[i + 1]) of the file; off[0] = 0 and off[n] = the file's size.
+struct SpanTable {
+    uint64_t *off;     // [cap + 1]
+    uint8_t *digest;   // [cap * 32]
+    uint64_t *loc;     // [cap] arena offset of the span's bytes (the store's loc[slot])
+    uint32_t *slot;    // [cap] the span's table slot (the distribution counts per slot)
+};
+
+enum ReadKind : uint32_t {
+    kReadComplete = 0,  // every span: read_file_complete
+    kReadSegment = 1,   // whole spans from the cursor while their total stays <= seg: read_from_file
+    kReadRange = 2,     // the bytes [a, a + b) clipped to the file: pread
+};
+
+// One read request, built on the host.
+struct ReadReq {
+    const uint64_t *off;
+    const uint64_t *loc;
+    uint64_t n;      // spans of the file
+    uint64_t a;      // segment: the cursor; range: the offset
+    uint64_t b;      // segment: the segment size; range: the length
+    uint64_t dst;    // device address of the request's first byte
+    uint64_t cap;    // bytes the destination holds
+    uint64_t spans;  // complete only: device address of cdc_chunk_t[n], or 0
+    uint32_t kind;
+    uint32_t pad;
+};
+
+// What the planner leaves per request (device scratch; `bytes`, `first` and
+// `count` also go to the host result block).
+struct ReadPlan {
+    uint64_t lo, hi;  // byte range of the file
+    uint64_t first;   // first span
+};
+struct ReadResult {
+    uint64_t bytes;  // what the request yields (also when it exceeds cap: nothing is copied then)
+    uint64_t first;
+    uint64_t count;  // spans the request touches
+};
+
+// Append n spans to a table holding n0 spans and size0 bytes, after a put of the
+// same n chunks: slot_of is the put's slot list.  val: n u64 scratch, block_sums:
+// store_scan_blocks(n) + 1.  *h_total (pinned host) = bytes appended.  d_stat
+// (device, preset to {~0, 0}): [0] = min(length - 1) over the spans of length >
+// 0, [1] += spans of length 0.
+hipError_t launch_files_append(const SpanTable &t, uint64_t n0, uint64_t size0, const uint32_t *slot_of,
+                               const uint64_t *tbl_length, const uint64_t *tbl_loc, const uint8_t *d_digests,
+                               uint64_t n, uint64_t *val, uint64_t *block_sums, unsigned long long *d_stat,
+                               unsigned long long *h_total, hipStream_t s);
+
+// The range planner and the copy: nreq requests -> span ranges -> pieces ->
+// tiles -> copy_kernel, with no host wait in between.  max_pieces / max_tiles
+// are host-side bounds (they size grids and scratch; a bound below the true
+// count would drop pieces); the exact counts stay on the device.  plan: nreq;
+// cnt: nreq u64; rblock: store_scan_blocks(nreq) + 1; pieces / tstart:
+// max_pieces; block_sums: store_scan_blocks(max_pieces) + 1; h_res: nreq results
+// in pinned host memory.
+hipError_t launch_files_read(const ReadReq *d_req, uint64_t nreq, uint64_t arena, ReadPlan *plan, uint64_t *cnt,
+                             uint64_t *rblock, StorePiece *pieces, uint64_t *tstart, uint64_t *block_sums,
+                             uint64_t max_pieces, uint64_t max_tiles, ReadResult *h_res, hipStream_t s);
+
+// chunk_count_distribution over spans [0, m), m = n - 1: per distinct slot, in
+// order of first occurrence, {digest, count, off[i + 1] - off[i] of the first
+// occurrence}.  cnt / firstpos: table-sized scratch (only the slots the file
+// uses are initialised); val: m; block_sums: store_scan_blocks(m) + 1.  Nothing
+// is written when the distinct count exceeds cap; *h_distinct (pinned) gets it.
+hipError_t launch_files_distribution(const SpanTable &t, uint64_t m, uint32_t *cnt, uint64_t *firstpos,
+                                     uint64_t *val, uint64_t *block_sums, uint8_t *d_digests, uint32_t *d_counts,
+                                     uint64_t *d_lengths, uint64_t cap, unsigned long long *h_distinct,
+                                     hipStream_t s);
+
+}  // namespace cdc

@@ -1,0 +1,554 @@
+// files_host.cpp -- C ABI of the device file layer (include/chunkfs_amd.h, "File
+// layer"): the reference's FileLayer (src/system/file_layer.rs) and the
+// FileSystem calls built on it (src/system/mod.rs:58-160, 271-278).  Names and
+// handles live here on the host; each file's span table lives in HBM and all
+// per-span work runs in files.hip.
+#include <chrono>
+#include <cstring>
+#include <map>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "../../include/chunkfs_amd.h"
+#include "engine.hpp"
+#include "files.hpp"
+#include "store.hpp"
+#include "store_internal.hpp"
+
+namespace {
+
+struct FileRec {
+    uint64_t n = 0;      // spans
+    uint64_t size = 0;   // bytes = off[n]
+    uint64_t cap = 0;    // spans the table holds
+    uint64_t epoch = 0;  // the store's epoch when the spans were resolved
+    uint64_t min_len = ~0ull;  // shortest span of length > 0 (~0: none yet)
+    uint64_t zeros = 0;        // spans of length 0
+    cdc::SpanTable t{};
+};
+
+}  // namespace
+
+struct cdc_files {
+    cdc_store *store = nullptr;
+    int device = 0;  // the store's, kept so that teardown needs nothing of the store
+    uint64_t seg = 0;
+    std::map<std::string, FileRec *> files;  // ordered: cdc_files_list is deterministic
+    std::set<cdc_fh *> handles;
+    // cdc_file_write_device: chunk list and digests of one call
+    uint64_t w_cap = 0;
+    cdc_chunk_t *w_chunks = nullptr;
+    uint8_t *w_dig = nullptr;
+    // append / distribution: per-span scratch
+    uint64_t a_cap = 0;
+    uint64_t *a_val = nullptr, *a_block = nullptr;
+    uint64_t d_slots = 0;
+    uint32_t *d_cnt = nullptr;
+    uint64_t *d_first = nullptr;
+    // reads: per-request and per-piece scratch
+    uint64_t r_cap = 0;
+    cdc::ReadReq *h_req = nullptr, *d_req = nullptr;  // h_*: pinned host memory
+    cdc::ReadPlan *d_plan = nullptr;
+    uint64_t *d_rcnt = nullptr, *d_rblock = nullptr;
+    cdc::ReadResult *h_res = nullptr;
+    uint64_t p_cap = 0;
+    cdc::StorePiece *d_pieces = nullptr;
+    uint64_t *d_tstart = nullptr, *d_pblock = nullptr;
+    unsigned long long *h_tot = nullptr;  // pinned: [0] appended bytes, [1] distinct digests, [2..3] d_stat's copy
+    unsigned long long *d_stat = nullptr;  // [2] append: min(length - 1), spans of length 0
+};
+
+struct cdc_fh {
+    cdc_files *fs = nullptr;  // NULL once the layer is destroyed
+    std::string name;         // the reference's handle holds the name, not the file (file_layer.rs:32-41)
+    bool readonly = false;
+    uint64_t cursor = 0;      // FileHandle::offset as read_from_file uses it
+    double chunk_s = 0, hash_s = 0;
+};
+
+namespace {
+
+#define FL_TRY(expr)                                                         \
+    do {                                                                     \
+        hipError_t e_ = (expr);                                              \
+        if (e_ != hipSuccess) {                                              \
+            cdc::set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); \
+            return e_ == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE;     \
+        }                                                                    \
+    } while (0)
+
+int fail(int code, const std::string &msg) {
+    cdc::set_error(msg);
+    return code;
+}
+
+void free_table(FileRec *f) {
+    (void)hipFree(f->t.off);
+    (void)hipFree(f->t.digest);
+    (void)hipFree(f->t.loc);
+    (void)hipFree(f->t.slot);
+    f->t = cdc::SpanTable{};
+    f->cap = 0;
+}
+
+void drop_files(cdc_files *fs) {
+    for (auto &kv : fs->files) {
+        free_table(kv.second);
+        delete kv.second;
+    }
+    fs->files.clear();
+}
+
+// Capacity doubles: allocate, copy on the call's stream, free the old arrays.
+int reserve(FileRec *f, uint64_t need, hipStream_t s) {
+    if (need <= f->cap) return CDC_OK;
+    uint64_t cap = f->cap ? f->cap : 64;
+    while (cap < need) cap *= 2;
+    cdc::SpanTable t{};
+    hipError_t e = hipMalloc(&t.off, (cap + 1) * 8);
+    if (e == hipSuccess) e = hipMalloc(&t.digest, cap * 32);
+    if (e == hipSuccess) e = hipMalloc(&t.loc, cap * 8);
+    if (e == hipSuccess) e = hipMalloc(&t.slot, cap * 4);
+    if (e == hipSuccess && f->n) {
+        e = hipMemcpyAsync(t.off, f->t.off, (f->n + 1) * 8, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(t.digest, f->t.digest, f->n * 32, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(t.loc, f->t.loc, f->n * 8, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(t.slot, f->t.slot, f->n * 4, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    if (e != hipSuccess) {
+        (void)hipFree(t.off);
+        (void)hipFree(t.digest);
+        (void)hipFree(t.loc);
+        (void)hipFree(t.slot);
+        cdc::set_error(std::string("file layer: span table growth: ") + hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE;
+    }
+    free_table(f);
+    f->t = t;
+    f->cap = cap;
+    return CDC_OK;
+}
+
+int grow_span_scratch(cdc_files *fs, uint64_t n) {
+    if (fs->a_cap >= n) return CDC_OK;
+    (void)hipFree(fs->a_val);
+    (void)hipFree(fs->a_block);
+    fs->a_val = fs->a_block = nullptr;
+    fs->a_cap = 0;
+    const uint64_t cap = n + n / 8 + 64;
+    FL_TRY(hipMalloc(&fs->a_val, cap * 8));
+    FL_TRY(hipMalloc(&fs->a_block, (cdc::store_scan_blocks(cap) + 1) * 8));
+    fs->a_cap = cap;
+    return CDC_OK;
+}
+
+int grow_requests(cdc_files *fs, uint64_t n) {
+    if (fs->r_cap >= n) return CDC_OK;
+    (void)hipHostFree(fs->h_req);
+    (void)hipHostFree(fs->h_res);
+    (void)hipFree(fs->d_req);
+    (void)hipFree(fs->d_plan);
+    (void)hipFree(fs->d_rcnt);
+    (void)hipFree(fs->d_rblock);
+    fs->h_req = fs->d_req = nullptr;
+    fs->h_res = nullptr;
+    fs->d_plan = nullptr;
+    fs->d_rcnt = fs->d_rblock = nullptr;
+    fs->r_cap = 0;
+    const uint64_t cap = n + n / 8 + 16;
+    FL_TRY(hipHostMalloc(&fs->h_req, cap * sizeof(cdc::ReadReq)));
+    FL_TRY(hipHostMalloc(&fs->h_res, cap * sizeof(cdc::ReadResult)));
+    FL_TRY(hipMalloc(&fs->d_req, cap * sizeof(cdc::ReadReq)));
+    FL_TRY(hipMalloc(&fs->d_plan, cap * sizeof(cdc::ReadPlan)));
+    FL_TRY(hipMalloc(&fs->d_rcnt, cap * 8));
+    FL_TRY(hipMalloc(&fs->d_rblock, (cdc::store_scan_blocks(cap) + 1) * 8));
+    fs->r_cap = cap;
+    return CDC_OK;
+}
+
+int grow_pieces(cdc_files *fs, uint64_t n) {
+    if (fs->p_cap >= n) return CDC_OK;
+    (void)hipFree(fs->d_pieces);
+    (void)hipFree(fs->d_tstart);
+    (void)hipFree(fs->d_pblock);
+    fs->d_pieces = nullptr;
+    fs->d_tstart = fs->d_pblock = nullptr;
+    fs->p_cap = 0;
+    const uint64_t cap = n + n / 8 + 64;
+    FL_TRY(hipMalloc(&fs->d_pieces, cap * sizeof(cdc::StorePiece)));
+    FL_TRY(hipMalloc(&fs->d_tstart, cap * 8));
+    FL_TRY(hipMalloc(&fs->d_pblock, (cdc::store_scan_blocks(cap) + 1) * 8));
+    fs->p_cap = cap;
+    return CDC_OK;
+}
+
+void release(cdc_files *fs) {
+    (void)hipSetDevice(fs->device);
+    drop_files(fs);
+    for (cdc_fh *h : fs->handles) h->fs = nullptr;
+    (void)hipFree(fs->w_chunks);
+    (void)hipFree(fs->w_dig);
+    (void)hipFree(fs->a_val);
+    (void)hipFree(fs->a_block);
+    (void)hipFree(fs->d_cnt);
+    (void)hipFree(fs->d_first);
+    (void)hipHostFree(fs->h_req);
+    (void)hipHostFree(fs->h_res);
+    (void)hipFree(fs->d_req);
+    (void)hipFree(fs->d_plan);
+    (void)hipFree(fs->d_rcnt);
+    (void)hipFree(fs->d_rblock);
+    (void)hipFree(fs->d_pieces);
+    (void)hipFree(fs->d_tstart);
+    (void)hipFree(fs->d_pblock);
+    (void)hipHostFree(fs->h_tot);
+    (void)hipFree(fs->d_stat);
+    delete fs;
+}
+
+// The handle's file, by name as the reference finds it (file_layer.rs:116-124).
+// for_read: the spans must have been resolved under the store's current epoch.
+int lookup(cdc_fh *fh, bool for_read, FileRec **out) {
+    if (!fh) return fail(CDC_EINVAL, "NULL file handle");
+    if (!fh->fs) return fail(CDC_EINVAL, "file handle outlived its file layer");
+    auto it = fh->fs->files.find(fh->name);
+    if (it == fh->fs->files.end()) return fail(CDC_ENOTFOUND, "file layer: no file named '" + fh->name + "'");
+    FileRec *f = it->second;
+    if (for_read && f->n && f->epoch != cdc::store_view(fh->fs->store).epoch)
+        return fail(CDC_ENOTFOUND, "file layer: the store was cleared since '" + fh->name + "' was written");
+    *out = f;
+    return CDC_OK;
+}
+
+hipStream_t stream_of(cdc_files *fs, void *hip_stream) {
+    return hip_stream ? static_cast<hipStream_t>(hip_stream) : cdc::store_view(fs->store).stream;
+}
+
+int64_t append(cdc_fh *fh, const uint8_t *d_data, uint64_t data_len, const cdc_chunk_t *d_chunks,
+               const uint8_t *d_digests, uint64_t n, void *hip_stream) {
+    FileRec *f = nullptr;
+    int rc = lookup(fh, false, &f);
+    if (rc) return rc;
+    if (fh->readonly) return fail(CDC_EPERM, "file handle is read-only");
+    cdc_files *fs = fh->fs;
+    cdc::StoreView v = cdc::store_view(fs->store);
+    if (f->n && f->epoch != v.epoch)
+        return fail(CDC_ENOTFOUND, "file layer: the store was cleared since '" + fh->name + "' was written");
+    if (n == 0) return 0;
+    FL_TRY(hipSetDevice(v.device));
+    hipStream_t s = stream_of(fs, hip_stream);
+    if ((rc = reserve(f, f->n + n, s)) != CDC_OK) return rc;
+    if ((rc = grow_span_scratch(fs, n)) != CDC_OK) return rc;
+    const int64_t put = cdc::store_put_slots(fs->store, d_data, data_len, d_chunks, d_digests, n, hip_stream);
+    if (put < 0) return put;  // refused: the file is as it was
+    v = cdc::store_view(fs->store);
+    FL_TRY(hipMemsetAsync(fs->d_stat, 0xFF, 8, s));
+    FL_TRY(hipMemsetAsync(fs->d_stat + 1, 0, 8, s));
+    FL_TRY(cdc::launch_files_append(f->t, f->n, f->size, v.slot_of, v.length, v.loc, d_digests, n, fs->a_val,
+                                    fs->a_block, fs->d_stat, fs->h_tot, s));
+    FL_TRY(hipMemcpyAsync(fs->h_tot + 2, fs->d_stat, 16, hipMemcpyDeviceToHost, s));
+    FL_TRY(hipStreamSynchronize(s));
+    f->n += n;
+    f->size += fs->h_tot[0];
+    f->epoch = v.epoch;
+    if (fs->h_tot[2] != ~0ull && fs->h_tot[2] + 1 < f->min_len) f->min_len = fs->h_tot[2] + 1;
+    f->zeros += fs->h_tot[3];
+    return (int64_t)n;
+}
+
+// Spans a range of at most `bytes` bytes can touch, whole spans but for its two
+// ends: the spans of length 0, the longer ones that fit, and the two ends.
+uint64_t spans_bound(const FileRec *f, uint64_t bytes) {
+    const uint64_t fit = f->min_len == ~0ull ? 0 : bytes / f->min_len;
+    const uint64_t bound = f->zeros + fit + 2;
+    return bound < f->n ? bound : f->n;
+}
+
+// One request of `kind` on a file; cap, the destination's size, also bounds the tiles.
+struct HostReq {
+    FileRec *f;
+    uint32_t kind;
+    uint64_t a, b;
+    uint8_t *dst;
+    uint64_t cap;
+    cdc_chunk_t *spans;
+};
+
+// Plans and copies every request in one pass; fs->h_res[i] holds the results.
+int run_reads(cdc_files *fs, const std::vector<HostReq> &reqs, void *hip_stream) {
+    const cdc::StoreView v = cdc::store_view(fs->store);
+    FL_TRY(hipSetDevice(v.device));
+    hipStream_t s = stream_of(fs, hip_stream);
+    const uint64_t nreq = reqs.size();
+    int rc = grow_requests(fs, nreq);
+    if (rc) return rc;
+    uint64_t max_pieces = 0, max_tiles = 0;
+    for (uint64_t i = 0; i < nreq; ++i) {
+        const HostReq &q = reqs[i];
+        cdc::ReadReq &d = fs->h_req[i];
+        d = cdc::ReadReq{q.f->t.off, q.f->t.loc, q.f->n, q.a, q.b, (uint64_t)(uintptr_t)q.dst, q.cap,
+                         (uint64_t)(uintptr_t)q.spans, q.kind, 0};
+        uint64_t bytes = q.f->size < q.cap ? q.f->size : q.cap;
+        if (q.kind != cdc::kReadComplete && q.b < bytes) bytes = q.b;
+        // Also without bytes: length-0 spans are pieces, and have entries in d_spans.
+        const uint64_t spans = q.kind == cdc::kReadComplete ? q.f->n : spans_bound(q.f, bytes);
+        max_pieces += spans;
+        if (bytes) max_tiles += bytes / cdc::kStoreTile + 2 * spans;  // a piece adds at most two ragged tiles
+    }
+    if ((rc = grow_pieces(fs, max_pieces)) != CDC_OK) return rc;
+    FL_TRY(hipMemcpyAsync(fs->d_req, fs->h_req, nreq * sizeof(cdc::ReadReq), hipMemcpyHostToDevice, s));
+    FL_TRY(cdc::launch_files_read(fs->d_req, nreq, (uint64_t)(uintptr_t)v.arena, fs->d_plan, fs->d_rcnt,
+                                  fs->d_rblock, fs->d_pieces, fs->d_tstart, fs->d_pblock, max_pieces, max_tiles,
+                                  fs->h_res, s));
+    FL_TRY(hipStreamSynchronize(s));
+    return CDC_OK;
+}
+
+int64_t read_one(cdc_fh *fh, uint32_t kind, uint64_t a, uint64_t b, uint8_t *d_out, uint64_t cap,
+                 cdc_chunk_t *d_spans, void *hip_stream) {
+    FileRec *f = nullptr;
+    int rc = lookup(fh, true, &f);
+    if (rc) return rc;
+    if (cap && !d_out) return fail(CDC_EINVAL, "file layer read: NULL destination");
+    if (f->n == 0) return 0;
+    std::vector<HostReq> reqs{HostReq{f, kind, a, b, d_out, cap, d_spans}};
+    if ((rc = run_reads(fh->fs, reqs, hip_stream)) != CDC_OK) return rc;
+    return (int64_t)fh->fs->h_res[0].bytes;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cdc_files_create(cdc_store_t *store, size_t seg_size, cdc_files_t **out) {
+    if (!out) return fail(CDC_EINVAL, "cdc_files_create: out is NULL");
+    *out = nullptr;
+    if (!store) return fail(CDC_EINVAL, "cdc_files_create: store is NULL");
+    cdc_files *fs = new cdc_files();
+    fs->store = store;
+    fs->seg = seg_size ? seg_size : (1u << 20);
+    fs->device = cdc::store_view(store).device;
+    hipError_t e = hipSetDevice(fs->device);
+    if (e == hipSuccess) e = hipHostMalloc(&fs->h_tot, 4 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc(&fs->d_stat, 2 * sizeof(unsigned long long));
+    if (e != hipSuccess) {
+        (void)hipHostFree(fs->h_tot);
+        delete fs;
+        return fail(e == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE,
+                    std::string("cdc_files_create: ") + hipGetErrorString(e));
+    }
+    *out = fs;
+    return CDC_OK;
+}
+
+void cdc_files_destroy(cdc_files_t *fs) {
+    if (fs) release(fs);
+}
+
+int cdc_files_clear(cdc_files_t *fs) {
+    if (!fs) return fail(CDC_EINVAL, "NULL file layer");
+    (void)hipSetDevice(cdc::store_view(fs->store).device);
+    drop_files(fs);
+    return cdc_store_clear(fs->store);
+}
+
+int cdc_files_exists(const cdc_files_t *fs, const char *name) {
+    if (!fs || !name) return fail(CDC_EINVAL, "cdc_files_exists: NULL argument");
+    return fs->files.count(name) ? 1 : 0;
+}
+
+int64_t cdc_files_list(const cdc_files_t *fs, char *buf, size_t cap) {
+    if (!fs || (cap && !buf)) return fail(CDC_EINVAL, "cdc_files_list: NULL argument");
+    uint64_t need = 0;
+    for (const auto &kv : fs->files) need += kv.first.size() + 1;
+    if (need > cap) return (int64_t)need;
+    for (const auto &kv : fs->files) {
+        std::memcpy(buf, kv.first.c_str(), kv.first.size() + 1);
+        buf += kv.first.size() + 1;
+    }
+    return (int64_t)need;
+}
+
+int cdc_files_create_file(cdc_files_t *fs, const char *name, int create_new, cdc_fh_t **out) {
+    if (!out) return fail(CDC_EINVAL, "cdc_files_create_file: out is NULL");
+    *out = nullptr;
+    if (!fs || !name) return fail(CDC_EINVAL, "cdc_files_create_file: NULL argument");
+    auto it = fs->files.find(name);
+    if (it != fs->files.end()) {
+        if (!create_new) return fail(CDC_EEXIST, std::string("file layer: '") + name + "' already exists");
+        (void)hipSetDevice(cdc::store_view(fs->store).device);
+        free_table(it->second);  // replaced by an empty file (file_layer.rs:95-96)
+        *it->second = FileRec{};
+    } else {
+        fs->files[name] = new FileRec();
+    }
+    cdc_fh *fh = new cdc_fh();
+    fh->fs = fs;
+    fh->name = name;
+    fs->handles.insert(fh);
+    *out = fh;
+    return CDC_OK;
+}
+
+int cdc_files_open(cdc_files_t *fs, const char *name, int readonly, cdc_fh_t **out) {
+    if (!out) return fail(CDC_EINVAL, "cdc_files_open: out is NULL");
+    *out = nullptr;
+    if (!fs || !name) return fail(CDC_EINVAL, "cdc_files_open: NULL argument");
+    if (!fs->files.count(name)) return fail(CDC_ENOTFOUND, std::string("file layer: no file named '") + name + "'");
+    cdc_fh *fh = new cdc_fh();
+    fh->fs = fs;
+    fh->name = name;
+    fh->readonly = readonly != 0;
+    fs->handles.insert(fh);
+    *out = fh;
+    return CDC_OK;
+}
+
+void cdc_file_close(cdc_fh_t *fh) {
+    if (!fh) return;
+    if (fh->fs) fh->fs->handles.erase(fh);
+    delete fh;
+}
+
+int cdc_file_stat(cdc_fh_t *fh, cdc_file_stat_t *out) {
+    if (!out) return fail(CDC_EINVAL, "cdc_file_stat: out is NULL");
+    FileRec *f = nullptr;
+    const int rc = lookup(fh, false, &f);
+    if (rc) return rc;
+    out->size = f->size;
+    out->spans = f->n;
+    out->cursor = fh->cursor;
+    out->chunk_seconds = fh->chunk_s;
+    out->hash_seconds = fh->hash_s;
+    return CDC_OK;
+}
+
+int64_t cdc_file_write_device(cdc_fh_t *fh, cdc_handle_t *chunker, const uint8_t *d_data, size_t len,
+                              void *hip_stream) {
+    FileRec *f = nullptr;
+    int rc = lookup(fh, false, &f);
+    if (rc) return rc;
+    if (fh->readonly) return fail(CDC_EPERM, "file handle is read-only");
+    if (!chunker) return fail(CDC_EINVAL, "cdc_file_write_device: NULL chunker");
+    if (len == 0) return 0;
+    if (!d_data) return fail(CDC_EINVAL, "cdc_file_write_device: NULL data");
+    cdc_files *fs = fh->fs;
+    FL_TRY(hipSetDevice(cdc::store_view(fs->store).device));
+    void *s = hip_stream ? hip_stream : (void *)cdc::store_view(fs->store).stream;
+    const uint64_t lens[1] = {len};
+    const uint8_t *streams[1] = {d_data};
+    const uint64_t cap = cdc_batch_max_chunks(chunker, 1, lens);
+    if (fs->w_cap < cap) {
+        (void)hipFree(fs->w_chunks);
+        (void)hipFree(fs->w_dig);
+        fs->w_chunks = nullptr;
+        fs->w_dig = nullptr;
+        fs->w_cap = 0;
+        FL_TRY(hipMalloc(&fs->w_chunks, cap * sizeof(cdc_chunk_t)));
+        FL_TRY(hipMalloc(&fs->w_dig, cap * 32));
+        fs->w_cap = cap;
+    }
+    uint64_t first[2] = {0, 0};
+    const auto t0 = std::chrono::steady_clock::now();
+    const int64_t n = cdc_chunk_batch_device(chunker, 1, streams, lens, fs->w_chunks, cap, first, s);
+    if (n < 0) return n;
+    const auto t1 = std::chrono::steady_clock::now();
+    rc = cdc_sha256_batch_device(chunker, 1, streams, first, fs->w_chunks, fs->w_dig, s);
+    if (rc) return rc;
+    const auto t2 = std::chrono::steady_clock::now();
+    const int64_t got = append(fh, d_data, len, fs->w_chunks, fs->w_dig, (uint64_t)n, s);
+    if (got < 0) return got;
+    fh->chunk_s += std::chrono::duration<double>(t1 - t0).count();
+    fh->hash_s += std::chrono::duration<double>(t2 - t1).count();
+    return got;
+}
+
+int64_t cdc_file_append_device(cdc_fh_t *fh, const uint8_t *d_data, size_t data_len, const cdc_chunk_t *d_chunks,
+                               const uint8_t *d_digests, size_t n, void *hip_stream) {
+    return append(fh, d_data, data_len, d_chunks, d_digests, n, hip_stream);
+}
+
+int64_t cdc_file_read_complete_device(cdc_fh_t *fh, uint8_t *d_out, size_t out_cap, cdc_chunk_t *d_spans,
+                                      void *hip_stream) {
+    return read_one(fh, cdc::kReadComplete, 0, 0, d_out, out_cap, d_spans, hip_stream);
+}
+
+int64_t cdc_file_read_device(cdc_fh_t *fh, uint8_t *d_out, size_t out_cap, void *hip_stream) {
+    if (!fh || !fh->fs) return fail(CDC_EINVAL, "NULL file handle");
+    const int64_t got = read_one(fh, cdc::kReadSegment, fh->cursor, fh->fs->seg, d_out, out_cap, nullptr, hip_stream);
+    if (got > 0 && (uint64_t)got <= out_cap) fh->cursor += (uint64_t)got;  // handle.offset += bytes_read
+    return got;
+}
+
+int64_t cdc_file_pread_device(cdc_fh_t *fh, uint64_t offset, size_t len, uint8_t *d_out, void *hip_stream) {
+    return read_one(fh, cdc::kReadRange, offset, len, d_out, len, nullptr, hip_stream);
+}
+
+int cdc_files_pread_batch_device(cdc_files_t *fs, size_t n, const cdc_pread_t *reqs, uint64_t *got,
+                                 void *hip_stream) {
+    if (!fs) return fail(CDC_EINVAL, "NULL file layer");
+    if (n == 0) return CDC_OK;
+    if (!reqs || !got) return fail(CDC_EINVAL, "cdc_files_pread_batch_device: NULL argument");
+    std::vector<HostReq> v;
+    v.reserve(n);
+    for (size_t i = 0; i < n; ++i) {
+        FileRec *f = nullptr;
+        const int rc = lookup(reqs[i].fh, true, &f);
+        if (rc) return rc;
+        if (reqs[i].fh->fs != fs) return fail(CDC_EINVAL, "cdc_files_pread_batch_device: a handle of another layer");
+        if (reqs[i].len && !reqs[i].d_dst) return fail(CDC_EINVAL, "cdc_files_pread_batch_device: NULL destination");
+        v.push_back(HostReq{f, cdc::kReadRange, reqs[i].offset, reqs[i].len, reqs[i].d_dst, reqs[i].len,
+                            nullptr});
+    }
+    const int rc = run_reads(fs, v, hip_stream);
+    if (rc) return rc;
+    for (size_t i = 0; i < n; ++i) got[i] = fs->h_res[i].bytes;
+    return CDC_OK;
+}
+
+int64_t cdc_file_hashes_device(cdc_fh_t *fh, uint8_t *d_digests, size_t cap) {
+    FileRec *f = nullptr;
+    const int rc = lookup(fh, false, &f);
+    if (rc) return rc;
+    if (f->n > cap || f->n == 0) return (int64_t)f->n;
+    if (!d_digests) return fail(CDC_EINVAL, "cdc_file_hashes_device: NULL destination");
+    const cdc::StoreView v = cdc::store_view(fh->fs->store);
+    FL_TRY(hipSetDevice(v.device));
+    FL_TRY(hipMemcpyAsync(d_digests, f->t.digest, f->n * 32, hipMemcpyDeviceToDevice, v.stream));
+    FL_TRY(hipStreamSynchronize(v.stream));
+    return (int64_t)f->n;
+}
+
+int64_t cdc_file_distribution_device(cdc_fh_t *fh, uint8_t *d_digests, uint32_t *d_counts, uint64_t *d_lengths,
+                                     size_t cap, void *hip_stream) {
+    FileRec *f = nullptr;
+    int rc = lookup(fh, true, &f);
+    if (rc) return rc;
+    if (f->n < 2) return 0;  // the zip with skip(1) drops the last span
+    if (cap && (!d_digests || !d_counts || !d_lengths))
+        return fail(CDC_EINVAL, "cdc_file_distribution_device: NULL destination");
+    cdc_files *fs = fh->fs;
+    const cdc::StoreView v = cdc::store_view(fs->store);
+    FL_TRY(hipSetDevice(v.device));
+    hipStream_t s = stream_of(fs, hip_stream);
+    const uint64_t m = f->n - 1;
+    if ((rc = grow_span_scratch(fs, m)) != CDC_OK) return rc;
+    if (fs->d_slots < v.slots) {
+        (void)hipFree(fs->d_cnt);
+        (void)hipFree(fs->d_first);
+        fs->d_cnt = nullptr;
+        fs->d_first = nullptr;
+        fs->d_slots = 0;
+        FL_TRY(hipMalloc(&fs->d_cnt, v.slots * 4));
+        FL_TRY(hipMalloc(&fs->d_first, v.slots * 8));
+        fs->d_slots = v.slots;
+    }
+    FL_TRY(cdc::launch_files_distribution(f->t, m, fs->d_cnt, fs->d_first, fs->a_val, fs->a_block, d_digests,
+                                          d_counts, d_lengths, cap, fs->h_tot + 1, s));
+    FL_TRY(hipStreamSynchronize(s));
+    return (int64_t)fs->h_tot[1];
+}
+
+}  // extern "C"

@@ -387,6 +387,20 @@ hipError_t launch_store_plan_get(StorePiece *pieces, uint64_t n, uint64_t d_out,
     return hipGetLastError();
 }
 
+hipError_t launch_store_scan(uint64_t *v, uint64_t n, uint64_t *block_sums, unsigned long long *total_out,
+                             hipStream_t s) {
+    if (!n) return hipSuccess;
+    scan_exclusive(v, n, block_sums, total_out, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_store_copy(const StorePiece *pieces, const uint64_t *tstart, uint64_t n, uint64_t max_tiles,
+                             const uint64_t *d_total, hipStream_t s) {
+    if (!n || !max_tiles) return hipSuccess;
+    copy_kernel<<<copy_grid(max_tiles), kStThreads, 0, s>>>(pieces, tstart, n, 0, d_total);
+    return hipGetLastError();
+}
+
 hipError_t launch_store_gather(const StorePiece *pieces, const uint64_t *tstart, uint64_t n, uint64_t tiles,
                                uint64_t d_out, void *d_spans, hipStream_t s) {
     if (!n) return hipSuccess;

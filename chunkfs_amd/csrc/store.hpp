@@ -59,4 +59,14 @@ hipError_t launch_store_plan_get(StorePiece *pieces, uint64_t n, uint64_t d_out,
 hipError_t launch_store_gather(const StorePiece *pieces, const uint64_t *tstart, uint64_t n, uint64_t tiles,
                                uint64_t d_out, void *d_spans, hipStream_t s);
 
+// For the file layer (files.hip): the exclusive scan of v[0, n) in place
+// (block_sums: store_scan_blocks(n) + 1 u64, the total left in block_sums[blocks]
+// and in *total_out when given), and the copy over a caller-built piece list
+// whose tile scan is tstart; the tile total is read on the device from
+// *d_total, max_tiles (a host-side bound) only sizes the grid.
+hipError_t launch_store_scan(uint64_t *v, uint64_t n, uint64_t *block_sums, unsigned long long *total_out,
+                             hipStream_t s);
+hipError_t launch_store_copy(const StorePiece *pieces, const uint64_t *tstart, uint64_t n, uint64_t max_tiles,
+                             const uint64_t *d_total, hipStream_t s);
+
 }  // namespace cdc

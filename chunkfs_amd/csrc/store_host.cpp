@@ -10,6 +10,7 @@
 #include "engine.hpp"
 #include "index.hpp"
 #include "store.hpp"
+#include "store_internal.hpp"
 
 struct cdc_store {
     int device = 0;
@@ -34,6 +35,7 @@ struct cdc_store {
     std::vector<uint64_t> h_streams;     // host image of d_streams
     hipStream_t stream = nullptr;
     cdc_index_stats_t st{};
+    uint64_t epoch = 0;            // bumped by reset: locations resolved before it are stale
 };
 
 namespace {
@@ -54,6 +56,7 @@ int reset(cdc_store *st) {
     ST_TRY(hipStreamSynchronize(st->stream));
     st->st = cdc_index_stats_t{};
     st->arena_used = 0;
+    ++st->epoch;
     return CDC_OK;
 }
 
@@ -217,6 +220,21 @@ int64_t put(cdc_store *st, size_t n_streams, const uint8_t *const *d_streams, co
 }
 
 }  // namespace
+
+namespace cdc {
+
+StoreView store_view(const cdc_store *st) {
+    return StoreView{st->device, st->stream, st->epoch, st->t.slots, st->t.length, st->loc, st->arena, st->d_slot};
+}
+
+int64_t store_put_slots(cdc_store *st, const uint8_t *d_data, uint64_t data_len, const cdc_chunk_t *d_chunks,
+                        const uint8_t *d_digests, uint64_t n, void *hip_stream) {
+    const uint64_t lens[1] = {data_len}, first[2] = {0, n};
+    const uint8_t *streams[1] = {d_data};
+    return put(st, 1, streams, lens, first, d_chunks, d_digests, nullptr, hip_stream);
+}
+
+}  // namespace cdc
 
 extern "C" {
 

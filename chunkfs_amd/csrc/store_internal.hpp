@@ -1,0 +1,33 @@
+// store_internal.hpp -- what the file layer (files_host.cpp) needs from the
+// chunk store's host object (store_host.cpp) beyond the C ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/chunkfs_amd.h"
+
+namespace cdc {
+
+// A snapshot of the store's device arrays.  epoch counts the clears: a table
+// slot or arena offset resolved under another epoch is stale.  slot_of is the
+// per-chunk slot list of the last put (launch_index_insert's d_slot_of,
+// duplicates included), valid until the next call on the store.
+struct StoreView {
+    int device;
+    hipStream_t stream;
+    uint64_t epoch;
+    uint64_t slots;
+    const uint64_t *length;  // [slots] length of the slot's chunk
+    const uint64_t *loc;     // [slots] arena offset of the slot's bytes
+    const uint8_t *arena;
+    const uint32_t *slot_of;
+};
+
+StoreView store_view(const cdc_store *st);
+
+// cdc_store_put_device without the new flags; on success store_view().slot_of
+// holds the n slots.  Same checks, same refusal rule, same return value.
+int64_t store_put_slots(cdc_store *st, const uint8_t *d_data, uint64_t data_len, const cdc_chunk_t *d_chunks,
+                        const uint8_t *d_digests, uint64_t n, void *hip_stream);
+
+}  // namespace cdc

@@ -1,6 +1,8 @@
 // store_example.cpp -- the device chunk store through the C++ mirror
 // (include/chunkfs_amd.hpp, class Store): put three fixed chunks (one a
-// duplicate), read two back in another order.
+// duplicate), read two back in another order.  Then the file layer on the same
+// store (classes Files and File): write two files from device buffers and read
+// one byte range of the second.
 #include <hip/hip_runtime_api.h>
 
 #include <cstdio>
@@ -71,6 +73,44 @@ int main() {
             return 1;
         }
         std::printf("store ok: %lld new of 3, read %lld bytes\n", (long long)n_new, (long long)got);
+
+        // Two files on a store of their own; a range that starts and ends inside chunks.
+        const size_t flen = 100000, at = 60000, want = 5000;
+        std::vector<uint8_t> a(flen), b(flen), back(want);
+        uint32_t x = 12345;
+        for (size_t i = 0; i < flen; ++i) {
+            x = x * 1664525u + 1013904223u;
+            a[i] = (uint8_t)(x >> 24);
+            b[i] = (uint8_t)(x >> 16);
+        }
+        uint8_t *d_a = nullptr, *d_b = nullptr, *d_back = nullptr;
+        HIP_OK(hipMalloc((void **)&d_a, flen));
+        HIP_OK(hipMalloc((void **)&d_b, flen));
+        HIP_OK(hipMalloc((void **)&d_back, want));
+        HIP_OK(hipMemcpy(d_a, a.data(), flen, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_b, b.data(), flen, hipMemcpyHostToDevice));
+        {
+            chunkfs_amd::Store fstore(1024, 1 << 20);
+            chunkfs_amd::Files files(fstore);
+            chunkfs_amd::FastChunker chunker({1024, 2048, 4096});
+            chunkfs_amd::File fa = files.create_file("a"), fb = files.create_file("b");
+            const int64_t spans_a = fa.write_device(chunker, d_a, flen);
+            const int64_t spans_b = fb.write_device(chunker, d_b, flen);
+            fa.close();
+            fb.close();
+            chunkfs_amd::File rb = files.open_file_readonly("b");
+            const int64_t n_read = rb.pread_device(at, want, d_back);
+            HIP_OK(hipMemcpy(back.data(), d_back, want, hipMemcpyDeviceToHost));
+            if (spans_a < 2 || spans_b < 2 || rb.stat().size != flen || n_read != (int64_t)want ||
+                std::memcmp(back.data(), b.data() + at, want) || files.list().size() != 2) {
+                std::fprintf(stderr, "file layer read-back differs\n");
+                return 1;
+            }
+            std::printf("files ok: %zu files, pread %lld bytes at %zu\n", files.list().size(), (long long)n_read, at);
+        }
+        (void)hipFree(d_a);
+        (void)hipFree(d_b);
+        (void)hipFree(d_back);
         (void)hipFree(d_data);
         (void)hipFree(d_dig);
         (void)hipFree(d_new);

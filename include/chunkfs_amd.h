@@ -30,8 +30,9 @@ extern "C" {
  * 3: cdc_timing_t.path / .timed appended; cdc_chunk_batch_device_async,
  *    cdc_batch_sync.
  * 4: cdc_sha256_batch_device.
- * 5: cdc_store_* (device chunk store), CDC_ENOTFOUND. */
-#define CHUNKFS_AMD_ABI_VERSION 5
+ * 5: cdc_store_* (device chunk store), CDC_ENOTFOUND.
+ * 6: cdc_files_* / cdc_file_* (device file layer), CDC_EEXIST, CDC_EPERM. */
+#define CHUNKFS_AMD_ABI_VERSION 6
 
 /* Chunk{offset,length} -- reference src/lib.rs:43-47 (usize fields; u64 here). */
 typedef struct cdc_chunk {
@@ -57,6 +58,8 @@ typedef enum cdc_algo {
 #define CDC_EDEVICE (-3) /* HIP runtime error, or no usable gfx950 device */
 #define CDC_ENOTSUP (-4) /* algorithm not implemented */
 #define CDC_ENOTFOUND (-5) /* a requested digest is not in the store (reference: ErrorKind::NotFound) */
+#define CDC_EEXIST (-6)  /* the file name is taken (reference: ErrorKind::AlreadyExists) */
+#define CDC_EPERM (-7)   /* write through a read-only handle (reference: ErrorKind::PermissionDenied) */
 
 typedef struct cdc_handle cdc_handle_t;
 
@@ -408,6 +411,141 @@ int64_t cdc_store_get_device(cdc_store_t *st, const uint8_t *d_digests, size_t n
  * how many were found. */
 int64_t cdc_store_contains_device(cdc_store_t *st, const uint8_t *d_digests, size_t n,
                                   uint8_t *d_found, void *hip_stream);
+
+/* ---- File layer ------------------------------------------------------------------
+ * The reference's FileLayer (src/system/file_layer.rs) and the FileSystem calls
+ * built on it (src/system/mod.rs:58-160, 271-278), bound to one chunk store:
+ * named files, each the ordered span list {hash, offset, len}
+ * (file_layer.rs:9-23).  Names and handles live on the host; each file's span
+ * table lives in HBM (the n + 1 byte offsets, the 32-byte digests, and per span
+ * the table slot and arena offset the store resolved when it was written), and
+ * every per-span step runs on the GPU.  A read goes from span to bytes with no
+ * digest lookup and no host check before the copy.
+ *
+ * Stream ordering and thread-safety are the store's: each call runs on
+ * hip_stream (NULL = the store's own stream) and synchronises it once before
+ * returning; one layer and its store are NOT thread-safe.  Calls on the bound
+ * store may be mixed with calls on the layer.
+ *
+ * A refused call changes nothing: a write the store refuses (CDC_ENOMEM,
+ * CDC_EINVAL) leaves the file's span count and size as they were; a read into
+ * too small a buffer returns the size it needs and writes nothing (snprintf
+ * convention, out_cap = 0 sizes a read).  If the bound store was cleared with
+ * cdc_store_clear since a file's spans were written, reads of that file and
+ * further writes to it return CDC_ENOTFOUND and write nothing.
+ *
+ * ONE deviation from the reference: a span's offset is always its true byte
+ * position in the file.  The reference derives it from the handle
+ * (file_layer.rs:136-145), and a handle from open starts at 0, so appending
+ * through a re-opened handle restarts the offsets at 0 and read then skips
+ * spans.  For a file written through one handle the two agree exactly, and
+ * read_file_complete agrees always.
+ *
+ * Two quirks of the reference are reproduced: a first span longer than the
+ * segment makes cdc_file_read_device return 0 with the cursor stuck
+ * (file_layer.rs:160-167), and the distribution leaves out the file's last span
+ * (file_layer.rs:193-197). */
+typedef struct cdc_files cdc_files_t; /* the layer */
+typedef struct cdc_fh cdc_fh_t;       /* FileHandle (file_layer.rs:32-41) */
+
+typedef struct cdc_file_stat {
+    uint64_t size;        /* bytes: the sum of the span lengths */
+    uint64_t spans;
+    uint64_t cursor;      /* FileHandle::offset as cdc_file_read_device advances it */
+    double chunk_seconds; /* WriteMeasurements of this handle's cdc_file_write_device calls: */
+    double hash_seconds;  /* wall time of the chunking and of the SHA-256 step, summed */
+} cdc_file_stat_t;
+
+/* One range of cdc_files_pread_batch_device. */
+typedef struct cdc_pread {
+    cdc_fh_t *fh;
+    uint64_t offset;
+    uint64_t len;
+    uint8_t *d_dst; /* DEVICE, len bytes, any alignment */
+} cdc_pread_t;
+
+/* FileLayer::default over `store` (not owned: destroy the layer first).
+ * seg_size is the segment of cdc_file_read_device, SEG_SIZE of
+ * file_layer.rs:162; 0 = 1 MiB. */
+int cdc_files_create(cdc_store_t *store, size_t seg_size, cdc_files_t **out);
+/* Open handles must still be closed with cdc_file_close; their other calls
+ * return CDC_EINVAL from here on. */
+void cdc_files_destroy(cdc_files_t *fs);
+/* FileSystem::clear_database (mod.rs:275-278): FileLayer::clear
+ * (file_layer.rs:183-185) and cdc_store_clear.  Every open handle is
+ * invalidated: its calls return CDC_ENOTFOUND until a file of its name is
+ * created again. */
+int cdc_files_clear(cdc_files_t *fs);
+/* FileLayer::file_exists (file_layer.rs:178-180): 1 / 0. */
+int cdc_files_exists(const cdc_files_t *fs, const char *name);
+/* FileLayer::list_files (file_layer.rs:271-273): the names in byte order, each
+ * followed by a NUL.  Returns the bytes needed; a return > cap means nothing
+ * was written. */
+int64_t cdc_files_list(const cdc_files_t *fs, char *buf, size_t cap);
+
+/* FileLayer::create (file_layer.rs:84-99): CDC_EEXIST if !create_new and the
+ * name exists; otherwise creates the file or replaces it with an empty one
+ * (FileSystem::create_file passes true, mod.rs:81-87).  The handle may write. */
+int cdc_files_create_file(cdc_files_t *fs, const char *name, int create_new, cdc_fh_t **out);
+/* FileLayer::open / open_readonly (file_layer.rs:102-114): CDC_ENOTFOUND for an
+ * unknown name.  Several handles may be open on one file; every handle starts
+ * with its cursor at 0. */
+int cdc_files_open(cdc_files_t *fs, const char *name, int readonly, cdc_fh_t **out);
+/* FileHandle::close (file_layer.rs:77-79); read the measurements with
+ * cdc_file_stat first. */
+void cdc_file_close(cdc_fh_t *fh);
+int cdc_file_stat(cdc_fh_t *fh, cdc_file_stat_t *out);
+
+/* FileSystem::write_to_file (mod.rs:93-110) for data already in HBM: one
+ * chunk_data over the whole call (cdc_chunk_batch_device, one stream), SHA-256
+ * of every chunk (cdc_sha256_batch_device), put into the store, spans appended
+ * (file_layer.rs:136-148) -- in buffers the layer owns, nothing but the counts
+ * crossing to the host.  d_data: DEVICE, 16-byte aligned (what FastCDC asks of
+ * device streams).  Returns the number of spans appended; CDC_EPERM through a
+ * read-only handle. */
+int64_t cdc_file_write_device(cdc_fh_t *fh, cdc_handle_t *chunker, const uint8_t *d_data, size_t len,
+                              void *hip_stream);
+/* The same for callers that chunked and hashed already: arguments as
+ * cdc_store_put_device.  Chunks need not tile the data; length-0 chunks are
+ * legal.  A span's length is that of the chunk stored under its digest. */
+int64_t cdc_file_append_device(cdc_fh_t *fh, const uint8_t *d_data, size_t data_len, const cdc_chunk_t *d_chunks,
+                               const uint8_t *d_digests, size_t n, void *hip_stream);
+
+/* FileSystem::read_file_complete (mod.rs:149-152): every span in order, back to
+ * back in d_out (DEVICE, any alignment); d_spans (nullable, DEVICE
+ * cdc_chunk_t[spans]) receives each span's {offset, length}.  Returns the
+ * file's size; a return > out_cap means nothing was written. */
+int64_t cdc_file_read_complete_device(cdc_fh_t *fh, uint8_t *d_out, size_t out_cap, cdc_chunk_t *d_spans,
+                                      void *hip_stream);
+/* FileSystem::read_from_file (mod.rs:157-160, file_layer.rs:152-175): from the
+ * handle's cursor, whole spans while their running total stays <= the layer's
+ * segment size; the cursor advances by the bytes returned.  0 at the end of the
+ * file, and 0 with the cursor unchanged when the span at the cursor is longer
+ * than the segment (as in the reference).  A return > out_cap: nothing
+ * written, cursor unchanged. */
+int64_t cdc_file_read_device(cdc_fh_t *fh, uint8_t *d_out, size_t out_cap, void *hip_stream);
+/* Not in the reference: the bytes [offset, min(offset + len, size)) of the file
+ * into d_out (DEVICE, len bytes, any alignment).  Returns the count like
+ * pread(2); len = 0 or offset >= size gives 0.  The cursor is not used. */
+int64_t cdc_file_pread_device(cdc_fh_t *fh, uint64_t offset, size_t len, uint8_t *d_out, void *hip_stream);
+/* n ranges over any files of the layer, planned and copied as one piece list.
+ * reqs and got are HOST arrays of n entries; got[i] = bytes of request i.
+ * Destinations must not overlap. */
+int cdc_files_pread_batch_device(cdc_files_t *fs, size_t n, const cdc_pread_t *reqs, uint64_t *got,
+                                 void *hip_stream);
+/* FileLayer::read_complete (file_layer.rs:127-133): the spans' digests, in
+ * order (DEVICE, 32 bytes each).  Returns the span count; a return > cap means
+ * nothing was written.  Runs on the store's own stream. */
+int64_t cdc_file_hashes_device(cdc_fh_t *fh, uint8_t *d_digests, size_t cap);
+
+/* FileLayer::chunk_count_distribution (file_layer.rs:188-206) over spans
+ * 0 .. n-2 (the reference's zip with skip(1) drops the last span): per distinct
+ * digest its count and the length of its first occurrence, in order of first
+ * occurrence in the file (the reference's map is unordered).  DEVICE arrays of
+ * cap entries (32-byte digests, u32 counts, u64 lengths).  Returns the number
+ * of distinct digests; a return > cap means nothing was written. */
+int64_t cdc_file_distribution_device(cdc_fh_t *fh, uint8_t *d_digests, uint32_t *d_counts, uint64_t *d_lengths,
+                                     size_t cap, void *hip_stream);
 
 /* ---- Synthetic data -----------------------------------------
  * Fill a DEVICE buffer with the splitmix64 stream: little-endian u64 words,

@@ -10,6 +10,7 @@
 //   Rabin/Ultra/Leap/SeqChunker     chunkers/{rabin,ultra,leap,seq}.rs  same names
 //   ChunkStorage::write spans       system/storage.rs:78-103  Chunker::write_spans
 //   Database + ChunkStorage::retrieve  system/database.rs, storage.rs:141-157  chunkfs_amd::Store
+//   FileSystem / FileLayer / FileHandle  system/mod.rs, file_layer.rs  chunkfs_amd::Files, File
 //
 // The reference panics on invalid sizes; here constructors throw
 // chunkfs_amd::Error (carrying the CDC_E* code and cdc_last_error()).
@@ -233,6 +234,115 @@ class Store {
 
   private:
     cdc_store_t *st_ = nullptr;
+};
+
+// FileHandle (file_layer.rs:32-41) on the device file layer: closes on
+// destruction.  Move-only.  All pointers named d_* are DEVICE pointers.
+class File {
+  public:
+    File() = default;
+    explicit File(cdc_fh_t *fh) : fh_(fh) {}
+    ~File() { cdc_file_close(fh_); }
+    File(File &&o) noexcept : fh_(o.fh_) { o.fh_ = nullptr; }
+    File &operator=(File &&o) noexcept {
+        if (this != &o) {
+            cdc_file_close(fh_);
+            fh_ = o.fh_;
+            o.fh_ = nullptr;
+        }
+        return *this;
+    }
+    File(const File &) = delete;
+    File &operator=(const File &) = delete;
+
+    // write_to_file (mod.rs:93-110) for data in HBM: chunk, SHA-256, put, append.
+    int64_t write_device(Chunker &chunker, const uint8_t *d_data, size_t len, void *hip_stream = nullptr) {
+        return check(cdc_file_write_device(fh_, chunker.handle(), d_data, len, hip_stream));
+    }
+    // The same for chunks and digests the caller computed.
+    int64_t append_device(const uint8_t *d_data, size_t data_len, const cdc_chunk_t *d_chunks,
+                          const uint8_t *d_digests, size_t n, void *hip_stream = nullptr) {
+        return check(cdc_file_append_device(fh_, d_data, data_len, d_chunks, d_digests, n, hip_stream));
+    }
+    // read_file_complete (mod.rs:149-152): the size; > out_cap means nothing was written.
+    int64_t read_complete_device(uint8_t *d_out, size_t out_cap, cdc_chunk_t *d_spans = nullptr,
+                                 void *hip_stream = nullptr) {
+        return check(cdc_file_read_complete_device(fh_, d_out, out_cap, d_spans, hip_stream));
+    }
+    // read_from_file (mod.rs:157-160): one segment of whole spans from the cursor.
+    int64_t read_device(uint8_t *d_out, size_t out_cap, void *hip_stream = nullptr) {
+        return check(cdc_file_read_device(fh_, d_out, out_cap, hip_stream));
+    }
+    // The bytes [offset, min(offset + len, size)).
+    int64_t pread_device(uint64_t offset, size_t len, uint8_t *d_out, void *hip_stream = nullptr) {
+        return check(cdc_file_pread_device(fh_, offset, len, d_out, hip_stream));
+    }
+    // FileLayer::read_complete (file_layer.rs:127-133): the span digests.
+    int64_t hashes_device(uint8_t *d_digests, size_t cap) { return check(cdc_file_hashes_device(fh_, d_digests, cap)); }
+    // chunk_count_distribution (file_layer.rs:188-206), first-occurrence order.
+    int64_t distribution_device(uint8_t *d_digests, uint32_t *d_counts, uint64_t *d_lengths, size_t cap,
+                                void *hip_stream = nullptr) {
+        return check(cdc_file_distribution_device(fh_, d_digests, d_counts, d_lengths, cap, hip_stream));
+    }
+    cdc_file_stat_t stat() const {
+        cdc_file_stat_t s{};
+        check(cdc_file_stat(fh_, &s));
+        return s;
+    }
+    // close_file (mod.rs:140-146); stat() first for the measurements.
+    void close() {
+        cdc_file_close(fh_);
+        fh_ = nullptr;
+    }
+    cdc_fh_t *handle() { return fh_; }
+
+  private:
+    cdc_fh_t *fh_ = nullptr;
+};
+
+// The device file layer over one Store: FileSystem's file calls
+// (system/mod.rs:58-160, 271-278).  A span's offset is its true byte position
+// in the file (the one deviation from file_layer.rs:136-145).  The Store must
+// outlive the Files; a refused call throws and changes nothing.
+class Files {
+  public:
+    explicit Files(Store &store, size_t seg_size = SEG_SIZE) { check(cdc_files_create(store.handle(), seg_size, &fs_)); }
+    ~Files() { cdc_files_destroy(fs_); }
+    Files(const Files &) = delete;
+    Files &operator=(const Files &) = delete;
+
+    // FileLayer::create (file_layer.rs:84-99); create_file passes create_new = true.
+    File create(const std::string &name, bool create_new) {
+        cdc_fh_t *fh = nullptr;
+        check(cdc_files_create_file(fs_, name.c_str(), create_new ? 1 : 0, &fh));
+        return File(fh);
+    }
+    File create_file(const std::string &name) { return create(name, true); }
+    File open_file(const std::string &name) { return open(name, false); }
+    File open_file_readonly(const std::string &name) { return open(name, true); }
+    bool exists(const std::string &name) const { return check(cdc_files_exists(fs_, name.c_str())) != 0; }
+    std::vector<std::string> list() const {
+        std::vector<char> buf((size_t)check(cdc_files_list(fs_, nullptr, 0)));
+        check(cdc_files_list(fs_, buf.data(), buf.size()));
+        std::vector<std::string> names;
+        for (size_t at = 0; at < buf.size(); at += names.back().size() + 1) names.emplace_back(buf.data() + at);
+        return names;
+    }
+    // Many ranges over many files, planned and copied as one piece list.
+    void pread_batch_device(size_t n, const cdc_pread_t *reqs, uint64_t *got, void *hip_stream = nullptr) {
+        check(cdc_files_pread_batch_device(fs_, n, reqs, got, hip_stream));
+    }
+    // clear_database (mod.rs:275-278): no files, an empty store, handles invalid.
+    void clear() { check(cdc_files_clear(fs_)); }
+    cdc_files_t *handle() { return fs_; }
+
+  private:
+    File open(const std::string &name, bool readonly) {
+        cdc_fh_t *fh = nullptr;
+        check(cdc_files_open(fs_, name.c_str(), readonly ? 1 : 0, &fh));
+        return File(fh);
+    }
+    cdc_files_t *fs_ = nullptr;
 };
 
 }  // namespace chunkfs_amd

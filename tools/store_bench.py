@@ -9,7 +9,13 @@ stream:
       (precheck + index insert + scans + the copy into the arena);
   (b) get_device of the whole file (lookup + scans + the copy out);
   (c) hipMemcpyAsync device-to-device of the same bytes, in the same process
-      -- the yardstick: the device's own copy of the same data.
+      -- the yardstick: the device's own copy of the same data;
+  (d) cdc_file_write_device of the whole stream into an empty file layer
+      (chunking + SHA-256 + put + span append: (d) includes the chunking and
+      hashing that (a) is handed ready-made, so the two are not compared);
+  (e) cdc_file_read_complete_device of that file (range planner + the copy:
+      no digest lookup, no host check before the copy) -- compare with (b);
+  (f) cdc_file_read_device looped over the file, reported per 1 MiB segment.
 
 Also timed, to separate the copy kernel from the bookkeeping around it:
 contains_device (the lookup alone) and get_device with out_cap = 0 (lookup +
@@ -110,6 +116,41 @@ def main():
         rc = hip.hipMemcpyAsync(out.data_ptr(), buf.data_ptr(), n, HIP_MEMCPY_D2D, sp)
         assert rc == 0, f"hipMemcpyAsync: {rc}"
 
+    # The file layer, on a store of its own of the same size.
+    L = _lib.lib()
+    P = ctypes.c_void_p
+    fsys = c.FileSystem(store=c.ChunkStore(k, n + 16 * k))
+    state = {}
+
+    def new_file():
+        fsys.clear_database()
+        state["w"] = fsys.create_file("bench", ch)
+
+    def do_fwrite():
+        got = L.cdc_file_write_device(state["w"]._fh, ch._h, P(buf.data_ptr()), n, P(sp))
+        assert got == k, f"cdc_file_write_device: {got}"
+
+    def do_fread():
+        assert L.cdc_file_read_complete_device(state["w"]._fh, P(out.data_ptr()), n, None, P(sp)) == n
+
+    def do_fsize():
+        assert L.cdc_file_read_complete_device(state["w"]._fh, None, 0, None, P(sp)) == n
+
+    def reopen():
+        state["r"] = fsys.open_file_readonly("bench")
+        state["segments"] = 0
+
+    def do_fsegments():
+        fh, total = state["r"]._fh, 0
+        while True:
+            got = L.cdc_file_read_device(fh, P(out.data_ptr()), c.SEG_SIZE, P(sp))
+            assert got >= 0
+            if got == 0:
+                break
+            total += got
+            state["segments"] += 1
+        assert total == n
+
     t_put = timed(do_put, before=store.clear)
     out.zero_()
     t_get = timed(do_get)
@@ -119,6 +160,15 @@ def main():
     t_memcpy = timed(do_memcpy)
     if not same:
         raise SystemExit("store_bench: get_device did not return the bytes put_batch_device stored")
+    t_fwrite = timed(do_fwrite, before=new_file)
+    out.zero_()
+    t_fread = timed(do_fread)
+    fsame = bool(torch.equal(out, buf))
+    t_fsize = timed(do_fsize)
+    t_fseg = timed(do_fsegments, before=reopen)
+    segments = state["segments"]
+    if not fsame:
+        raise SystemExit("store_bench: cdc_file_read_complete_device did not return the bytes written")
 
     gib = n / (1 << 30)
     med = lambda v: float(np.median(v))  # noqa: E731
@@ -138,6 +188,15 @@ def main():
         "contains_ms": med(t_contains), "get_size_only_ms": med(t_size),
         "get_copy_ms": copy_ms, "get_copy_GiBps": gib / (copy_ms * 1e-3) if copy_ms > 0 else None,
         "readback_equal": same,
+        # (d) includes chunking and SHA-256, which (a) does not: the two are not compared.
+        "file_write_ms": med(t_fwrite), "file_write_ms_min_max": [min(t_fwrite), max(t_fwrite)],
+        "file_write_GiBps": rate(t_fwrite),
+        "file_read_ms": med(t_fread), "file_read_ms_min_max": [min(t_fread), max(t_fread)],
+        "file_read_GiBps": rate(t_fread), "file_read_vs_get": med(t_get) / med(t_fread),
+        "file_read_vs_memcpy": med(t_memcpy) / med(t_fread),
+        "file_read_size_only_ms": med(t_fsize), "file_read_copy_ms": med(t_fread) - med(t_fsize),
+        "file_segments": segments, "file_segment_us": med(t_fseg) * 1e3 / segments,
+        "file_segment_pass_ms": med(t_fseg), "file_readback_equal": fsame,
     }
     line = json.dumps(res)
     print(line)
