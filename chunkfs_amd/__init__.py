@@ -16,6 +16,9 @@ include/chunkfs_amd.h (libchunkfs_amd.so, hand-written HIP for gfx950):
     ChunkStorage::write  system/storage.rs    write_spans()
     Database (digest set) system/database.rs  DedupIndex
     Database + retrieve / read_file_complete  ChunkStore
+    Scrub, CopyScrubber, DumbScrubber         CopyScrubber, DumbScrubber (system/scrub.rs);
+                                              RechunkScrubber is this project's own
+    ScrubMeasurements  system/scrub.rs:71-79  ScrubMeasurements
     FileSystem / FileLayer  system/mod.rs,    FileSystem, FileHandle
                             file_layer.rs
 
@@ -39,6 +42,7 @@ __all__ = [
     "FSChunker", "RabinChunker", "SuperChunker", "UltraChunker", "LeapChunker",
     "SeqChunker", "OperationMode", "SeqConfig", "CdcError", "write_spans", "StreamWriter", "version",
     "DedupIndex", "ChunkStore", "FileSystem", "FileHandle",
+    "CopyScrubber", "DumbScrubber", "RechunkScrubber", "ScrubMeasurements",
 ]
 
 
@@ -498,6 +502,49 @@ def _ptr(p):
     return None if p is None else ctypes.c_void_p(int(p))
 
 
+def _ratio(num, den):
+    """num / den by f64 rules, as the reference's `as f64` divisions: inf when
+    only the divisor is 0, nan for 0 / 0."""
+    if den:
+        return num / den
+    return float("inf") if num else float("nan")
+
+
+class ScrubMeasurements:
+    """ScrubMeasurements (scrub.rs:71-79): bytes processed, seconds spent, bytes left untouched."""
+
+    __slots__ = ("processed_data", "running_time", "data_left")
+
+    def __init__(self, processed_data=0, running_time=0.0, data_left=0):
+        self.processed_data, self.running_time, self.data_left = int(processed_data), float(running_time), int(data_left)
+
+    def __repr__(self):
+        return (f"ScrubMeasurements {{ processed_data: {self.processed_data}, running_time: {self.running_time}s, "
+                f"data_left: {self.data_left} }}")
+
+
+class CopyScrubber:
+    """CopyScrubber (scrub.rs:85-114): every chunk moves to the target map under
+    its own hash; the container keeps that one key."""
+    _code, chunker = _lib.CDC_SCRUB_COPY, None
+
+
+class DumbScrubber:
+    """DumbScrubber (scrub.rs:116-129): does nothing, all-zero measurements."""
+    _code, chunker = _lib.CDC_SCRUB_DUMB, None
+
+
+class RechunkScrubber:
+    """Not in the reference: every stored chunk is chunked again with `chunker`
+    (any Chunker of this package, normally a finer one), the sub-chunks are
+    deduplicated in the target map under their SHA-256, and the container keeps
+    the list of keys."""
+    _code = _lib.CDC_SCRUB_RECHUNK
+
+    def __init__(self, chunker):
+        self.chunker = chunker
+
+
 class ChunkStore:
     """The reference's key -> data Database (database.rs:10-36, 74-87, first
     insert wins) with ChunkStorage::retrieve (storage.rs:141-157) and
@@ -557,9 +604,62 @@ class ChunkStore:
         check(lib().cdc_store_stats(self._h, ctypes.byref(s)))
         d = {f: getattr(s.index, f) for f, _ in _lib.cdc_index_stats_t._fields_}
         d["arena_used"], d["arena_capacity"] = s.arena_used, s.arena_capacity
+        if getattr(self, "_target", None) is not None:
+            # total_cdc_size counts chunk-kind containers only (storage.rs:193-200)
+            cdc = self.scrub_stats()["cdc_bytes"]
+            d["cdc_dedup_ratio"] = _ratio(d["bytes_written"], cdc)
+            d["average_chunk_size"] = cdc // d["unique_chunks"] if d["unique_chunks"] else 0
+            return d
         d["cdc_dedup_ratio"] = d["bytes_written"] / d["unique_bytes"] if d["unique_bytes"] else float("nan")
         d["average_chunk_size"] = d["unique_bytes"] // d["unique_chunks"] if d["unique_chunks"] else 0
         return d
+
+    # -- scrub stage (include/chunkfs_amd.h, "Scrub stage") -----------------------
+    def set_target(self, target):
+        """ChunkStorage::new_with_scrubber's target_map: `target` (a ChunkStore on
+        the same device) becomes this store's target map."""
+        check(lib().cdc_store_set_target(self._h, target._h if target is not None else None))
+        self._target = target  # kept alive: the library does not own it
+
+    def scrub(self, scrubber, stream=None):
+        """ChunkStorage::scrub (storage.rs:180-190) with CopyScrubber(),
+        DumbScrubber() or RechunkScrubber(chunker); returns ScrubMeasurements."""
+        m = _lib.cdc_scrub_measurements_t()
+        ch = scrubber.chunker._h if scrubber.chunker is not None else None
+        check(lib().cdc_store_scrub(self._h, scrubber._code, ch, ctypes.byref(m), _ptr(stream)))
+        if scrubber.chunker is not None:
+            scrubber.chunker._drained()
+        return ScrubMeasurements(m.processed_data, m.running_seconds, m.data_left)
+
+    def scrub_stats(self):
+        s = _lib.cdc_scrub_stats_t()
+        check(lib().cdc_store_scrub_stats(self._h, ctypes.byref(s)))
+        return {f: getattr(s, f) for f, _ in _lib.cdc_scrub_stats_t._fields_}
+
+    def storage_iterator(self):
+        """ChunkStorage::iterator (storage.rs:233-235): a list of (digest bytes,
+        "chunk" | "target", length the container restores to, [key bytes]), in
+        the store's slot order."""
+        import torch
+        dev = f"cuda:{self.device}"
+        n = check(lib().cdc_store_iterate_device(self._h, None, None, None, None, 0, None))
+        if n == 0:
+            return []
+        dig = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+        kind = torch.empty(n, dtype=torch.uint8, device=dev)
+        ln = torch.empty(n, dtype=torch.int64, device=dev)
+        kf = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        assert check(lib().cdc_store_iterate_device(self._h, _ptr(dig.data_ptr()), _ptr(kind.data_ptr()),
+                                                    _ptr(ln.data_ptr()), _ptr(kf.data_ptr()), n, None)) == n
+        nk = check(lib().cdc_store_keys_device(self._h, None, 0, None))
+        keys = torch.empty((max(nk, 1), 32), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        assert check(lib().cdc_store_keys_device(self._h, _ptr(keys.data_ptr()), nk, None)) == nk
+        dig, kind, ln, kf, keys = (t.cpu().numpy() for t in (dig, kind, ln, kf, keys))
+        assert int(kf[n]) == nk
+        return [(dig[i].tobytes(), "target" if kind[i] else "chunk", int(ln[i]),
+                 [keys[k].tobytes() for k in range(int(kf[i]), int(kf[i + 1]))]) for i in range(n)]
 
     # -- host conveniences over the calls above --------------------------------
     def write(self, chunker, data):
@@ -641,6 +741,20 @@ class FileSystem:
         h = ctypes.c_void_p()
         check(lib().cdc_files_create(self.store._h, self.seg_size, ctypes.byref(h)))
         self._h = h
+
+    @classmethod
+    def new_with_scrubber(cls, scrubber, target=None, max_chunks=1 << 16, arena_bytes=256 * MB,
+                          target_max_chunks=1 << 18, target_arena_bytes=256 * MB, seg_size=SEG_SIZE, device=0):
+        """FileSystem::new_with_scrubber (mod.rs:226-239): a file system whose
+        store has a target map (`target`, a ChunkStore, created here when None)
+        and whose scrub() runs `scrubber`."""
+        store = ChunkStore(max_chunks, arena_bytes, device)
+        if target is None:
+            target = ChunkStore(target_max_chunks, target_arena_bytes, device)
+        store.set_target(target)
+        fs = cls(store=store, seg_size=seg_size)
+        fs.target, fs._scrubber = target, scrubber
+        return fs
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -808,8 +922,21 @@ class FileSystem:
     def full_cdc_dedup_ratio(self):
         """size_written / (unique bytes + 32 bytes of key per unique digest)."""
         s = self.store.stats()
+        if getattr(self.store, "_target", None) is not None:
+            return _ratio(s["bytes_written"], self.store.scrub_stats()["cdc_bytes"] + 32 * s["unique_chunks"])
         denom = s["unique_bytes"] + 32 * s["unique_chunks"]
         return s["bytes_written"] / denom if denom else float("nan")
+
+    def total_dedup_ratio(self):
+        """FileSystem::total_dedup_ratio (mod.rs:289-291): size_written / (bytes
+        of the chunk-kind containers + bytes of the target map's values)."""
+        x = self.store.scrub_stats()
+        return _ratio(self.store.stats()["bytes_written"], x["cdc_bytes"] + x["target_bytes"])
+
+    def storage_iterator(self):
+        """FileSystem::storage_iterator (mod.rs:266-269) as a list; see
+        ChunkStore.storage_iterator."""
+        return self.store.storage_iterator()
 
     def average_chunk_size(self):
         return self.store.stats()["average_chunk_size"]
@@ -819,9 +946,22 @@ class FileSystem:
         every open handle invalid."""
         check(lib().cdc_files_clear(self._h))
 
+    def clear_file_system(self):
+        """FileSystem::clear_file_system (mod.rs:294-297): clear_database and the
+        target map."""
+        target = getattr(self.store, "_target", None)
+        if target is not None:
+            target.clear()  # first: the base's clear then adopts the emptied target
+        self.clear_database()
+
     def scrub(self):
-        """A CDC file system has no scrubber: ErrorKind::InvalidInput (storage.rs:180-190)."""
-        raise CdcError(_lib.CDC_EINVAL, "scrub: this file system was created without a scrubber")
+        """FileSystem::scrub (mod.rs:245-247): runs the scrubber the file system
+        was created with (new_with_scrubber) and returns its ScrubMeasurements.
+        A CDC file system has none: ErrorKind::InvalidInput (storage.rs:180-190)."""
+        scrubber = getattr(self, "_scrubber", None)
+        if scrubber is None:
+            raise CdcError(_lib.CDC_EINVAL, "scrub: this file system was created without a scrubber")
+        return self.store.scrub(scrubber)
 
 
 def version():

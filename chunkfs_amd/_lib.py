@@ -33,6 +33,8 @@ EXPORTS = [
     "cdc_index_stats",
     "cdc_store_create", "cdc_store_destroy", "cdc_store_clear", "cdc_store_stats", "cdc_store_put_device",
     "cdc_store_put_batch_device", "cdc_store_get_device", "cdc_store_contains_device",
+    "cdc_store_set_target", "cdc_store_scrub", "cdc_store_scrub_stats", "cdc_store_iterate_device",
+    "cdc_store_keys_device",
     "cdc_files_create", "cdc_files_destroy", "cdc_files_clear", "cdc_files_exists", "cdc_files_list",
     "cdc_files_create_file", "cdc_files_open", "cdc_file_close", "cdc_file_stat", "cdc_file_write_device",
     "cdc_file_append_device", "cdc_file_read_complete_device", "cdc_file_read_device", "cdc_file_pread_device",
@@ -63,6 +65,20 @@ class cdc_index_stats_t(ctypes.Structure):
 class cdc_store_stats_t(ctypes.Structure):
     _fields_ = [("index", cdc_index_stats_t), ("arena_capacity", ctypes.c_uint64),
                 ("arena_used", ctypes.c_uint64)]
+
+
+class cdc_scrub_measurements_t(ctypes.Structure):
+    _fields_ = [("processed_data", ctypes.c_uint64), ("running_seconds", ctypes.c_double),
+                ("data_left", ctypes.c_uint64)]
+
+
+class cdc_scrub_stats_t(ctypes.Structure):
+    _fields_ = [("cdc_bytes", ctypes.c_uint64), ("chunk_containers", ctypes.c_uint64),
+                ("target_containers", ctypes.c_uint64), ("keys", ctypes.c_uint64),
+                ("target_bytes", ctypes.c_uint64), ("target_values", ctypes.c_uint64)]
+
+
+CDC_SCRUB_DUMB, CDC_SCRUB_COPY, CDC_SCRUB_RECHUNK = 0, 1, 2
 
 
 class cdc_file_stat_t(ctypes.Structure):
@@ -198,6 +214,16 @@ def lib():
     L.cdc_store_get_device.restype = ctypes.c_int64
     L.cdc_store_contains_device.argtypes = [P, P, sz, P, P]
     L.cdc_store_contains_device.restype = ctypes.c_int64
+    L.cdc_store_set_target.argtypes = [P, P]
+    L.cdc_store_set_target.restype = ctypes.c_int
+    L.cdc_store_scrub.argtypes = [P, ctypes.c_int, P, ctypes.POINTER(cdc_scrub_measurements_t), P]
+    L.cdc_store_scrub.restype = ctypes.c_int
+    L.cdc_store_scrub_stats.argtypes = [P, ctypes.POINTER(cdc_scrub_stats_t)]
+    L.cdc_store_scrub_stats.restype = ctypes.c_int
+    L.cdc_store_iterate_device.argtypes = [P, P, P, P, P, sz, P]
+    L.cdc_store_iterate_device.restype = ctypes.c_int64
+    L.cdc_store_keys_device.argtypes = [P, P, sz, P]
+    L.cdc_store_keys_device.restype = ctypes.c_int64
     L.cdc_files_create.argtypes = [P, sz, ctypes.POINTER(P)]
     L.cdc_files_create.restype = ctypes.c_int
     L.cdc_files_destroy.argtypes = [P]

@@ -18,6 +18,10 @@ int64_t bad_handle() {
 }
 }  // namespace
 
+namespace cdc {
+int handle_device(const cdc_handle *h) { return h->engine->device(); }
+}  // namespace cdc
+
 extern "C" {
 
 int cdc_create(cdc_algo_t algo, uint32_t min, uint32_t avg, uint32_t max,

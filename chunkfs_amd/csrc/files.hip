@@ -21,6 +21,12 @@
 // per piece finds its request by binary search and writes the trimmed {src,
 // dst, len} and its tile count; the tile scan and the store's copy kernel
 // (store.hip) follow, the tile total read on the device.
+//
+// Once the store holds target-kind containers (the scrub stage, store.hpp
+// ScrubView) the chain has one more level: the spans of a request become span
+// records, a target-kind span yields one piece per key, a range trims its two
+// end spans by binary search over the per-key offsets, and the exact piece
+// count goes to the host before the copy.  The chain above is untouched.
 #include "files.hpp"
 
 namespace cdc {
@@ -192,6 +198,100 @@ __global__ __launch_bounds__(kFlThreads) void pieces_kernel(const ReadReq *__res
     tiles[p] = t;
 }
 
+// ---- the scrubbed state: span -> pieces ------------------------------------------
+// pstart = exclusive scan of the span counts, *total_spans their sum.  Threads
+// past the total write a count of 0, so the piece scan runs over max_spans.
+__global__ __launch_bounds__(kFlThreads) void span_x_kernel(const ReadReq *__restrict__ req,
+                                                            const uint64_t *__restrict__ rslot, uint64_t nreq,
+                                                            const ReadPlan *__restrict__ plan,
+                                                            const uint64_t *__restrict__ pstart,
+                                                            const uint64_t *__restrict__ total_spans, ScrubView v,
+                                                            SpanRec *recs, uint64_t *pcnt, uint64_t max_spans,
+                                                            unsigned long long *touch) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t touched = 0;
+    if (p < max_spans) {
+        uint64_t cnt = 0;
+        if (p < *total_spans) {
+            uint64_t a = 0, b = nreq;  // last request r with pstart[r] <= p
+            while (b - a > 1) {
+                const uint64_t mid = (a + b) >> 1;
+                if (pstart[mid] <= p) a = mid;
+                else b = mid;
+            }
+            const ReadReq q = req[a];
+            const ReadPlan pl = plan[a];
+            const uint64_t k = p - pstart[a], i = pl.first + k;
+            const uint64_t s0 = q.off[i], s1 = q.off[i + 1];
+            const uint64_t from = s0 > pl.lo ? s0 : pl.lo, to = s1 < pl.hi ? s1 : pl.hi;
+            const uint64_t len = to > from ? to - from : 0;
+            if (q.spans) reinterpret_cast<cdc_chunk_pod *>(q.spans)[k] = cdc_chunk_pod{from - pl.lo, len};
+            const uint32_t slot = reinterpret_cast<const uint32_t *>(rslot[a])[i];
+            SpanRec r{s0, from, from + len, q.dst - pl.lo, ~0ull, slot, 0};
+            if (slot != kNoSlot) {
+                if (!v.kind[slot]) {
+                    cnt = 1;
+                } else {
+                    touched = 1;
+                    const uint64_t kf = v.key_first[slot], kc = v.key_count[slot];
+                    if (kc && from == s0 && to == s1) {  // a whole span: every key
+                        r.key0 = kf;
+                        cnt = kc;
+                    } else if (kc && len) {
+                        // Only the two ends of a range: the keys that hold its first and last byte.
+                        // Keys of length 0 share an offset with the key after them, so the last
+                        // key starting at or before a byte is the one that holds it.
+                        const uint64_t k0 = last_at_or_before(v.key_off, kf, kf + kc - 1, from - s0);
+                        const uint64_t k1 = last_at_or_before(v.key_off, k0, kf + kc - 1, to - 1 - s0);
+                        r.key0 = k0;
+                        cnt = k1 - k0 + 1;
+                    } else {
+                        r.key0 = kf;
+                    }
+                }
+            }
+            recs[p] = r;
+        }
+        pcnt[p] = cnt;
+    }
+#pragma unroll
+    for (int k = 1; k < 64; k <<= 1) touched += __shfl_xor(touched, k);
+    if ((threadIdx.x & 63) == 0 && touched) atomicAdd(touch, (unsigned long long)touched);
+}
+
+__global__ __launch_bounds__(kFlThreads) void span_pieces_kernel(const SpanRec *__restrict__ recs,
+                                                              const uint64_t *__restrict__ pstart,
+                                                              uint64_t max_spans, ScrubView v,
+                                                              const uint64_t *__restrict__ loc, uint64_t arena,
+                                                              StorePiece *pieces, uint64_t *tiles,
+                                                              uint64_t n_pieces) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pieces) return;
+    uint64_t a = 0, b = max_spans;  // last span q with pstart[q] <= p (spans of no pieces share a start)
+    while (b - a > 1) {
+        const uint64_t mid = (a + b) >> 1;
+        if (pstart[mid] <= p) a = mid;
+        else b = mid;
+    }
+    const SpanRec r = recs[a];
+    StorePiece pc;
+    if (r.key0 == ~0ull) {
+        pc.src = arena + loc[r.slot] + (r.from - r.s0);
+        pc.dst = r.dst0 + r.from;
+        pc.len = r.to - r.from;
+    } else {
+        const uint64_t k = r.key0 + (p - pstart[a]);
+        const uint32_t ts = v.key_slot[k];
+        const uint64_t k0 = r.s0 + v.key_off[k], k1 = k0 + v.t_length[ts];  // the key's bytes in the file
+        const uint64_t from = k0 > r.from ? k0 : r.from, to = k1 < r.to ? k1 : r.to;
+        pc.src = v.t_arena + v.t_loc[ts] + (from - k0);
+        pc.dst = r.dst0 + from;
+        pc.len = to > from ? to - from : 0;
+    }
+    pieces[p] = pc;
+    tiles[p] = pc.len ? ((pc.dst & (kStoreAlign - 1)) + pc.len + (kStoreTile - 1)) / kStoreTile : 0;
+}
+
 // ---- distribution ----------------------------------------------------------------
 __global__ __launch_bounds__(kFlThreads) void dist_init_kernel(const uint32_t *__restrict__ slot, uint64_t m,
                                                                uint32_t *cnt, uint64_t *firstpos) {
@@ -271,6 +371,38 @@ hipError_t launch_files_read(const ReadReq *d_req, uint64_t nreq, uint64_t arena
     e = launch_store_scan(tstart, max_pieces, block_sums, nullptr, s);
     if (e != hipSuccess) return e;
     return launch_store_copy(pieces, tstart, max_pieces, max_tiles, block_sums + store_scan_blocks(max_pieces), s);
+}
+
+hipError_t launch_files_plan_x(const ReadReq *d_req, const uint64_t *d_rslot, uint64_t nreq, const ScrubView &v,
+                               ReadPlan *plan, uint64_t *cnt, uint64_t *rblock, SpanRec *recs, uint64_t *pcnt,
+                               uint64_t *pblock, uint64_t max_spans, ReadResult *h_res,
+                               unsigned long long *d_touch, unsigned long long *h_tot, hipStream_t s) {
+    if (!nreq) return hipSuccess;
+    uint64_t *total_spans = rblock + store_scan_blocks(nreq);
+    resolve_kernel<<<grid_of(nreq), kFlThreads, 0, s>>>(d_req, nreq, plan, cnt, nreq == 1 ? total_spans : nullptr,
+                                                        h_res);
+    h_tot[0] = h_tot[1] = 0;
+    if (!max_spans) return hipGetLastError();
+    hipError_t e = nreq == 1 ? hipSuccess : launch_store_scan(cnt, nreq, rblock, nullptr, s);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(d_touch, 0, 8, s);
+    if (e != hipSuccess) return e;
+    span_x_kernel<<<grid_of(max_spans), kFlThreads, 0, s>>>(d_req, d_rslot, nreq, plan, cnt, total_spans, v, recs,
+                                                            pcnt, max_spans, d_touch);
+    e = launch_store_scan(pcnt, max_spans, pblock, h_tot, s);
+    if (e != hipSuccess) return e;
+    return hipMemcpyAsync(h_tot + 1, d_touch, 8, hipMemcpyDeviceToHost, s);
+}
+
+hipError_t launch_files_copy_x(const SpanRec *recs, const uint64_t *pcnt, uint64_t max_spans, const ScrubView &v,
+                               const uint64_t *loc, uint64_t arena, StorePiece *pieces, uint64_t *tstart,
+                               uint64_t *block_sums, uint64_t n_pieces, uint64_t max_tiles, hipStream_t s) {
+    if (!n_pieces) return hipSuccess;
+    span_pieces_kernel<<<grid_of(n_pieces), kFlThreads, 0, s>>>(recs, pcnt, max_spans, v, loc, arena, pieces, tstart,
+                                                             n_pieces);
+    const hipError_t e = launch_store_scan(tstart, n_pieces, block_sums, nullptr, s);
+    if (e != hipSuccess) return e;
+    return launch_store_copy(pieces, tstart, n_pieces, max_tiles, block_sums + store_scan_blocks(n_pieces), s);
 }
 
 hipError_t launch_files_distribution(const SpanTable &t, uint64_t m, uint32_t *cnt, uint64_t *firstpos,

@@ -70,6 +70,41 @@ hipError_t launch_files_read(const ReadReq *d_req, uint64_t nreq, uint64_t arena
                              uint64_t *rblock, StorePiece *pieces, uint64_t *tstart, uint64_t *block_sums,
                              uint64_t max_pieces, uint64_t max_tiles, ReadResult *h_res, hipStream_t s);
 
+// ---- reads in the scrubbed state ------------------------------------------------
+// Once the store holds target-kind containers a span's bytes are found through
+// its slot's current container (ScrubView, store.hpp): the same chain with one
+// more level, span -> pieces.  One record per span a request touches.
+struct SpanRec {
+    uint64_t s0;        // the span's first byte in the file
+    uint64_t from, to;  // the part of it the request takes
+    uint64_t dst0;      // destination address of file byte 0: a file byte x goes to dst0 + x
+    uint64_t key0;      // first key taken of a target-kind span; ~0 for a chunk-kind span
+    uint32_t slot;
+    uint32_t pad;
+};
+
+// Steps 1-3: requests -> span ranges (as launch_files_read) -> one SpanRec and
+// piece count per span: a chunk-kind span is one piece, a target-kind span one
+// piece per key, and a range read trims its first and last span by binary
+// search over the per-key offsets inside the container.  d_rslot[r] = device
+// address of request r's slot array.  max_spans is the host-side bound
+// launch_files_read calls max_pieces; recs / pcnt: max_spans; pblock:
+// store_scan_blocks(max_spans) + 1.  h_tot (pinned host): [0] = pieces in all,
+// [1] = target-kind spans touched -- the host reads both before the copy, so
+// the piece scratch is sized exactly and a cleared target is refused before a
+// byte is written.
+hipError_t launch_files_plan_x(const ReadReq *d_req, const uint64_t *d_rslot, uint64_t nreq, const ScrubView &v,
+                               ReadPlan *plan, uint64_t *cnt, uint64_t *rblock, SpanRec *recs, uint64_t *pcnt,
+                               uint64_t *pblock, uint64_t max_spans, ReadResult *h_res,
+                               unsigned long long *d_touch, unsigned long long *h_tot, hipStream_t s);
+
+// Steps 4-6 after the host has read h_tot: the n_pieces pieces, the tile scan
+// and the store's copy.  pcnt is the scan launch_files_plan_x left; pieces /
+// tstart: n_pieces; block_sums: store_scan_blocks(n_pieces) + 1.
+hipError_t launch_files_copy_x(const SpanRec *recs, const uint64_t *pcnt, uint64_t max_spans, const ScrubView &v,
+                               const uint64_t *loc, uint64_t arena, StorePiece *pieces, uint64_t *tstart,
+                               uint64_t *block_sums, uint64_t n_pieces, uint64_t max_tiles, hipStream_t s);
+
 // chunk_count_distribution over spans [0, m), m = n - 1: per distinct slot, in
 // order of first occurrence, {digest, count, off[i + 1] - off[i] of the first
 // occurrence}.  cnt / firstpos: table-sized scratch (only the slots the file

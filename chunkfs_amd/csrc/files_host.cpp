@@ -57,6 +57,14 @@ struct cdc_files {
     uint64_t *d_tstart = nullptr, *d_pblock = nullptr;
     unsigned long long *h_tot = nullptr;  // pinned: [0] appended bytes, [1] distinct digests, [2..3] d_stat's copy
     unsigned long long *d_stat = nullptr;  // [2] append: min(length - 1), spans of length 0
+    // reads in the scrubbed state: per-request slot arrays, per-span records
+    uint64_t xr_cap = 0;
+    uint64_t *h_rslot = nullptr, *d_rslot = nullptr;
+    uint64_t xs_cap = 0;
+    cdc::SpanRec *d_recs = nullptr;
+    uint64_t *d_pcnt = nullptr, *d_xblock = nullptr;
+    unsigned long long *h_xtot = nullptr;  // pinned: [0] pieces, [1] target-kind spans touched
+    unsigned long long *d_touch = nullptr;
 };
 
 struct cdc_fh {
@@ -205,6 +213,13 @@ void release(cdc_files *fs) {
     (void)hipFree(fs->d_pblock);
     (void)hipHostFree(fs->h_tot);
     (void)hipFree(fs->d_stat);
+    (void)hipHostFree(fs->h_rslot);
+    (void)hipFree(fs->d_rslot);
+    (void)hipFree(fs->d_recs);
+    (void)hipFree(fs->d_pcnt);
+    (void)hipFree(fs->d_xblock);
+    (void)hipHostFree(fs->h_xtot);
+    (void)hipFree(fs->d_touch);
     delete fs;
 }
 
@@ -276,8 +291,104 @@ struct HostReq {
     cdc_chunk_t *spans;
 };
 
+int grow_scrubbed(cdc_files *fs, uint64_t nreq, uint64_t spans) {
+    if (!fs->h_xtot) {
+        FL_TRY(hipHostMalloc(&fs->h_xtot, 2 * sizeof(unsigned long long)));
+        FL_TRY(hipMalloc(&fs->d_touch, sizeof(unsigned long long)));
+    }
+    if (fs->xr_cap < nreq) {
+        (void)hipHostFree(fs->h_rslot);
+        (void)hipFree(fs->d_rslot);
+        fs->h_rslot = fs->d_rslot = nullptr;
+        fs->xr_cap = 0;
+        const uint64_t cap = nreq + nreq / 8 + 16;
+        FL_TRY(hipHostMalloc(&fs->h_rslot, cap * 8));
+        FL_TRY(hipMalloc(&fs->d_rslot, cap * 8));
+        fs->xr_cap = cap;
+    }
+    if (fs->xs_cap < spans) {
+        (void)hipFree(fs->d_recs);
+        (void)hipFree(fs->d_pcnt);
+        (void)hipFree(fs->d_xblock);
+        fs->d_recs = nullptr;
+        fs->d_pcnt = fs->d_xblock = nullptr;
+        fs->xs_cap = 0;
+        const uint64_t cap = spans + spans / 8 + 64;
+        FL_TRY(hipMalloc(&fs->d_recs, cap * sizeof(cdc::SpanRec)));
+        FL_TRY(hipMalloc(&fs->d_pcnt, cap * 8));
+        FL_TRY(hipMalloc(&fs->d_xblock, (cdc::store_scan_blocks(cap) + 1) * 8));
+        fs->xs_cap = cap;
+    }
+    return CDC_OK;
+}
+
+// run_reads once the store holds target-kind containers: a span's bytes are
+// found through its slot's current container, and a span yields one piece per
+// key.  The exact piece count is read back before the copy (one more host wait
+// than the unscrubbed path): a sub-chunk may be one byte long, so a bound from
+// the byte count alone would be the byte count.
+int run_reads_scrubbed(cdc_files *fs, const std::vector<HostReq> &reqs, const cdc::ScrubView &sv, bool stale,
+                       void *hip_stream) {
+    const cdc::StoreView v = cdc::store_view(fs->store);
+    FL_TRY(hipSetDevice(v.device));
+    hipStream_t s = stream_of(fs, hip_stream);
+    const uint64_t nreq = reqs.size();
+    int rc = grow_requests(fs, nreq);
+    if (rc) return rc;
+    uint64_t max_spans = 0, max_bytes = 0;
+    for (uint64_t i = 0; i < nreq; ++i) {
+        const HostReq &q = reqs[i];
+        uint64_t bytes = q.f->size < q.cap ? q.f->size : q.cap;
+        if (q.kind != cdc::kReadComplete && q.b < bytes) bytes = q.b;
+        max_spans += q.kind == cdc::kReadComplete ? q.f->n : spans_bound(q.f, bytes);  // span lengths only: as unscrubbed
+        max_bytes += bytes;
+    }
+    if ((rc = grow_scrubbed(fs, nreq, max_spans)) != CDC_OK) return rc;
+    for (uint64_t i = 0; i < nreq; ++i) {
+        const HostReq &q = reqs[i];
+        fs->h_req[i] = cdc::ReadReq{q.f->t.off, q.f->t.loc, q.f->n, q.a, q.b, (uint64_t)(uintptr_t)q.dst, q.cap,
+                                    (uint64_t)(uintptr_t)q.spans, q.kind, 0};
+        fs->h_rslot[i] = (uint64_t)(uintptr_t)q.f->t.slot;
+    }
+    if (stale)  // nothing may be written if the read turns out to need the cleared target: spans go out after the check
+        for (uint64_t i = 0; i < nreq; ++i) fs->h_req[i].spans = 0;
+    FL_TRY(hipMemcpyAsync(fs->d_req, fs->h_req, nreq * sizeof(cdc::ReadReq), hipMemcpyHostToDevice, s));
+    FL_TRY(hipMemcpyAsync(fs->d_rslot, fs->h_rslot, nreq * 8, hipMemcpyHostToDevice, s));
+    FL_TRY(cdc::launch_files_plan_x(fs->d_req, fs->d_rslot, nreq, sv, fs->d_plan, fs->d_rcnt, fs->d_rblock, fs->d_recs,
+                                    fs->d_pcnt, fs->d_xblock, max_spans, fs->h_res, fs->d_touch, fs->h_xtot, s));
+    FL_TRY(hipStreamSynchronize(s));
+    if (stale && fs->h_xtot[1])
+        return fail(CDC_ENOTFOUND, "file layer: the target store was cleared since these chunks were scrubbed");
+    if (stale) {  // every span touched is chunk-kind: plan again, with the span output
+        bool any = false;
+        for (uint64_t i = 0; i < nreq; ++i) any = any || reqs[i].spans;
+        if (any) {
+            for (uint64_t i = 0; i < nreq; ++i) fs->h_req[i].spans = (uint64_t)(uintptr_t)reqs[i].spans;
+            FL_TRY(hipMemcpyAsync(fs->d_req, fs->h_req, nreq * sizeof(cdc::ReadReq), hipMemcpyHostToDevice, s));
+            FL_TRY(cdc::launch_files_plan_x(fs->d_req, fs->d_rslot, nreq, sv, fs->d_plan, fs->d_rcnt, fs->d_rblock,
+                                            fs->d_recs, fs->d_pcnt, fs->d_xblock, max_spans, fs->h_res, fs->d_touch,
+                                            fs->h_xtot, s));
+            FL_TRY(hipStreamSynchronize(s));
+        }
+    }
+    const uint64_t np = fs->h_xtot[0];
+    if (!np) return CDC_OK;
+    if ((rc = grow_pieces(fs, np)) != CDC_OK) return rc;
+    // A piece adds at most two ragged tiles to its whole ones.
+    FL_TRY(cdc::launch_files_copy_x(fs->d_recs, fs->d_pcnt, max_spans, sv, v.loc, (uint64_t)(uintptr_t)v.arena,
+                                    fs->d_pieces, fs->d_tstart, fs->d_pblock, np, max_bytes / cdc::kStoreTile + 2 * np,
+                                    s));
+    FL_TRY(hipStreamSynchronize(s));
+    return CDC_OK;
+}
+
 // Plans and copies every request in one pass; fs->h_res[i] holds the results.
 int run_reads(cdc_files *fs, const std::vector<HostReq> &reqs, void *hip_stream) {
+    {
+        cdc::ScrubView sv;
+        bool stale = false;
+        if (cdc::store_scrub_view(fs->store, &sv, &stale)) return run_reads_scrubbed(fs, reqs, sv, stale, hip_stream);
+    }
     const cdc::StoreView v = cdc::store_view(fs->store);
     FL_TRY(hipSetDevice(v.device));
     hipStream_t s = stream_of(fs, hip_stream);

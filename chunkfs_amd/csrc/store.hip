@@ -23,6 +23,15 @@
 // destination, funnel-shifted in registers); the ragged head and tail slots
 // are byte copies.  No load leaves the aligned 16-byte blocks that hold source
 // bytes, no store touches a byte outside the destination.
+//
+// Scrub stage (the reference's Scrub hook, src/system/scrub.rs, and the
+// DataContainer that is a chunk or a list of target keys, storage.rs:12-21):
+// with a target store attached a slot also has a kind and, for a target, a run
+// of resolved keys {target slot, byte offset inside the container}.  The scrub
+// lists the chunk-kind containers with the scan above, the target's put takes
+// their bytes (COPY) or their re-chunked sub-chunks (RECHUNK) straight from this
+// arena, and a marking kernel writes the key runs; get then expands a digest
+// into one piece per key and feeds the same copy kernel.
 #include "store.hpp"
 
 namespace cdc {
@@ -332,6 +341,190 @@ __global__ __launch_bounds__(kStThreads) void copy_kernel(const StorePiece *__re
     }
 }
 
+// ---- scrub stage -----------------------------------------------------------------
+// A slot holds a container once a chunk has been recorded as its first insert.
+__device__ __forceinline__ bool occupied(const IndexTable &t, uint64_t s) {
+    return t.tag[s] != 0 && t.owner[s] != ~0ull;
+}
+
+__global__ __launch_bounds__(kStThreads) void scrub_flag_kernel(IndexTable t, const uint8_t *__restrict__ kind,
+                                                                int want_kind, uint64_t *val) {
+    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= t.slots) return;
+    val[s] = occupied(t, s) && (want_kind < 0 || kind[s] == want_kind) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(kStThreads) void scrub_list_kernel(IndexTable t, const uint8_t *__restrict__ kind,
+                                                                const uint64_t *__restrict__ loc,
+                                                                const uint64_t *__restrict__ val,
+                                                                cdc_chunk_pod *chunks, uint8_t *digests,
+                                                                uint32_t *slot_of, unsigned long long *bytes) {
+    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t len = 0;
+    if (s < t.slots && occupied(t, s) && kind[s] == 0) {
+        const uint64_t j = val[s];
+        len = t.length[s];
+        chunks[j] = cdc_chunk_pod{loc[s], len};
+        const uint4 *src = reinterpret_cast<const uint4 *>(t.digest + 32 * s);
+        uint4 *dst = reinterpret_cast<uint4 *>(digests + 32 * j);
+        dst[0] = src[0];
+        dst[1] = src[1];
+        slot_of[j] = (uint32_t)s;
+    }
+#pragma unroll
+    for (int k = 1; k < 64; k <<= 1) len += __shfl_xor(len, k);
+    if ((threadIdx.x & 63) == 0 && len) atomicAdd(bytes, (unsigned long long)len);
+}
+
+__global__ __launch_bounds__(kStThreads) void scrub_padsum_kernel(const cdc_chunk_pod *__restrict__ chunks,
+                                                                  uint64_t n, unsigned long long *sum) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t pad = i < n ? (chunks[i].length + (kStoreAlign - 1)) & ~(kStoreAlign - 1) : 0;
+#pragma unroll
+    for (int k = 1; k < 64; k <<= 1) pad += __shfl_xor(pad, k);
+    if ((threadIdx.x & 63) == 0 && pad) atomicAdd(sum, (unsigned long long)pad);
+}
+
+// Thread i < nc turns container i into a target; thread i < n writes key i.
+__global__ __launch_bounds__(kStThreads) void scrub_mark_kernel(ScrubState w, const uint32_t *__restrict__ c_slot,
+                                                                uint64_t nc, const uint64_t *__restrict__ first,
+                                                                const cdc_chunk_pod *__restrict__ sub,
+                                                                const uint32_t *__restrict__ t_slot, uint64_t n,
+                                                                uint64_t key_base) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nc) {
+        const uint32_t s = c_slot[i];
+        const uint64_t f0 = first ? first[i] : i, f1 = first ? first[i + 1] : i + 1;
+        w.kind[s] = 1;
+        w.key_first[s] = key_base + f0;
+        w.key_count[s] = (uint32_t)(f1 - f0);
+    }
+    if (i < n) {
+        w.key_slot[key_base + i] = t_slot[i];
+        w.key_off[key_base + i] = sub ? sub[i].offset : 0;
+    }
+}
+
+__global__ __launch_bounds__(kStThreads) void lookup_x_kernel(IndexTable t, ScrubView v,
+                                                              const uint8_t *__restrict__ digests, uint64_t n,
+                                                              uint32_t *slot_of, uint64_t *cnt, uint64_t *val,
+                                                              unsigned long long *res) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t missing = 0, targets = 0;
+    if (i < n) {
+        const uint8_t *d = digests + 32 * i;
+        const uint2 w = *reinterpret_cast<const uint2 *>(d);
+        const uint64_t key = (((uint64_t)w.y << 32) | w.x) | 1ull;  // index.hip key_of
+        const uint64_t mask = t.slots - 1;
+        uint64_t s = (key >> 1) & mask;
+        uint32_t hit = kNoSlot;
+        for (uint64_t probe = 0; probe < t.slots; ++probe, s = (s + 1) & mask) {
+            const uint64_t cur = t.tag[s];
+            if (cur == 0) break;
+            if (cur == key && same_digest(t.digest + 32 * s, d)) {
+                hit = (uint32_t)s;
+                break;
+            }
+        }
+        slot_of[i] = hit;
+        if (hit == kNoSlot) {
+            missing = 1;
+            cnt[i] = 0;
+            val[i] = 0;
+        } else {
+            targets = v.kind[hit];
+            cnt[i] = targets ? v.key_count[hit] : 1;
+            val[i] = t.length[hit];
+        }
+    }
+#pragma unroll
+    for (int k = 1; k < 64; k <<= 1) {
+        missing += __shfl_xor(missing, k);
+        targets += __shfl_xor(targets, k);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (missing) atomicAdd(&res[0], (unsigned long long)missing);
+        if (targets) atomicAdd(&res[3], (unsigned long long)targets);
+    }
+}
+
+__global__ __launch_bounds__(kStThreads) void pieces_x_kernel(IndexTable t, ScrubView v,
+                                                              const uint64_t *__restrict__ loc, uint64_t arena,
+                                                              const uint32_t *__restrict__ slot_of,
+                                                              const uint64_t *__restrict__ pstart,
+                                                              const uint64_t *__restrict__ off, uint64_t n,
+                                                              uint64_t d_out, StorePiece *pieces, uint64_t *tiles,
+                                                              uint64_t n_pieces) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pieces) return;
+    uint64_t a = 0, b = n;  // last digest i with pstart[i] <= p (digests of no pieces share a start)
+    while (b - a > 1) {
+        const uint64_t mid = (a + b) >> 1;
+        if (pstart[mid] <= p) a = mid;
+        else b = mid;
+    }
+    const uint32_t s = slot_of[a];
+    StorePiece pc;
+    if (v.kind[s]) {
+        const uint64_t k = v.key_first[s] + (p - pstart[a]);
+        const uint32_t ts = v.key_slot[k];
+        pc.src = v.t_arena + v.t_loc[ts];
+        pc.dst = d_out + off[a] + v.key_off[k];
+        pc.len = v.t_length[ts];
+    } else {
+        pc.src = arena + loc[s];
+        pc.dst = d_out + off[a];
+        pc.len = t.length[s];
+    }
+    pieces[p] = pc;
+    tiles[p] = pc.len ? ((pc.dst & (kStoreAlign - 1)) + pc.len + (kStoreTile - 1)) / kStoreTile : 0;
+}
+
+__global__ __launch_bounds__(kStThreads) void spans_x_kernel(IndexTable t, const uint32_t *__restrict__ slot_of,
+                                                             const uint64_t *__restrict__ off, uint64_t n,
+                                                             cdc_chunk_pod *spans) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) spans[i] = cdc_chunk_pod{off[i], t.length[slot_of[i]]};
+}
+
+__global__ __launch_bounds__(kStThreads) void iterate_kernel(IndexTable t, ScrubView v,
+                                                             const uint64_t *__restrict__ val, uint8_t *digests,
+                                                             uint8_t *kinds, uint64_t *lengths, uint64_t *key_first) {
+    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= t.slots || !occupied(t, s)) return;
+    const uint64_t j = val[s];
+    const uint4 *src = reinterpret_cast<const uint4 *>(t.digest + 32 * s);
+    uint4 *dst = reinterpret_cast<uint4 *>(digests + 32 * j);
+    dst[0] = src[0];
+    dst[1] = src[1];
+    const uint8_t k = v.kind ? v.kind[s] : 0;
+    kinds[j] = k;
+    lengths[j] = t.length[s];
+    key_first[j] = k ? v.key_count[s] : 0;
+}
+
+__global__ __launch_bounds__(kStThreads) void key_counts_kernel(IndexTable t, ScrubView v, uint64_t *val) {
+    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= t.slots) return;
+    val[s] = occupied(t, s) && v.kind[s] ? v.key_count[s] : 0;
+}
+
+// One thread per slot copies its container's keys in a loop (6144 x 32 bytes
+// from one lane for a 3 MiB container under 512-byte sub-chunks): enough for
+// storage_iterator, not meant for a hot path.
+__global__ __launch_bounds__(kStThreads) void keys_kernel(IndexTable t, ScrubView v,
+                                                          const uint64_t *__restrict__ val, uint8_t *keys) {
+    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= t.slots || !occupied(t, s) || !v.kind[s]) return;
+    const uint64_t k0 = v.key_first[s], at = val[s];
+    for (uint32_t k = 0; k < v.key_count[s]; ++k) {
+        const uint4 *src = reinterpret_cast<const uint4 *>(v.t_digest + 32ull * v.key_slot[k0 + k]);
+        uint4 *dst = reinterpret_cast<uint4 *>(keys + 32 * (at + k));
+        dst[0] = src[0];
+        dst[1] = src[1];
+    }
+}
+
 constexpr uint64_t kMaxCopyBlocks = 1u << 20;  // waves past this stride over the tiles
 
 inline unsigned grid_of(uint64_t n) { return (unsigned)((n + kStThreads - 1) / kStThreads); }
@@ -407,6 +600,81 @@ hipError_t launch_store_gather(const StorePiece *pieces, const uint64_t *tstart,
     if (tiles) copy_kernel<<<copy_grid(tiles), kStThreads, 0, s>>>(pieces, tstart, n, tiles, nullptr);
     if (d_spans)
         spans_kernel<<<grid_of(n), kStThreads, 0, s>>>(pieces, n, d_out, reinterpret_cast<cdc_chunk_pod *>(d_spans));
+    return hipGetLastError();
+}
+
+hipError_t launch_scrub_flag(const IndexTable &t, const uint8_t *kind, int want_kind, uint64_t *val,
+                             uint64_t *block_sums, unsigned long long *d_total, hipStream_t s) {
+    scrub_flag_kernel<<<grid_of(t.slots), kStThreads, 0, s>>>(t, kind, want_kind, val);
+    scan_exclusive(val, t.slots, block_sums, d_total, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_scrub_list(const IndexTable &t, const uint8_t *kind, const uint64_t *loc, const uint64_t *val,
+                             void *d_chunks, uint8_t *d_digests, uint32_t *d_slot, unsigned long long *d_bytes,
+                             hipStream_t s) {
+    scrub_list_kernel<<<grid_of(t.slots), kStThreads, 0, s>>>(t, kind, loc, val,
+                                                              reinterpret_cast<cdc_chunk_pod *>(d_chunks), d_digests,
+                                                              d_slot, d_bytes);
+    return hipGetLastError();
+}
+
+hipError_t launch_scrub_padsum(const void *d_chunks, uint64_t n, unsigned long long *d_sum, hipStream_t s) {
+    if (!n) return hipSuccess;
+    scrub_padsum_kernel<<<grid_of(n), kStThreads, 0, s>>>(reinterpret_cast<const cdc_chunk_pod *>(d_chunks), n, d_sum);
+    return hipGetLastError();
+}
+
+hipError_t launch_scrub_mark(const ScrubState &w, const uint32_t *c_slot, uint64_t nc, const uint64_t *d_first,
+                             const void *d_sub, const uint32_t *t_slot, uint64_t n, uint64_t key_base,
+                             hipStream_t s) {
+    const uint64_t m = nc > n ? nc : n;
+    if (!m) return hipSuccess;
+    scrub_mark_kernel<<<grid_of(m), kStThreads, 0, s>>>(w, c_slot, nc, d_first,
+                                                        reinterpret_cast<const cdc_chunk_pod *>(d_sub), t_slot, n,
+                                                        key_base);
+    return hipGetLastError();
+}
+
+hipError_t launch_store_lookup_x(const IndexTable &t, const ScrubView &v, const uint8_t *d_digests, uint64_t n,
+                                 uint32_t *slot_of, uint64_t *cnt, uint64_t *val, unsigned long long *d_res,
+                                 hipStream_t s) {
+    if (!n) return hipSuccess;
+    lookup_x_kernel<<<grid_of(n), kStThreads, 0, s>>>(t, v, d_digests, n, slot_of, cnt, val, d_res);
+    return hipGetLastError();
+}
+
+hipError_t launch_store_pieces_x(const IndexTable &t, const ScrubView &v, const uint64_t *loc, const uint8_t *arena,
+                                 const uint32_t *slot_of, const uint64_t *pstart, const uint64_t *off, uint64_t n,
+                                 uint64_t d_out, StorePiece *pieces, uint64_t *tiles, uint64_t n_pieces,
+                                 hipStream_t s) {
+    if (!n || !n_pieces) return hipSuccess;
+    pieces_x_kernel<<<grid_of(n_pieces), kStThreads, 0, s>>>(t, v, loc, (uint64_t)(uintptr_t)arena, slot_of, pstart,
+                                                             off, n, d_out, pieces, tiles, n_pieces);
+    return hipGetLastError();
+}
+
+hipError_t launch_store_spans_x(const IndexTable &t, const uint32_t *slot_of, const uint64_t *off, uint64_t n,
+                                void *d_spans, hipStream_t s) {
+    if (!n) return hipSuccess;
+    spans_x_kernel<<<grid_of(n), kStThreads, 0, s>>>(t, slot_of, off, n, reinterpret_cast<cdc_chunk_pod *>(d_spans));
+    return hipGetLastError();
+}
+
+hipError_t launch_store_iterate(const IndexTable &t, const ScrubView &v, const uint64_t *val, uint8_t *d_digests,
+                                uint8_t *d_kinds, uint64_t *d_lengths, uint64_t *d_key_first, hipStream_t s) {
+    iterate_kernel<<<grid_of(t.slots), kStThreads, 0, s>>>(t, v, val, d_digests, d_kinds, d_lengths, d_key_first);
+    return hipGetLastError();
+}
+
+hipError_t launch_store_key_counts(const IndexTable &t, const ScrubView &v, uint64_t *val, hipStream_t s) {
+    key_counts_kernel<<<grid_of(t.slots), kStThreads, 0, s>>>(t, v, val);
+    return hipGetLastError();
+}
+
+hipError_t launch_store_keys(const IndexTable &t, const ScrubView &v, const uint64_t *val, uint8_t *d_keys,
+                             hipStream_t s) {
+    keys_kernel<<<grid_of(t.slots), kStThreads, 0, s>>>(t, v, val, d_keys);
     return hipGetLastError();
 }
 

@@ -69,4 +69,88 @@ hipError_t launch_store_scan(uint64_t *v, uint64_t n, uint64_t *block_sums, unsi
 hipError_t launch_store_copy(const StorePiece *pieces, const uint64_t *tstart, uint64_t n, uint64_t max_tiles,
                              const uint64_t *d_total, hipStream_t s);
 
+// ---- scrub stage ---------------------------------------------------------------
+// The base store's view of its containers once a target store is attached
+// (DataContainer, src/system/storage.rs:12-21): kind[slot] = 0 for a chunk, 1
+// for a list of target keys; a target-kind slot owns the run [key_first,
+// key_first + key_count) of the key arrays.  Keys are stored resolved: the
+// target store's slot, and the byte offset of the key's value inside the
+// container it restores.  t_* are the target store's arrays.
+struct ScrubView {
+    const uint8_t *kind;
+    const uint64_t *key_first;
+    const uint32_t *key_count;
+    const uint32_t *key_slot;
+    const uint64_t *key_off;
+    const uint64_t *t_length;
+    const uint64_t *t_loc;
+    const uint8_t *t_digest;
+    uint64_t t_arena;
+};
+
+// The writable side of the same arrays (the marking kernel).
+struct ScrubState {
+    uint8_t *kind;
+    uint64_t *key_first;
+    uint32_t *key_count;
+    uint32_t *key_slot;
+    uint64_t *key_off;
+};
+
+// scrub, step 1: val[s] = 1 for the occupied chunk-kind slots (`want_kind` 0)
+// or for every occupied slot (`want_kind` < 0), scanned in place; *d_total =
+// how many.  val: slots u64, block_sums: store_scan_blocks(slots) + 1.
+hipError_t launch_scrub_flag(const IndexTable &t, const uint8_t *kind, int want_kind, uint64_t *val,
+                             uint64_t *block_sums, unsigned long long *d_total, hipStream_t s);
+
+// scrub, step 1b: the container list in slot order from the scanned flags:
+// chunks[j] = {arena offset, length}, digests[j], slot_of[j]; *d_bytes += the
+// lengths.
+hipError_t launch_scrub_list(const IndexTable &t, const uint8_t *kind, const uint64_t *loc, const uint64_t *val,
+                             void *d_chunks, uint8_t *d_digests, uint32_t *d_slot, unsigned long long *d_bytes,
+                             hipStream_t s);
+
+// RECHUNK planning: *d_sum += sum of round_up(length, 16) over n chunks.
+hipError_t launch_scrub_padsum(const void *d_chunks, uint64_t n, unsigned long long *d_sum, hipStream_t s);
+
+// scrub, step 4: containers [0, nc) of a group (slots c_slot) become
+// target-kind; container j owns keys [first[j], first[j + 1]) of the group's n
+// keys (d_first NULL: one key each, key j), written from key_base on.  Key i
+// is the target slot t_slot[i] at offset d_sub[i].offset inside its container
+// (d_sub NULL: 0).
+hipError_t launch_scrub_mark(const ScrubState &w, const uint32_t *c_slot, uint64_t nc, const uint64_t *d_first,
+                             const void *d_sub, const uint32_t *t_slot, uint64_t n, uint64_t key_base,
+                             hipStream_t s);
+
+// get on a store with target-kind containers, step 1: slot_of[i] (0xFFFFFFFF
+// when absent), cnt[i] = pieces the digest expands into (1 for a chunk, the key
+// count for a target), val[i] = the length it restores to.  d_res[0] += digests
+// absent, d_res[3] += target-kind hits.
+hipError_t launch_store_lookup_x(const IndexTable &t, const ScrubView &v, const uint8_t *d_digests, uint64_t n,
+                                 uint32_t *slot_of, uint64_t *cnt, uint64_t *val, unsigned long long *d_res,
+                                 hipStream_t s);
+
+// step 2, after both scans (cnt -> first piece, val -> offset in d_out): the
+// n_pieces pieces and their tile counts.
+hipError_t launch_store_pieces_x(const IndexTable &t, const ScrubView &v, const uint64_t *loc, const uint8_t *arena,
+                                 const uint32_t *slot_of, const uint64_t *pstart, const uint64_t *off, uint64_t n,
+                                 uint64_t d_out, StorePiece *pieces, uint64_t *tiles, uint64_t n_pieces,
+                                 hipStream_t s);
+
+// spans[i] = {off[i], length of the digest's container}.
+hipError_t launch_store_spans_x(const IndexTable &t, const uint32_t *slot_of, const uint64_t *off, uint64_t n,
+                                void *d_spans, hipStream_t s);
+
+// storage_iterator: per occupied slot, at its rank val[s] (the scanned flags):
+// digest, kind, length, and its key count into key_first[rank].
+hipError_t launch_store_iterate(const IndexTable &t, const ScrubView &v, const uint64_t *val, uint8_t *d_digests,
+                                uint8_t *d_kinds, uint64_t *d_lengths, uint64_t *d_key_first, hipStream_t s);
+
+// val[s] = keys of slot s (0 unless target-kind), for the scan that places them.
+hipError_t launch_store_key_counts(const IndexTable &t, const ScrubView &v, uint64_t *val, hipStream_t s);
+// The 32-byte keys (the target store's digests) of every target-kind slot, from
+// d_keys + 32 * val[s] on.
+hipError_t launch_store_keys(const IndexTable &t, const ScrubView &v, const uint64_t *val, uint8_t *d_keys,
+                             hipStream_t s);
+
 }  // namespace cdc

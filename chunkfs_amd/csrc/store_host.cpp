@@ -1,7 +1,13 @@
 // store_host.cpp -- C ABI of the device chunk store (include/chunkfs_amd.h,
 // "Chunk store"): the reference's key -> data Database (src/system/database.rs:
 // 10-36, 74-87), ChunkStorage::retrieve (src/system/storage.rs:141-157) and
-// FileSystem::read_file_complete (src/system/mod.rs:149-160).
+// FileSystem::read_file_complete (src/system/mod.rs:149-160); and of the scrub
+// stage ("Scrub stage"): the target map as a second store, the Scrub hook
+// (src/system/scrub.rs), DataContainer kinds with resolved key runs
+// (storage.rs:12-21), new_with_scrubber / scrub / iterator (storage.rs:165-235).
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -36,6 +42,18 @@ struct cdc_store {
     hipStream_t stream = nullptr;
     cdc_index_stats_t st{};
     uint64_t epoch = 0;            // bumped by reset: locations resolved before it are stale
+    // Scrub stage (allocated by cdc_store_set_target): the target map and this
+    // store's containers that have become lists of its keys.
+    cdc_store *target = nullptr;   // not owned
+    uint64_t target_epoch = 0;     // the target's epoch the keys were resolved under
+    cdc::ScrubState sc{};          // kind / key_first / key_count: [slots]; key_slot / key_off: [key_cap]
+    uint64_t key_cap = 0, keys_used = 0;
+    uint64_t target_containers = 0;
+    uint64_t scrubbed_bytes = 0;   // unique bytes whose containers are target-kind now
+    // get through targets: per-piece scratch
+    uint64_t x_cap = 0;
+    cdc::StorePiece *x_pieces = nullptr;
+    uint64_t *x_tstart = nullptr, *x_block = nullptr;
 };
 
 namespace {
@@ -53,10 +71,15 @@ int reset(cdc_store *st) {
     ST_TRY(hipSetDevice(st->device));
     ST_TRY(hipMemsetAsync(st->t.tag, 0, st->t.slots * 8, st->stream));
     ST_TRY(hipMemsetAsync(st->t.owner, 0xFF, st->t.slots * 8, st->stream));
+    if (st->sc.kind) ST_TRY(hipMemsetAsync(st->sc.kind, 0, st->t.slots, st->stream));
     ST_TRY(hipStreamSynchronize(st->stream));
     st->st = cdc_index_stats_t{};
     st->arena_used = 0;
     ++st->epoch;
+    // The containers and their keys are gone; the attachment stays and follows
+    // the target as it is now.
+    st->keys_used = st->target_containers = st->scrubbed_bytes = 0;
+    if (st->target) st->target_epoch = st->target->epoch;
     return CDC_OK;
 }
 
@@ -85,6 +108,14 @@ void release(cdc_store *st) {
     (void)hipFree(st->d_acc);
     (void)hipFree(st->d_pending);
     (void)hipFree(st->d_streams);
+    (void)hipFree(st->sc.kind);
+    (void)hipFree(st->sc.key_first);
+    (void)hipFree(st->sc.key_count);
+    (void)hipFree(st->sc.key_slot);
+    (void)hipFree(st->sc.key_off);
+    (void)hipFree(st->x_pieces);
+    (void)hipFree(st->x_tstart);
+    (void)hipFree(st->x_block);
     free_scratch(st);
     if (st->stream) (void)hipStreamDestroy(st->stream);
     delete st;
@@ -219,9 +250,368 @@ int64_t put(cdc_store *st, size_t n_streams, const uint8_t *const *d_streams, co
     return (int64_t)res[0];
 }
 
+// ---- scrub stage -------------------------------------------------------------------
+// Device memory of one call, freed when the call returns.
+struct Scratch {
+    std::vector<void *> ptrs;
+    ~Scratch() {
+        for (void *p : ptrs) (void)hipFree(p);
+    }
+    template <typename T>
+    hipError_t alloc(T **out, uint64_t count) {
+        void *p = nullptr;
+        const hipError_t e = hipMalloc(&p, (count ? count : 1) * sizeof(T));
+        if (e == hipSuccess) ptrs.push_back(p);
+        *out = static_cast<T *>(p);
+        return e;
+    }
+};
+
+cdc::ScrubView scrub_view(const cdc_store *st) {
+    const cdc_store *t = st->target;
+    return cdc::ScrubView{st->sc.kind, st->sc.key_first, st->sc.key_count, st->sc.key_slot, st->sc.key_off,
+                          t ? t->t.length : nullptr, t ? t->loc : nullptr, t ? t->t.digest : nullptr,
+                          t ? (uint64_t)(uintptr_t)t->arena : 0};
+}
+
+// The keys were resolved in a target that has been cleared since.
+bool target_stale(const cdc_store *st) {
+    return st->target && st->target_containers && st->target->epoch != st->target_epoch;
+}
+
+// Room for `need` keys; the run arrays keep their contents.
+int reserve_keys(cdc_store *st, uint64_t need, hipStream_t s) {
+    if (need <= st->key_cap) return CDC_OK;
+    uint64_t cap = st->key_cap ? st->key_cap : 1024;
+    while (cap < need) cap *= 2;
+    uint32_t *slot = nullptr;
+    uint64_t *off = nullptr;
+    hipError_t e = hipMalloc(&slot, cap * 4);
+    if (e == hipSuccess) e = hipMalloc(&off, cap * 8);
+    if (e == hipSuccess && st->keys_used) {
+        e = hipMemcpyAsync(slot, st->sc.key_slot, st->keys_used * 4, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(off, st->sc.key_off, st->keys_used * 8, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    if (e != hipSuccess) {
+        (void)hipFree(slot);
+        (void)hipFree(off);
+        cdc::set_error(std::string("chunk store scrub: key array growth: ") + hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE;
+    }
+    (void)hipFree(st->sc.key_slot);
+    (void)hipFree(st->sc.key_off);
+    st->sc.key_slot = slot;
+    st->sc.key_off = off;
+    st->key_cap = cap;
+    return CDC_OK;
+}
+
+// Containers and bytes of one RECHUNK group: CHUNKFS_AMD_SCRUB_GROUP=containers[,bytes].
+void scrub_group_limits(uint64_t *containers, uint64_t *bytes) {
+    *containers = 1u << 20;  // measured on a 1 GiB store (DESIGN.md "Scrub stage"): fewer, larger groups win,
+    *bytes = 1ull << 30;     // and a store that fits one group is chunked once instead of twice
+    if (const char *v = std::getenv("CHUNKFS_AMD_SCRUB_GROUP")) {
+        unsigned long long a = 0, b = 0;
+        const int got = std::sscanf(v, "%llu,%llu", &a, &b);
+        if (got >= 1 && a >= 1) *containers = a;
+        if (got >= 2 && b >= 1) *bytes = b;
+    }
+}
+
+int set_target(cdc_store *st, cdc_store *target) {
+    if (!st || !target) {
+        cdc::set_error("cdc_store_set_target: NULL store");
+        return CDC_EINVAL;
+    }
+    if (st == target) {
+        cdc::set_error("cdc_store_set_target: a store cannot be its own target");
+        return CDC_EINVAL;
+    }
+    if (st->device != target->device) {
+        cdc::set_error("cdc_store_set_target: the two stores are on different devices");
+        return CDC_EINVAL;
+    }
+    if (target->target) {
+        cdc::set_error("cdc_store_set_target: the target store has a target itself");
+        return CDC_EINVAL;
+    }
+    if (st->target_containers) {
+        cdc::set_error("cdc_store_set_target: the store holds containers that refer to its present target");
+        return CDC_EINVAL;
+    }
+    ST_TRY(hipSetDevice(st->device));
+    if (!st->sc.kind) {
+        cdc::ScrubState sc{};
+        hipError_t e = hipMalloc(&sc.kind, st->t.slots);
+        if (e == hipSuccess) e = hipMalloc(&sc.key_first, st->t.slots * 8);
+        if (e == hipSuccess) e = hipMalloc(&sc.key_count, st->t.slots * 4);
+        if (e == hipSuccess) e = hipMemsetAsync(sc.kind, 0, st->t.slots, st->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(st->stream);
+        if (e != hipSuccess) {
+            (void)hipFree(sc.kind);
+            (void)hipFree(sc.key_first);
+            (void)hipFree(sc.key_count);
+            cdc::set_error(std::string("cdc_store_set_target: ") + hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE;
+        }
+        st->sc = sc;
+    }
+    st->target = target;
+    st->target_epoch = target->epoch;
+    return CDC_OK;
+}
+
+int scrub(cdc_store *st, int scrubber, cdc_handle_t *chunker, cdc_scrub_measurements_t *out, void *hip_stream) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!st || !out) {
+        cdc::set_error("cdc_store_scrub: NULL argument");
+        return CDC_EINVAL;
+    }
+    if (!st->target) {
+        cdc::set_error("cdc_store_scrub: no target store attached (this store was created without a scrubber)");
+        return CDC_EINVAL;
+    }
+    if (scrubber != CDC_SCRUB_DUMB && scrubber != CDC_SCRUB_COPY && scrubber != CDC_SCRUB_RECHUNK) {
+        cdc::set_error("cdc_store_scrub: unknown scrubber");
+        return CDC_EINVAL;
+    }
+    if (scrubber == CDC_SCRUB_RECHUNK && (!chunker || cdc::handle_device(chunker) != st->device)) {
+        cdc::set_error("cdc_store_scrub: RECHUNK needs a chunker on the store's device");
+        return CDC_EINVAL;
+    }
+    *out = cdc_scrub_measurements_t{0, 0.0, 0};
+    if (scrubber == CDC_SCRUB_DUMB) return CDC_OK;  // scrub.rs:116-129
+    cdc_store *tg = st->target;
+    if (tg->epoch != st->target_epoch) {
+        if (st->target_containers) {
+            cdc::set_error("chunk store scrub: the target store was cleared; clear this store too");
+            return CDC_ENOTFOUND;
+        }
+        st->target_epoch = tg->epoch;
+    }
+    ST_TRY(hipSetDevice(st->device));
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : st->stream;
+    auto finish = [&](uint64_t processed) {
+        out->processed_data = processed;
+        out->running_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return CDC_OK;
+    };
+    // No chunk-kind container (an empty store, or nothing written since the last
+    // scrub): nothing to list, and no kernel is launched over zero items.
+    if (st->st.unique_chunks == st->target_containers) return finish(0);
+
+    // 1. The chunk-kind containers, in slot order.
+    Scratch mem;
+    const uint64_t slots = st->t.slots;
+    uint64_t *val = nullptr, *block = nullptr;
+    ST_TRY(mem.alloc(&val, slots));
+    ST_TRY(mem.alloc(&block, cdc::store_scan_blocks(slots) + 1));
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(st->d_acc) + 8;
+    ST_TRY(hipMemsetAsync(acc, 0, 4 * 8, s));
+    ST_TRY(cdc::launch_scrub_flag(st->t, st->sc.kind, 0, val, block, acc, s));
+    uint64_t nc = 0;
+    ST_TRY(hipMemcpyAsync(&nc, acc, 8, hipMemcpyDeviceToHost, s));
+    ST_TRY(hipStreamSynchronize(s));
+    if (nc == 0) return finish(0);
+    cdc_chunk_t *c_chunks = nullptr;
+    uint8_t *c_dig = nullptr;
+    uint32_t *c_slot = nullptr;
+    ST_TRY(mem.alloc(&c_chunks, nc));
+    ST_TRY(mem.alloc(&c_dig, nc * 32));
+    ST_TRY(mem.alloc(&c_slot, nc));
+    ST_TRY(cdc::launch_scrub_list(st->t, st->sc.kind, st->loc, val, c_chunks, c_dig, c_slot, acc + 1, s));
+    uint64_t processed = 0;
+    ST_TRY(hipMemcpyAsync(&processed, acc + 1, 8, hipMemcpyDeviceToHost, s));
+    ST_TRY(hipStreamSynchronize(s));
+
+    auto converted = [&](uint64_t containers, uint64_t bytes, uint64_t keys) {
+        st->target_containers += containers;
+        st->scrubbed_bytes += bytes;
+        st->keys_used += keys;
+    };
+
+    if (scrubber == CDC_SCRUB_COPY) {
+        // 2. scrub.rs:85-114: target.insert(hash, chunk) with the base arena as
+        // the source -- the digest is the key, nothing is hashed again.  The
+        // put's own precheck is the planning pass: it refuses before it writes.
+        int rc = reserve_keys(st, st->keys_used + nc, s);
+        if (rc) return rc;
+        const uint64_t lens[1] = {st->arena_used}, first[2] = {0, nc};
+        const uint8_t *streams[1] = {st->arena};
+        const int64_t got = put(tg, 1, streams, lens, first, c_chunks, c_dig, nullptr, s);
+        if (got < 0) return (int)got;
+        ST_TRY(cdc::launch_scrub_mark(st->sc, c_slot, nc, nullptr, nullptr, tg->d_slot, nc, st->keys_used, s));
+        ST_TRY(hipStreamSynchronize(s));
+        converted(nc, processed, nc);
+        st->arena_used = 0;  // every chunk container was converted: no byte of the arena is live
+        return finish(processed);
+    }
+
+    // 3. RECHUNK: every container is one stream of a batch; groups bound the scratch.
+    std::vector<cdc_chunk_t> h_c(nc);
+    ST_TRY(hipMemcpyAsync(h_c.data(), c_chunks, nc * sizeof(cdc_chunk_t), hipMemcpyDeviceToHost, s));
+    ST_TRY(hipStreamSynchronize(s));
+    uint64_t g_containers, g_bytes;
+    scrub_group_limits(&g_containers, &g_bytes);
+    std::vector<uint64_t> gstart{0};  // group g = containers [gstart[g], gstart[g + 1])
+    {
+        uint64_t cnt = 0, bytes = 0;
+        for (uint64_t j = 0; j < nc; ++j) {
+            if (cnt && (cnt >= g_containers || bytes + h_c[j].length > g_bytes)) {
+                gstart.push_back(j);
+                cnt = bytes = 0;
+            }
+            ++cnt;
+            bytes += h_c[j].length;
+        }
+        gstart.push_back(nc);
+    }
+    const uint64_t groups = gstart.size() - 1;
+    std::vector<const uint8_t *> ptrs(nc);
+    std::vector<uint64_t> lens(nc);
+    uint64_t sub_cap = 0, max_group = 0;
+    for (uint64_t j = 0; j < nc; ++j) {
+        ptrs[j] = st->arena + h_c[j].offset;  // 16-byte aligned by the store's layout
+        lens[j] = h_c[j].length;
+    }
+    for (uint64_t g = 0; g < groups; ++g) {
+        const uint64_t a = gstart[g], ng = gstart[g + 1] - a;
+        const uint64_t cap = cdc_batch_max_chunks(chunker, ng, &lens[a]);
+        sub_cap = cap > sub_cap ? cap : sub_cap;
+        max_group = ng > max_group ? ng : max_group;
+    }
+    cdc_chunk_t *d_sub = nullptr;
+    uint8_t *d_dig = nullptr;
+    uint64_t *d_first = nullptr;
+    ST_TRY(mem.alloc(&d_sub, sub_cap));
+    ST_TRY(mem.alloc(&d_dig, sub_cap * 32));
+    ST_TRY(mem.alloc(&d_first, max_group + 1));
+    std::vector<uint64_t> first(max_group + 1);
+    auto chunk_group = [&](uint64_t g) -> int64_t {
+        const uint64_t a = gstart[g], ng = gstart[g + 1] - a;
+        return cdc_chunk_batch_device(chunker, ng, &ptrs[a], &lens[a], d_sub, sub_cap, first.data(), s);
+    };
+
+    // The planning pass: key count and padded bytes "as if every key were new",
+    // before the target or this store is touched.  One group needs none: the
+    // put's own precheck refuses before it writes, and the lists are kept.
+    if (groups > 1) {
+        uint64_t keys = 0;
+        ST_TRY(hipMemsetAsync(acc + 2, 0, 8, s));
+        for (uint64_t g = 0; g < groups; ++g) {
+            const int64_t n = chunk_group(g);
+            if (n < 0) return (int)n;
+            keys += (uint64_t)n;
+            ST_TRY(cdc::launch_scrub_padsum(d_sub, (uint64_t)n, acc + 2, s));
+        }
+        uint64_t padded = 0;
+        ST_TRY(hipMemcpyAsync(&padded, acc + 2, 8, hipMemcpyDeviceToHost, s));
+        ST_TRY(hipStreamSynchronize(s));
+        if (tg->st.unique_chunks + keys > tg->capacity) {
+            cdc::set_error("chunk store scrub: the target's max_chunks is too small for the sub-chunks");
+            return CDC_ENOMEM;
+        }
+        if (padded > tg->arena_capacity - tg->arena_used) {
+            cdc::set_error("chunk store scrub: the target's arena is too small for the sub-chunks");
+            return CDC_ENOMEM;
+        }
+        const int rc = reserve_keys(st, st->keys_used + keys, s);
+        if (rc) return rc;
+    }
+    uint64_t done_bytes = 0;
+    for (uint64_t g = 0; g < groups; ++g) {
+        const uint64_t a = gstart[g], ng = gstart[g + 1] - a;
+        const int64_t n = chunk_group(g);
+        if (n < 0) return (int)n;
+        int rc = cdc_sha256_batch_device(chunker, ng, &ptrs[a], first.data(), d_sub, d_dig, s);
+        if (rc) return rc;
+        if (groups == 1 && (rc = reserve_keys(st, st->keys_used + (uint64_t)n, s)) != CDC_OK) return rc;
+        const int64_t got = put(tg, ng, &ptrs[a], &lens[a], first.data(), d_sub, d_dig, nullptr, s);
+        if (got < 0) return (int)got;  // one group: nothing was touched; later groups: the index's own errors only
+        ST_TRY(hipMemcpyAsync(d_first, first.data(), (ng + 1) * 8, hipMemcpyHostToDevice, s));
+        ST_TRY(cdc::launch_scrub_mark(st->sc, c_slot + a, ng, d_first, d_sub, tg->d_slot, (uint64_t)n, st->keys_used, s));
+        ST_TRY(hipStreamSynchronize(s));
+        uint64_t bytes = 0;
+        for (uint64_t j = a; j < a + ng; ++j) bytes += lens[j];
+        converted(ng, bytes, (uint64_t)n);
+        done_bytes += bytes;
+    }
+    st->arena_used = 0;
+    return finish(done_bytes);
+}
+
+// Flags over the slots -> ranks; returns the scratch through mem.
+int rank_slots(cdc_store *st, Scratch &mem, int want_kind, uint64_t **val, uint64_t *total, hipStream_t s) {
+    uint64_t *block = nullptr;
+    ST_TRY(mem.alloc(val, st->t.slots));
+    ST_TRY(mem.alloc(&block, cdc::store_scan_blocks(st->t.slots) + 1));
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(st->d_acc) + 8;
+    ST_TRY(cdc::launch_scrub_flag(st->t, st->sc.kind, want_kind, *val, block, acc, s));
+    ST_TRY(hipMemcpyAsync(total, acc, 8, hipMemcpyDeviceToHost, s));
+    ST_TRY(hipStreamSynchronize(s));
+    return CDC_OK;
+}
+
+// cdc_store_get_device once target-kind containers exist: a digest expands
+// into its keys' pieces.
+int64_t get_expanded(cdc_store *st, const uint8_t *d_digests, size_t n, uint8_t *d_out, size_t out_cap,
+                     cdc_chunk_t *d_spans, hipStream_t s) {
+    const cdc::ScrubView v = scrub_view(st);
+    unsigned long long *res_d = reinterpret_cast<unsigned long long *>(st->d_acc) + 8;
+    ST_TRY(hipMemsetAsync(res_d, 0, 4 * 8, s));
+    ST_TRY(cdc::launch_store_lookup_x(st->t, v, d_digests, n, st->d_slot, st->d_tstart, st->d_val, res_d, s));
+    ST_TRY(cdc::launch_store_scan(st->d_tstart, n, st->d_block, res_d + 2, s));  // first piece of each digest
+    ST_TRY(cdc::launch_store_scan(st->d_val, n, st->d_block, res_d + 1, s));     // its offset in d_out
+    uint64_t res[4];  // digests absent, total bytes, total pieces, target-kind hits
+    ST_TRY(hipMemcpyAsync(res, res_d, sizeof res, hipMemcpyDeviceToHost, s));
+    ST_TRY(hipStreamSynchronize(s));
+    if (res[0]) {
+        cdc::set_error("chunk store get: " + std::to_string(res[0]) + " digest(s) not found");
+        return CDC_ENOTFOUND;
+    }
+    if (res[3] && target_stale(st)) {
+        cdc::set_error("chunk store get: the target store was cleared since these containers were scrubbed");
+        return CDC_ENOTFOUND;
+    }
+    if (res[1] > out_cap) return (int64_t)res[1];
+    const uint64_t np = res[2];
+    if (st->x_cap < np) {
+        (void)hipFree(st->x_pieces);
+        (void)hipFree(st->x_tstart);
+        (void)hipFree(st->x_block);
+        st->x_pieces = nullptr;
+        st->x_tstart = st->x_block = nullptr;
+        st->x_cap = 0;
+        const uint64_t cap = np + np / 8 + 64;
+        ST_TRY(hipMalloc(&st->x_pieces, cap * sizeof(cdc::StorePiece)));
+        ST_TRY(hipMalloc(&st->x_tstart, cap * 8));
+        ST_TRY(hipMalloc(&st->x_block, (cdc::store_scan_blocks(cap) + 1) * 8));
+        st->x_cap = cap;
+    }
+    if (np) {
+        ST_TRY(cdc::launch_store_pieces_x(st->t, v, st->loc, st->arena, st->d_slot, st->d_tstart, st->d_val, n,
+                                          (uint64_t)(uintptr_t)d_out, st->x_pieces, st->x_tstart, np, s));
+        ST_TRY(cdc::launch_store_scan(st->x_tstart, np, st->x_block, nullptr, s));
+        // A piece adds at most two ragged tiles to its whole ones; the exact total is read on the device.
+        ST_TRY(cdc::launch_store_copy(st->x_pieces, st->x_tstart, np, res[1] / cdc::kStoreTile + 2 * np,
+                                      st->x_block + cdc::store_scan_blocks(np), s));
+    }
+    if (d_spans) ST_TRY(cdc::launch_store_spans_x(st->t, st->d_slot, st->d_val, n, d_spans, s));
+    ST_TRY(hipStreamSynchronize(s));
+    return (int64_t)res[1];
+}
+
 }  // namespace
 
 namespace cdc {
+
+bool store_scrub_view(const cdc_store *st, ScrubView *view, bool *stale) {
+    if (!st->target || !st->target_containers) return false;
+    *view = scrub_view(st);
+    *stale = target_stale(st);
+    return true;
+}
 
 StoreView store_view(const cdc_store *st) {
     return StoreView{st->device, st->stream, st->epoch, st->t.slots, st->t.length, st->loc, st->arena, st->d_slot};
@@ -320,6 +710,7 @@ int64_t cdc_store_get_device(cdc_store_t *st, const uint8_t *d_digests, size_t n
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : st->stream;
     const int rc = grow(st, n);
     if (rc) return rc;
+    if (st->target_containers) return get_expanded(st, d_digests, n, d_out, out_cap, d_spans, s);
     unsigned long long *res_d = reinterpret_cast<unsigned long long *>(st->d_acc) + 8;
     ST_TRY(hipMemsetAsync(res_d, 0, 3 * 8, s));
     ST_TRY(cdc::launch_store_lookup(st->t, st->loc, st->arena, d_digests, n, st->d_pieces, nullptr, res_d, s));
@@ -360,6 +751,86 @@ int64_t cdc_store_contains_device(cdc_store_t *st, const uint8_t *d_digests, siz
     ST_TRY(hipMemcpyAsync(&missing, res_d, 8, hipMemcpyDeviceToHost, s));
     ST_TRY(hipStreamSynchronize(s));
     return (int64_t)(n - missing);
+}
+
+int cdc_store_set_target(cdc_store_t *base, cdc_store_t *target) { return set_target(base, target); }
+
+int cdc_store_scrub(cdc_store_t *base, int scrubber, cdc_handle_t *chunker, cdc_scrub_measurements_t *out,
+                    void *hip_stream) {
+    return scrub(base, scrubber, chunker, out, hip_stream);
+}
+
+int cdc_store_scrub_stats(const cdc_store_t *st, cdc_scrub_stats_t *out) {
+    if (!st || !out) {
+        cdc::set_error("NULL argument");
+        return CDC_EINVAL;
+    }
+    out->cdc_bytes = st->st.unique_bytes - st->scrubbed_bytes;
+    out->chunk_containers = st->st.unique_chunks - st->target_containers;
+    out->target_containers = st->target_containers;
+    out->keys = st->keys_used;
+    out->target_bytes = st->target ? st->target->st.unique_bytes : 0;
+    out->target_values = st->target ? st->target->st.unique_chunks : 0;
+    return CDC_OK;
+}
+
+int64_t cdc_store_iterate_device(cdc_store_t *st, uint8_t *d_digests, uint8_t *d_kinds, uint64_t *d_lengths,
+                                 uint64_t *d_key_first, size_t cap, void *hip_stream) {
+    if (!st) {
+        cdc::set_error("NULL store");
+        return CDC_EINVAL;
+    }
+    if (cap && (!d_digests || !d_kinds || !d_lengths || !d_key_first)) {
+        cdc::set_error("cdc_store_iterate_device: NULL destination");
+        return CDC_EINVAL;
+    }
+    ST_TRY(hipSetDevice(st->device));
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : st->stream;
+    Scratch mem;
+    uint64_t *val = nullptr, n = 0;
+    int rc = rank_slots(st, mem, -1, &val, &n, s);
+    if (rc) return rc;
+    if (n > cap || n == 0) return (int64_t)n;
+    uint64_t *block = nullptr;
+    ST_TRY(mem.alloc(&block, cdc::store_scan_blocks(n + 1) + 1));
+    ST_TRY(hipMemsetAsync(d_key_first + n, 0, 8, s));
+    ST_TRY(cdc::launch_store_iterate(st->t, scrub_view(st), val, d_digests, d_kinds, d_lengths, d_key_first, s));
+    ST_TRY(cdc::launch_store_scan(d_key_first, n + 1, block, nullptr, s));
+    ST_TRY(hipStreamSynchronize(s));
+    return (int64_t)n;
+}
+
+int64_t cdc_store_keys_device(cdc_store_t *st, uint8_t *d_keys, size_t cap, void *hip_stream) {
+    if (!st) {
+        cdc::set_error("NULL store");
+        return CDC_EINVAL;
+    }
+    if (cap && !d_keys) {
+        cdc::set_error("cdc_store_keys_device: NULL destination");
+        return CDC_EINVAL;
+    }
+    if (!st->target_containers) return 0;
+    if (target_stale(st)) {
+        cdc::set_error("chunk store keys: the target store was cleared since these containers were scrubbed");
+        return CDC_ENOTFOUND;
+    }
+    ST_TRY(hipSetDevice(st->device));
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : st->stream;
+    Scratch mem;
+    uint64_t *val = nullptr, *block = nullptr;
+    ST_TRY(mem.alloc(&val, st->t.slots));
+    ST_TRY(mem.alloc(&block, cdc::store_scan_blocks(st->t.slots) + 1));
+    const cdc::ScrubView v = scrub_view(st);
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(st->d_acc) + 8;
+    ST_TRY(cdc::launch_store_key_counts(st->t, v, val, s));
+    ST_TRY(cdc::launch_store_scan(val, st->t.slots, block, acc, s));
+    uint64_t n = 0;
+    ST_TRY(hipMemcpyAsync(&n, acc, 8, hipMemcpyDeviceToHost, s));
+    ST_TRY(hipStreamSynchronize(s));
+    if (n > cap || n == 0) return (int64_t)n;
+    ST_TRY(cdc::launch_store_keys(st->t, v, val, d_keys, s));
+    ST_TRY(hipStreamSynchronize(s));
+    return (int64_t)n;
 }
 
 }  // extern "C"

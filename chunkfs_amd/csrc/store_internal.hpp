@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/chunkfs_amd.h"
+#include "store.hpp"
 
 namespace cdc {
 
@@ -29,5 +30,16 @@ StoreView store_view(const cdc_store *st);
 // holds the n slots.  Same checks, same refusal rule, same return value.
 int64_t store_put_slots(cdc_store *st, const uint8_t *d_data, uint64_t data_len, const cdc_chunk_t *d_chunks,
                         const uint8_t *d_digests, uint64_t n, void *hip_stream);
+
+
+// The scrubbed state: true once the store holds target-kind containers, whose
+// bytes are found through the slot's current container (the base arena was
+// reset by the scrub, so a location cached before it is stale).  *stale: the
+// target store was cleared since; a read that needs a target-kind container
+// must return CDC_ENOTFOUND.
+bool store_scrub_view(const cdc_store *st, ScrubView *view, bool *stale);
+
+// The device a chunker handle is bound to (capi.cpp).
+int handle_device(const cdc_handle *h);
 
 }  // namespace cdc

@@ -31,7 +31,12 @@ extern "C" {
  *    cdc_batch_sync.
  * 4: cdc_sha256_batch_device.
  * 5: cdc_store_* (device chunk store), CDC_ENOTFOUND.
- * 6: cdc_files_* / cdc_file_* (device file layer), CDC_EEXIST, CDC_EPERM. */
+ * 6: cdc_files_* / cdc_file_* (device file layer), CDC_EEXIST, CDC_EPERM.
+ *    Added since, with no change to an existing entry point or struct (the
+ *    number stays 6): the scrub stage -- cdc_store_set_target,
+ *    cdc_store_scrub, cdc_store_scrub_stats, cdc_store_iterate_device,
+ *    cdc_store_keys_device, cdc_scrub_measurements_t, cdc_scrub_stats_t,
+ *    CDC_SCRUB_*. */
 #define CHUNKFS_AMD_ABI_VERSION 6
 
 /* Chunk{offset,length} -- reference src/lib.rs:43-47 (usize fields; u64 here). */
@@ -411,6 +416,100 @@ int64_t cdc_store_get_device(cdc_store_t *st, const uint8_t *d_digests, size_t n
  * how many were found. */
 int64_t cdc_store_contains_device(cdc_store_t *st, const uint8_t *d_digests, size_t n,
                                   uint8_t *d_found, void *hip_stream);
+
+/* ---- Scrub stage -----------------------------------------------------------------
+ * The reference's second stage: the Scrub hook (src/system/scrub.rs:31-64),
+ * the DataContainer that is either a chunk or a list of target keys
+ * (src/system/storage.rs:12-21), the target map, retrieve through target keys
+ * (storage.rs:141-157), and new_with_scrubber / scrub / total_dedup_ratio /
+ * storage_iterator / clear_file_system (src/system/mod.rs:226-298).
+ *
+ * The target map is a second cdc_store_t: its key is the 32-byte SHA-256 of the
+ * value, a Database<Hash, Vec<u8>>.  The base store keeps, per slot, the
+ * container's kind and -- for a target -- a run of resolved keys: the target
+ * store's slot and the byte offset of the key's value inside the container.  A
+ * read goes from slot to target location with no digest lookup.
+ *
+ * Once a store holds target-kind containers, cdc_store_get_device expands a
+ * digest into the pieces of its keys (d_spans still reports one {offset,
+ * length} per digest; every convention of the call is unchanged) and
+ * cdc_store_contains_device is true for them.  The file layer finds a span's
+ * bytes through its slot's current container.  Writes go on as before: a digest
+ * that exists as a target adds nothing (first insert wins), a new digest
+ * becomes a chunk-kind container.
+ *
+ * A COPY or RECHUNK scrub converts every chunk-kind container, so afterwards no
+ * byte of the base arena is live: arena_used becomes 0 and later writes fill
+ * the arena again from the start.
+ *
+ * A refused scrub changes nothing.  Before the target or the base is touched, a
+ * planning pass computes the key count and the sum of round_up(length, 16) "as
+ * if every key were new" (for RECHUNK by chunking every group once for the
+ * counts; a scrub that fits one group keeps its lists and does not chunk
+ * twice) and returns CDC_ENOMEM if the target's max_chunks or arena cannot take
+ * that much.  The index's result-dependent errors (a table full of 64-bit key
+ * collisions) stay what they are for put: they can leave the containers of
+ * earlier groups converted, each still readable.
+ *
+ * Epochs: the base remembers the target's clear count.  After
+ * cdc_store_clear(target), a read that needs a target-kind container returns
+ * CDC_ENOTFOUND and writes nothing, and a scrub returns CDC_ENOTFOUND while
+ * target-kind containers exist; cdc_store_clear(base) drops the containers and
+ * keys, keeps the attachment and adopts the target's present state. */
+#define CDC_SCRUB_DUMB 0    /* DumbScrubber (scrub.rs:116-129): does nothing, all-zero measurements */
+#define CDC_SCRUB_COPY 1    /* CopyScrubber (scrub.rs:85-114): target.insert(hash, chunk), make_target([hash]) */
+#define CDC_SCRUB_RECHUNK 2 /* this project's own, no counterpart in the reference: every chunk container is
+                               chunked again with `chunker`, keys = SHA-256 of the sub-chunks, each
+                               (key, sub-chunk) inserted into the target, make_target(keys).  A length-0
+                               chunk becomes a target with no keys. */
+
+/* ScrubMeasurements (scrub.rs:71-79). */
+typedef struct cdc_scrub_measurements {
+    uint64_t processed_data;  /* bytes of the chunk containers the scrubber converted */
+    double running_seconds;   /* wall time of the call */
+    uint64_t data_left;       /* 0: the provided scrubbers convert every chunk container or none */
+} cdc_scrub_measurements_t;
+
+typedef struct cdc_scrub_stats {
+    uint64_t cdc_bytes;          /* total_cdc_size (storage.rs:193-200): bytes of the chunk-kind containers */
+    uint64_t chunk_containers;
+    uint64_t target_containers;
+    uint64_t keys;               /* over all target-kind containers */
+    uint64_t target_bytes;       /* sum of the target map's value lengths (storage.rs:250-257) */
+    uint64_t target_values;
+} cdc_scrub_stats_t;
+
+/* ChunkStorage::new_with_scrubber's target_map (storage.rs:165-178): `target`
+ * becomes the target map of `base` (not owned: destroy the base first).
+ * CDC_EINVAL if either is NULL, base == target, they are on different devices,
+ * `target` has a target itself, or `base` holds target-kind containers. */
+int cdc_store_set_target(cdc_store_t *base, cdc_store_t *target);
+/* ChunkStorage::scrub (storage.rs:180-190) with one of the CDC_SCRUB_*
+ * scrubbers; CDC_EINVAL without a target ("scrubber cannot be used with CDC
+ * filesystem").  `chunker` is used by RECHUNK only and must be on the store's
+ * device; every algorithm is allowed.  RECHUNK works in groups of containers
+ * (one cdc_chunk_batch_device + cdc_sha256_batch_device + put each) so that its
+ * scratch stays bounded; CHUNKFS_AMD_SCRUB_GROUP=containers[,bytes] sets the
+ * bounds of a group. */
+int cdc_store_scrub(cdc_store_t *base, int scrubber, cdc_handle_t *chunker,
+                    cdc_scrub_measurements_t *out, void *hip_stream);
+/* The numbers behind cdc_dedup_ratio / average_chunk_size / full_cdc_dedup_ratio
+ * (storage.rs:193-231) and total_dedup_ratio (storage.rs:250-261).  Without a
+ * target: cdc_bytes = unique_bytes, the rest 0. */
+int cdc_store_scrub_stats(const cdc_store_t *base, cdc_scrub_stats_t *out);
+/* ChunkStorage::iterator (storage.rs:233-235, FileSystem::storage_iterator,
+ * mod.rs:266-269): per occupied slot, in slot order, the digest (32 bytes), the
+ * kind (0 chunk, 1 target), the length the container restores to, and
+ * d_key_first[n + 1] -- container i owns keys [d_key_first[i], d_key_first[i +
+ * 1]) of cdc_store_keys_device.  DEVICE arrays of cap (cap + 1) entries.
+ * Returns n; a return > cap means nothing was written.  The order is
+ * unspecified but the same for both calls while the store is not modified. */
+int64_t cdc_store_iterate_device(cdc_store_t *st, uint8_t *d_digests, uint8_t *d_kinds,
+                                 uint64_t *d_lengths, uint64_t *d_key_first, size_t cap,
+                                 void *hip_stream);
+/* The flat 32-byte keys of every target-kind container, in the same order.
+ * Returns the key count; a return > cap means nothing was written. */
+int64_t cdc_store_keys_device(cdc_store_t *st, uint8_t *d_keys, size_t cap, void *hip_stream);
 
 /* ---- File layer ------------------------------------------------------------------
  * The reference's FileLayer (src/system/file_layer.rs) and the FileSystem calls

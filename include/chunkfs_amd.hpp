@@ -232,6 +232,29 @@ class Store {
     }
     cdc_store_t *handle() { return st_; }
 
+    // Scrub stage (chunkfs_amd.h "Scrub stage"; system/scrub.rs, storage.rs:165-190,
+    // 233-235).  `target` becomes this store's target map and must outlive it.
+    void set_target(Store &target) { check(cdc_store_set_target(st_, target.st_)); }
+    // scrubber: CDC_SCRUB_DUMB / _COPY / _RECHUNK (the last with a chunker on the store's device).
+    cdc_scrub_measurements_t scrub(int scrubber, Chunker *chunker = nullptr, void *hip_stream = nullptr) {
+        cdc_scrub_measurements_t m{};
+        check(cdc_store_scrub(st_, scrubber, chunker ? chunker->handle() : nullptr, &m, hip_stream));
+        return m;
+    }
+    cdc_scrub_stats_t scrub_stats() const {
+        cdc_scrub_stats_t s{};
+        check(cdc_store_scrub_stats(st_, &s));
+        return s;
+    }
+    // storage_iterator: containers in slot order; d_key_first has cap + 1 entries.
+    int64_t iterate_device(uint8_t *d_digests, uint8_t *d_kinds, uint64_t *d_lengths, uint64_t *d_key_first,
+                           size_t cap, void *hip_stream = nullptr) {
+        return check(cdc_store_iterate_device(st_, d_digests, d_kinds, d_lengths, d_key_first, cap, hip_stream));
+    }
+    int64_t keys_device(uint8_t *d_keys, size_t cap, void *hip_stream = nullptr) {
+        return check(cdc_store_keys_device(st_, d_keys, cap, hip_stream));
+    }
+
   private:
     cdc_store_t *st_ = nullptr;
 };
@@ -334,6 +357,12 @@ class Files {
     }
     // clear_database (mod.rs:275-278): no files, an empty store, handles invalid.
     void clear() { check(cdc_files_clear(fs_)); }
+    // clear_file_system (mod.rs:294-297): the target map first, so that the
+    // store's clear adopts the emptied target.
+    void clear_file_system(Store &target) {
+        target.clear();
+        clear();
+    }
     cdc_files_t *handle() { return fs_; }
 
   private:

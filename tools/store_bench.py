@@ -24,6 +24,18 @@ per-kernel split of put comes from a profiler's kernel trace of
 `store_bench.py --iters 2 --warmup 1` (kernel names: copy_kernel,
 precheck_kernel, scan_*_kernel, lookup_kernel, claim/verify/mark_kernel).
 
+Scrub stage (skipped with --no-scrub), on file systems of their own with a
+target store, the file written again before every timed scrub:
+
+  (g) scrub COPY of the whole store (container list + put into the target from
+      the base arena + marking);
+  (h) cdc_file_read_complete_device after COPY -- the same piece count and
+      bytes as (e), reported as a ratio to (e), with its planner-only time;
+  (i) scrub RECHUNK with FastCDC 1024/2048/4096 at three group sizes
+      (CHUNKFS_AMD_SCRUB_GROUP), to choose the default group;
+  (j) cdc_file_read_complete_device and 4 KiB cdc_file_pread_device calls after
+      RECHUNK at the default group (about avg / sub-avg times the pieces).
+
 Prints one JSON line; --out also writes it to a file.
 """
 import argparse
@@ -45,6 +57,88 @@ def _hip_runtime():
     raise RuntimeError("no HIP runtime is loaded")
 
 
+def _group_env(spec):
+    cnt, nbytes = spec.split(",")
+    mult = {"k": 1 << 10, "m": 1 << 20}.get(nbytes[-1].lower())
+    return f"{int(cnt)},{int(nbytes[:-1]) * mult if mult else int(nbytes)}"
+
+
+def scrub_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med, fread_ms):
+    """Legs (g)-(j): the same stream in file systems with a target store."""
+    import torch
+
+    def file_system(scrubber):
+        return c.FileSystem.new_with_scrubber(scrubber, max_chunks=k, arena_bytes=n + 16 * k,
+                                              target_max_chunks=n // 1024 + 2 * k,
+                                              target_arena_bytes=n + n // 64 + 16 * k)
+
+    state = {}
+
+    def rewrite():
+        state["fs"].clear_file_system()
+        state["w"] = state["fs"].create_file("bench", ch)
+        assert L.cdc_file_write_device(state["w"]._fh, ch._h, P(buf.data_ptr()), n, P(sp)) == k
+
+    def do_scrub():
+        assert state["fs"].store.scrub(state["scrubber"], stream=sp).processed_data == n
+
+    def do_read():
+        assert L.cdc_file_read_complete_device(state["w"]._fh, P(out.data_ptr()), n, None, P(sp)) == n
+
+    def do_size():
+        assert L.cdc_file_read_complete_device(state["w"]._fh, None, 0, None, P(sp)) == n
+
+    def do_preads():
+        for i in range(256):
+            off = (i * 0x9E3779B1) % (n - 4096)
+            assert L.cdc_file_pread_device(state["w"]._fh, off, 4096, P(out.data_ptr()), P(sp)) == 4096
+
+    def check_equal(what):
+        out.zero_()
+        do_read()
+        torch.cuda.synchronize()
+        if not torch.equal(out, buf):
+            raise SystemExit(f"store_bench: the file read back after {what} differs")
+
+    def scrub_times():
+        return timed(do_scrub, before=rewrite, iters=a.scrub_iters, warmup=1)
+
+    gib = n / (1 << 30)
+    res = {"scrub_iters": a.scrub_iters}
+    state["scrubber"] = c.CopyScrubber()
+    state["fs"] = file_system(state["scrubber"])
+    t = scrub_times()
+    res.update(scrub_copy_ms=med(t), scrub_copy_ms_min_max=[min(t), max(t)], scrub_copy_GiBps=gib / (med(t) * 1e-3))
+    check_equal("COPY")
+    t, tz = timed(do_read), timed(do_size)
+    res.update(copy_read_ms=med(t), copy_read_ms_min_max=[min(t), max(t)], copy_read_size_only_ms=med(tz),
+               copy_read_copy_ms=med(t) - med(tz), copy_read_vs_file_read=med(t) / fread_ms)
+
+    state.pop("w")._close()
+    state["scrubber"] = c.RechunkScrubber(c.FastChunker(c.SizeParams(1024, 2048, 4096)))
+    state["fs"] = file_system(state["scrubber"])  # a second file system; the first one is released here
+    old = os.environ.pop("CHUNKFS_AMD_SCRUB_GROUP", None)
+    res["scrub_rechunk"] = {}
+    try:
+        for spec in a.scrub_groups.split(";"):
+            os.environ["CHUNKFS_AMD_SCRUB_GROUP"] = _group_env(spec)
+            t = scrub_times()
+            res["scrub_rechunk"][spec] = {"ms": med(t), "ms_min_max": [min(t), max(t)], "GiBps": gib / (med(t) * 1e-3)}
+    finally:
+        os.environ.pop("CHUNKFS_AMD_SCRUB_GROUP", None)
+        if old is not None:
+            os.environ["CHUNKFS_AMD_SCRUB_GROUP"] = old
+    t = scrub_times()  # the default group
+    x = state["fs"].store.scrub_stats()
+    res.update(scrub_rechunk_default_ms=med(t), scrub_rechunk_default_ms_min_max=[min(t), max(t)],
+               rechunk_keys=x["keys"], rechunk_target_values=x["target_values"])
+    check_equal("RECHUNK")
+    t, tz, tp = timed(do_read), timed(do_size), timed(do_preads)
+    res.update(rechunk_read_ms=med(t), rechunk_read_ms_min_max=[min(t), max(t)], rechunk_read_size_only_ms=med(tz),
+               rechunk_read_vs_file_read=med(t) / fread_ms, rechunk_pread4k_us=med(tp) * 1e3 / 256)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--bytes", type=int, default=1 << 30)
@@ -52,6 +146,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--out", default=None, help="also write the JSON result to this file")
+    ap.add_argument("--no-scrub", action="store_true", help="skip the scrub-stage legs (g)-(j)")
+    ap.add_argument("--scrub-iters", type=int, default=3)
+    ap.add_argument("--scrub-groups", default="4096,64m;65536,256m;1048576,1024m",
+                    help="RECHUNK groups to time: containers,bytes[k|m] separated by ';'")
     a = ap.parse_args()
 
     import numpy as np
@@ -84,9 +182,9 @@ def main():
     hip.hipMemcpyAsync.restype = ctypes.c_int
     HIP_MEMCPY_D2D = 3
 
-    def timed(fn, before=None):
+    def timed(fn, before=None, iters=a.iters, warmup=a.warmup):
         ms = []
-        for it in range(a.warmup + a.iters):
+        for it in range(warmup + iters):
             if before:
                 before()
             torch.cuda.synchronize()
@@ -95,7 +193,7 @@ def main():
             fn()
             e1.record(s)
             e1.synchronize()
-            if it >= a.warmup:
+            if it >= warmup:
                 ms.append(e0.elapsed_time(e1))
         return ms
 
@@ -198,6 +296,8 @@ def main():
         "file_segments": segments, "file_segment_us": med(t_fseg) * 1e3 / segments,
         "file_segment_pass_ms": med(t_fseg), "file_readback_equal": fsame,
     }
+    if not a.no_scrub:
+        res.update(scrub_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med, med(t_fread)))
     line = json.dumps(res)
     print(line)
     if a.out:
