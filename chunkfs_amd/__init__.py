@@ -661,6 +661,23 @@ class ChunkStore:
         return [(dig[i].tobytes(), "target" if kind[i] else "chunk", int(ln[i]),
                  [keys[k].tobytes() for k in range(int(kf[i]), int(kf[i + 1]))]) for i in range(n)]
 
+    def size_distribution(self, adjustment):
+        """CDCFixture::size_distribution (bench/mod.rs:218-232): {length //
+        adjustment * adjustment: containers}, over every container of the store
+        (cdc_store_size_distribution_device).  adjustment == 0 is CDC_EINVAL
+        (the reference divides by zero)."""
+        import torch
+        dev = f"cuda:{self.device}"
+        n = check(lib().cdc_store_size_distribution_device(self._h, int(adjustment), None, None, 0, None))
+        if n == 0:
+            return {}
+        sizes = torch.empty(n, dtype=torch.int64, device=dev)
+        counts = torch.empty(n, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        assert check(lib().cdc_store_size_distribution_device(self._h, int(adjustment), _ptr(sizes.data_ptr()),
+                                                              _ptr(counts.data_ptr()), n, None)) == n
+        return dict(zip(sizes.cpu().tolist(), counts.cpu().tolist()))
+
     # -- host conveniences over the calls above --------------------------------
     def write(self, chunker, data):
         """One file write: chunk and hash `data` (host bytes) with `chunker`, put
@@ -825,6 +842,17 @@ class FileSystem:
         return check(lib().cdc_file_write_device(handle._fh, handle.chunker._h, _ptr(t.data_ptr()), t.numel(),
                                                  _ptr(stream)))
 
+    def write_from_stream(self, handle, reader):
+        """FileSystem::write_from_stream (mod.rs:116-134): reads `reader` (an
+        object with read()) to its end and issues ONE write_to_file.  Chunking
+        does not depend on how a write is cut into segments, so
+        the spans equal those of the reference's loop over 1 MiB segments.  The
+        whole dataset is uploaded at once: it must fit beside the store in HBM."""
+        data = reader.read()
+        if len(data) == 0:
+            return 0
+        return self.write_to_file(handle, data)
+
     def append_device(self, handle, d_data, data_len, d_chunks, d_digests, n, stream=None):
         """cdc_file_append_device: spans chunked and hashed by the caller (device pointers)."""
         return check(lib().cdc_file_append_device(handle._fh, _ptr(d_data), data_len, _ptr(d_chunks),
@@ -902,6 +930,30 @@ class FileSystem:
                                                      _ptr(ln.data_ptr()), cap, None))
         dig, cnt, ln = dig[:k].cpu().numpy(), cnt[:k].cpu().numpy(), ln[:k].cpu().numpy()
         return {dig[i].tobytes(): (int(cnt[i]), int(ln[i])) for i in range(k)}
+
+    def get_to_dedup_ratio(self, name, dedup_ratio, stream=None):
+        """FileSystem::get_to_dedup_ratio (mod.rs:170-178, file_layer.rs:208-268):
+        derives the file "{name}.{ratio:.2}" from the unique spans of `name`,
+        repeating the first ceil(U / ratio) of them until the file holds about
+        ratio times its unique bytes; returns the new name.  Span offsets in the
+        new file are true byte positions (the layer's one deviation).
+        CdcError(CDC_EINVAL) for a ratio < 1, NaN or infinite, and when the
+        repeating spans are all empty (the reference would not return)."""
+        buf = ctypes.create_string_buffer(len(name.encode()) + 400)
+        need = check(lib().cdc_files_get_to_dedup_ratio(self._h, name.encode(), float(dedup_ratio), buf, len(buf),
+                                                        _ptr(stream)))
+        assert need <= len(buf)
+        return buf.value.decode()
+
+    def verify_device(self, handle, d_ptr, length, stream=None):
+        """cdc_file_verify_device: compares the file with the `length` bytes at
+        the device pointer `d_ptr` without reading it back.  Returns (equal,
+        first_diff): first_diff is None when equal, else the smallest differing
+        byte offset (min(size, length) when only the sizes differ)."""
+        diff = ctypes.c_uint64(0)
+        same = check(lib().cdc_file_verify_device(handle._fh, _ptr(d_ptr), int(length), ctypes.byref(diff),
+                                                  _ptr(stream)))
+        return bool(same), (None if same else int(diff.value))
 
     def write_file_to_disk(self, name, path):
         """FileSystem::write_file_to_disk (mod.rs:181-200): loops read_from_file;

@@ -39,6 +39,7 @@ EXPORTS = [
     "cdc_files_create_file", "cdc_files_open", "cdc_file_close", "cdc_file_stat", "cdc_file_write_device",
     "cdc_file_append_device", "cdc_file_read_complete_device", "cdc_file_read_device", "cdc_file_pread_device",
     "cdc_files_pread_batch_device", "cdc_file_hashes_device", "cdc_file_distribution_device",
+    "cdc_files_get_to_dedup_ratio", "cdc_file_verify_device", "cdc_store_size_distribution_device",
     "cdc_fill_splitmix64_device", "cdc_version", "cdc_abi_version",
 ]
 # include/chunkfs_amd_debug.h (diagnostics, not part of the drop-in boundary)
@@ -258,6 +259,12 @@ def lib():
     L.cdc_file_hashes_device.restype = ctypes.c_int64
     L.cdc_file_distribution_device.argtypes = [P, P, P, P, sz, P]
     L.cdc_file_distribution_device.restype = ctypes.c_int64
+    L.cdc_files_get_to_dedup_ratio.argtypes = [P, ctypes.c_char_p, ctypes.c_double, ctypes.c_char_p, sz, P]
+    L.cdc_files_get_to_dedup_ratio.restype = ctypes.c_int64
+    L.cdc_file_verify_device.argtypes = [P, P, sz, u64p, P]
+    L.cdc_file_verify_device.restype = ctypes.c_int64
+    L.cdc_store_size_distribution_device.argtypes = [P, ctypes.c_uint64, P, P, sz, P]
+    L.cdc_store_size_distribution_device.restype = ctypes.c_int64
     L.cdc_fill_splitmix64_device.argtypes = [P, sz, ctypes.c_uint64, P]
     L.cdc_fill_splitmix64_device.restype = ctypes.c_int
     L.cdc_debug_pipeline.argtypes = [P]

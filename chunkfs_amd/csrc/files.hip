@@ -27,6 +27,13 @@
 // records, a target-kind span yields one piece per key, a range trims its two
 // end spans by binary search over the per-key offsets, and the exact piece
 // count goes to the host before the copy.  The chain above is untouched.
+//
+// get_to_dedup_ratio (file_layer.rs:208-268) derives a file from another one's
+// unique spans: the distribution's first-occurrence flags and scan give the
+// unique list as span indices, a scan of its lengths gives the cycle's prefix
+// sums, and a gather writes the new table with true offsets.  verify
+// (src/bench/mod.rs:241-275) is the read chain with the store's compare kernel
+// as its last step.
 #include "files.hpp"
 
 namespace cdc {
@@ -341,7 +348,131 @@ __global__ __launch_bounds__(kFlThreads) void dist_compact_kernel(SpanTable t, u
     lengths[j] = t.off[i + 1] - t.off[i];
 }
 
+// ---- get_to_dedup_ratio ------------------------------------------------------------
+// The unique list of file_layer.rs:225-231 as span indices: the spans flagged as
+// first occurrences by the distribution's kernels, at their rank val[i], with
+// the length the reference gives them (the next span's offset minus their own).
+__global__ __launch_bounds__(kFlThreads) void ratio_uniq_kernel(SpanTable t, uint64_t m,
+                                                                const uint64_t *__restrict__ firstpos,
+                                                                const uint64_t *__restrict__ val, uint64_t *uidx,
+                                                                uint64_t *ulen) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t s = t.slot[i];
+    if (s == kNoSlot || firstpos[s] != i) return;
+    const uint64_t j = val[i];
+    uidx[j] = i;
+    ulen[j] = t.off[i + 1] - t.off[i];
+}
+
+// One thread.  pre = exclusive scan of the unique lengths over m entries (zero
+// past the unique count), *pre_total their sum, so the sum of the first i
+// lengths is pre[i] for i < m and *pre_total for i = m.  out[0] = C, the bytes
+// of one cycle over the first R entries; out[1] = the largest i <= R whose
+// prefix is <= total_size mod C: the entries the take-while accepts of the last,
+// partial cycle (entries of length 0 count).  C = 0: out[1] = 0, the host refuses.
+__global__ void ratio_take_kernel(const uint64_t *__restrict__ pre, const uint64_t *__restrict__ pre_total,
+                                  uint64_t m, uint64_t R, uint64_t total_size, unsigned long long *out) {
+    if (blockIdx.x || threadIdx.x) return;
+    const uint64_t C = R < m ? pre[R] : *pre_total;
+    uint64_t lo = 0;
+    if (C) {
+        const uint64_t rem = total_size % C;
+        uint64_t hi = R;  // prefix(0) = 0 <= rem
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi + 1) >> 1;
+            const uint64_t p = mid < m ? pre[mid] : *pre_total;
+            if (p <= rem) lo = mid;
+            else hi = mid - 1;
+        }
+    }
+    out[0] = C;
+    out[1] = lo;
+}
+
+// Output span i of the derived file takes unique entry i mod R while i < K (the
+// repeating part) and R + i - K after it (the remaining entries): its source
+// span goes to sidx, its length to the scan input, and the planner's bounds to
+// stat as span_len_kernel leaves them.
+__global__ __launch_bounds__(kFlThreads) void ratio_src_kernel(SpanTable src, const uint64_t *__restrict__ uidx,
+                                                               uint64_t K, uint64_t R, uint64_t n, uint64_t *sidx,
+                                                               uint64_t *val, unsigned long long *stat) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t least = ~0ull, zeros = 0;
+    if (i < n) {
+        const uint64_t si = uidx[i < K ? i % R : R + (i - K)];
+        const uint64_t len = src.off[si + 1] - src.off[si];
+        sidx[i] = si;
+        val[i] = len;
+        least = len - 1;
+        zeros = len == 0;
+    }
+#pragma unroll
+    for (int k = 1; k < 64; k <<= 1) {
+        const uint64_t o = __shfl_xor(least, k);
+        least = o < least ? o : least;
+        zeros += __shfl_xor(zeros, k);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (least != ~0ull) atomicMin(&stat[0], (unsigned long long)least);
+        if (zeros) atomicAdd(&stat[1], (unsigned long long)zeros);
+    }
+}
+
+// val = exclusive scan of the lengths: the true offsets in the new file.
+__global__ __launch_bounds__(kFlThreads) void ratio_write_kernel(SpanTable src, SpanTable dst,
+                                                                 const uint64_t *__restrict__ sidx,
+                                                                 const uint64_t *__restrict__ val,
+                                                                 const uint64_t *__restrict__ total, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    if (i == n) {
+        dst.off[n] = *total;
+        return;
+    }
+    const uint64_t si = sidx[i];
+    dst.off[i] = val[i];
+    dst.slot[i] = src.slot[si];
+    dst.loc[i] = src.loc[si];
+    const uint4 *from = reinterpret_cast<const uint4 *>(src.digest + 32 * si);
+    uint4 *to = reinterpret_cast<uint4 *>(dst.digest + 32 * i);
+    to[0] = from[0];
+    to[1] = from[1];
+}
+
 }  // namespace
+
+hipError_t launch_files_ratio_unique(const SpanTable &t, uint64_t m, uint32_t *cnt, uint64_t *firstpos, uint64_t *val,
+                                     uint64_t *block_sums, uint64_t *uidx, uint64_t *ulen, uint64_t *ublock,
+                                     unsigned long long *h_out, hipStream_t s) {
+    if (!m) return hipSuccess;
+    dist_init_kernel<<<grid_of(m), kFlThreads, 0, s>>>(t.slot, m, cnt, firstpos);
+    dist_count_kernel<<<grid_of(m), kFlThreads, 0, s>>>(t.slot, m, cnt, firstpos);
+    dist_flag_kernel<<<grid_of(m), kFlThreads, 0, s>>>(t.slot, m, firstpos, val);
+    hipError_t e = launch_store_scan(val, m, block_sums, h_out, s);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(ulen, 0, m * 8, s);
+    if (e != hipSuccess) return e;
+    ratio_uniq_kernel<<<grid_of(m), kFlThreads, 0, s>>>(t, m, firstpos, val, uidx, ulen);
+    return launch_store_scan(ulen, m, ublock, h_out + 1, s);
+}
+
+hipError_t launch_files_ratio_take(const uint64_t *pre, const uint64_t *ublock, uint64_t m, uint64_t R,
+                                   uint64_t total_size, unsigned long long *h_out, hipStream_t s) {
+    ratio_take_kernel<<<1, 64, 0, s>>>(pre, ublock + store_scan_blocks(m), m, R, total_size, h_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_files_ratio_gather(const SpanTable &src, const SpanTable &dst, const uint64_t *uidx, uint64_t K,
+                                     uint64_t R, uint64_t n, uint64_t *sidx, uint64_t *val, uint64_t *block_sums,
+                                     unsigned long long *d_stat, unsigned long long *h_total, hipStream_t s) {
+    if (!n) return hipSuccess;
+    ratio_src_kernel<<<grid_of(n), kFlThreads, 0, s>>>(src, uidx, K, R, n, sidx, val, d_stat);
+    const hipError_t e = launch_store_scan(val, n, block_sums, h_total, s);
+    if (e != hipSuccess) return e;
+    ratio_write_kernel<<<grid_of(n + 1), kFlThreads, 0, s>>>(src, dst, sidx, val, block_sums + store_scan_blocks(n), n);
+    return hipGetLastError();
+}
 
 hipError_t launch_files_append(const SpanTable &t, uint64_t n0, uint64_t size0, const uint32_t *slot_of,
                                const uint64_t *tbl_length, const uint64_t *tbl_loc, const uint8_t *d_digests,
@@ -358,7 +489,8 @@ hipError_t launch_files_append(const SpanTable &t, uint64_t n0, uint64_t size0, 
 
 hipError_t launch_files_read(const ReadReq *d_req, uint64_t nreq, uint64_t arena, ReadPlan *plan, uint64_t *cnt,
                              uint64_t *rblock, StorePiece *pieces, uint64_t *tstart, uint64_t *block_sums,
-                             uint64_t max_pieces, uint64_t max_tiles, ReadResult *h_res, hipStream_t s) {
+                             uint64_t max_pieces, uint64_t max_tiles, ReadResult *h_res, hipStream_t s,
+                             uint64_t cmp_base, unsigned long long *d_diff) {
     if (!nreq) return hipSuccess;
     uint64_t *total_pieces = rblock + store_scan_blocks(nreq);
     resolve_kernel<<<grid_of(nreq), kFlThreads, 0, s>>>(d_req, nreq, plan, cnt, nreq == 1 ? total_pieces : nullptr,
@@ -370,6 +502,9 @@ hipError_t launch_files_read(const ReadReq *d_req, uint64_t nreq, uint64_t arena
                                                              tstart, max_pieces);
     e = launch_store_scan(tstart, max_pieces, block_sums, nullptr, s);
     if (e != hipSuccess) return e;
+    if (d_diff)
+        return launch_store_compare(pieces, tstart, max_pieces, max_tiles, block_sums + store_scan_blocks(max_pieces),
+                                    cmp_base, d_diff, s);
     return launch_store_copy(pieces, tstart, max_pieces, max_tiles, block_sums + store_scan_blocks(max_pieces), s);
 }
 
@@ -396,12 +531,16 @@ hipError_t launch_files_plan_x(const ReadReq *d_req, const uint64_t *d_rslot, ui
 
 hipError_t launch_files_copy_x(const SpanRec *recs, const uint64_t *pcnt, uint64_t max_spans, const ScrubView &v,
                                const uint64_t *loc, uint64_t arena, StorePiece *pieces, uint64_t *tstart,
-                               uint64_t *block_sums, uint64_t n_pieces, uint64_t max_tiles, hipStream_t s) {
+                               uint64_t *block_sums, uint64_t n_pieces, uint64_t max_tiles, hipStream_t s,
+                               uint64_t cmp_base, unsigned long long *d_diff) {
     if (!n_pieces) return hipSuccess;
     span_pieces_kernel<<<grid_of(n_pieces), kFlThreads, 0, s>>>(recs, pcnt, max_spans, v, loc, arena, pieces, tstart,
                                                              n_pieces);
     const hipError_t e = launch_store_scan(tstart, n_pieces, block_sums, nullptr, s);
     if (e != hipSuccess) return e;
+    if (d_diff)
+        return launch_store_compare(pieces, tstart, n_pieces, max_tiles, block_sums + store_scan_blocks(n_pieces),
+                                    cmp_base, d_diff, s);
     return launch_store_copy(pieces, tstart, n_pieces, max_tiles, block_sums + store_scan_blocks(n_pieces), s);
 }
 

@@ -65,10 +65,14 @@ hipError_t launch_files_append(const SpanTable &t, uint64_t n0, uint64_t size0, 
 // count would drop pieces); the exact counts stay on the device.  plan: nreq;
 // cnt: nreq u64; rblock: store_scan_blocks(nreq) + 1; pieces / tstart:
 // max_pieces; block_sums: store_scan_blocks(max_pieces) + 1; h_res: nreq results
-// in pinned host memory.
+// in pinned host memory.  With d_diff (device u64, preset to ~0) the last step is
+// the store's compare instead of its copy (cdc_file_verify_device): the
+// requests' destinations are read, not written, and *d_diff receives the
+// smallest destination address - cmp_base at which a byte differs.
 hipError_t launch_files_read(const ReadReq *d_req, uint64_t nreq, uint64_t arena, ReadPlan *plan, uint64_t *cnt,
                              uint64_t *rblock, StorePiece *pieces, uint64_t *tstart, uint64_t *block_sums,
-                             uint64_t max_pieces, uint64_t max_tiles, ReadResult *h_res, hipStream_t s);
+                             uint64_t max_pieces, uint64_t max_tiles, ReadResult *h_res, hipStream_t s,
+                             uint64_t cmp_base = 0, unsigned long long *d_diff = nullptr);
 
 // ---- reads in the scrubbed state ------------------------------------------------
 // Once the store holds target-kind containers a span's bytes are found through
@@ -100,10 +104,12 @@ hipError_t launch_files_plan_x(const ReadReq *d_req, const uint64_t *d_rslot, ui
 
 // Steps 4-6 after the host has read h_tot: the n_pieces pieces, the tile scan
 // and the store's copy.  pcnt is the scan launch_files_plan_x left; pieces /
-// tstart: n_pieces; block_sums: store_scan_blocks(n_pieces) + 1.
+// tstart: n_pieces; block_sums: store_scan_blocks(n_pieces) + 1.  d_diff /
+// cmp_base: the compare instead of the copy, as in launch_files_read.
 hipError_t launch_files_copy_x(const SpanRec *recs, const uint64_t *pcnt, uint64_t max_spans, const ScrubView &v,
                                const uint64_t *loc, uint64_t arena, StorePiece *pieces, uint64_t *tstart,
-                               uint64_t *block_sums, uint64_t n_pieces, uint64_t max_tiles, hipStream_t s);
+                               uint64_t *block_sums, uint64_t n_pieces, uint64_t max_tiles, hipStream_t s,
+                               uint64_t cmp_base = 0, unsigned long long *d_diff = nullptr);
 
 // chunk_count_distribution over spans [0, m), m = n - 1: per distinct slot, in
 // order of first occurrence, {digest, count, off[i + 1] - off[i] of the first
@@ -114,5 +120,31 @@ hipError_t launch_files_distribution(const SpanTable &t, uint64_t m, uint32_t *c
                                      uint64_t *val, uint64_t *block_sums, uint8_t *d_digests, uint32_t *d_counts,
                                      uint64_t *d_lengths, uint64_t cap, unsigned long long *h_distinct,
                                      hipStream_t s);
+
+// ---- get_to_dedup_ratio (file_layer.rs:208-268) -----------------------------------
+// Step 1: the unique list over spans [0, m), m = n - 1, from the distribution's
+// first-occurrence flags and scan: uidx[j] = span index of the j-th distinct
+// slot, ulen = the exclusive scan of their lengths over m entries (zero past
+// the unique count; the total in ublock[store_scan_blocks(m)]).  cnt / firstpos
+// / val / block_sums as launch_files_distribution; uidx / ulen: m; ublock:
+// store_scan_blocks(m) + 1.  h_out (pinned): [0] = U, [1] = unique_length.
+hipError_t launch_files_ratio_unique(const SpanTable &t, uint64_t m, uint32_t *cnt, uint64_t *firstpos, uint64_t *val,
+                                     uint64_t *block_sums, uint64_t *uidx, uint64_t *ulen, uint64_t *ublock,
+                                     unsigned long long *h_out, hipStream_t s);
+
+// Step 2, once the host has R and total_size: h_out[0] = C = bytes of one cycle
+// over the first R unique entries, h_out[1] = entries the take-while accepts of
+// the last, partial cycle.
+hipError_t launch_files_ratio_take(const uint64_t *pre, const uint64_t *ublock, uint64_t m, uint64_t R,
+                                   uint64_t total_size, unsigned long long *h_out, hipStream_t s);
+
+// Step 3: the n = K + (U - R) spans of the derived file into dst (room for n):
+// span i < K is unique entry i mod R, span i >= K entry R + i - K; offsets are
+// the scan of the gathered lengths; digest, slot and loc are the source's.
+// sidx / val: n; block_sums: store_scan_blocks(n) + 1; d_stat as
+// launch_files_append; *h_total (pinned) = the new file's size.
+hipError_t launch_files_ratio_gather(const SpanTable &src, const SpanTable &dst, const uint64_t *uidx, uint64_t K,
+                                     uint64_t R, uint64_t n, uint64_t *sidx, uint64_t *val, uint64_t *block_sums,
+                                     unsigned long long *d_stat, unsigned long long *h_total, hipStream_t s);
 
 }  // namespace cdc

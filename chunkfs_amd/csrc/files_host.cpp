@@ -4,6 +4,8 @@
 // handles live here on the host; each file's span table lives in HBM and all
 // per-span work runs in files.hip.
 #include <chrono>
+#include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <map>
 #include <set>
@@ -55,8 +57,10 @@ struct cdc_files {
     uint64_t p_cap = 0;
     cdc::StorePiece *d_pieces = nullptr;
     uint64_t *d_tstart = nullptr, *d_pblock = nullptr;
-    unsigned long long *h_tot = nullptr;  // pinned: [0] appended bytes, [1] distinct digests, [2..3] d_stat's copy
-    unsigned long long *d_stat = nullptr;  // [2] append: min(length - 1), spans of length 0
+    // pinned: [0] appended bytes, [1] distinct digests, [2..3] d_stat's copy, [4..7] get_to_dedup_ratio: U,
+    // unique_length, C, spans of the partial cycle, [8] verify: d_stat[2]'s copy
+    unsigned long long *h_tot = nullptr;
+    unsigned long long *d_stat = nullptr;  // [0..1] append: min(length - 1), spans of length 0; [2] verify: first difference
     // reads in the scrubbed state: per-request slot arrays, per-span records
     uint64_t xr_cap = 0;
     uint64_t *h_rslot = nullptr, *d_rslot = nullptr;
@@ -149,6 +153,20 @@ int grow_span_scratch(cdc_files *fs, uint64_t n) {
     FL_TRY(hipMalloc(&fs->a_val, cap * 8));
     FL_TRY(hipMalloc(&fs->a_block, (cdc::store_scan_blocks(cap) + 1) * 8));
     fs->a_cap = cap;
+    return CDC_OK;
+}
+
+// The distribution's per-slot scratch: as large as the store's table.
+int grow_slot_scratch(cdc_files *fs, uint64_t slots) {
+    if (fs->d_slots >= slots) return CDC_OK;
+    (void)hipFree(fs->d_cnt);
+    (void)hipFree(fs->d_first);
+    fs->d_cnt = nullptr;
+    fs->d_first = nullptr;
+    fs->d_slots = 0;
+    FL_TRY(hipMalloc(&fs->d_cnt, slots * 4));
+    FL_TRY(hipMalloc(&fs->d_first, slots * 8));
+    fs->d_slots = slots;
     return CDC_OK;
 }
 
@@ -328,7 +346,7 @@ int grow_scrubbed(cdc_files *fs, uint64_t nreq, uint64_t spans) {
 // than the unscrubbed path): a sub-chunk may be one byte long, so a bound from
 // the byte count alone would be the byte count.
 int run_reads_scrubbed(cdc_files *fs, const std::vector<HostReq> &reqs, const cdc::ScrubView &sv, bool stale,
-                       void *hip_stream) {
+                       void *hip_stream, const uint8_t *cmp_base) {
     const cdc::StoreView v = cdc::store_view(fs->store);
     FL_TRY(hipSetDevice(v.device));
     hipStream_t s = stream_of(fs, hip_stream);
@@ -377,17 +395,27 @@ int run_reads_scrubbed(cdc_files *fs, const std::vector<HostReq> &reqs, const cd
     // A piece adds at most two ragged tiles to its whole ones.
     FL_TRY(cdc::launch_files_copy_x(fs->d_recs, fs->d_pcnt, max_spans, sv, v.loc, (uint64_t)(uintptr_t)v.arena,
                                     fs->d_pieces, fs->d_tstart, fs->d_pblock, np, max_bytes / cdc::kStoreTile + 2 * np,
-                                    s));
+                                    s, (uint64_t)(uintptr_t)cmp_base, cmp_base ? fs->d_stat + 2 : nullptr));
+    if (cmp_base) FL_TRY(hipMemcpyAsync(fs->h_tot + 8, fs->d_stat + 2, 8, hipMemcpyDeviceToHost, s));
     FL_TRY(hipStreamSynchronize(s));
     return CDC_OK;
 }
 
 // Plans and copies every request in one pass; fs->h_res[i] holds the results.
-int run_reads(cdc_files *fs, const std::vector<HostReq> &reqs, void *hip_stream) {
+// cmp_base (verify): the destinations are compared with the file's bytes
+// instead of written; fs->h_tot[8] = the smallest destination address - cmp_base
+// at which a byte differs, ~0 when none does.
+int run_reads(cdc_files *fs, const std::vector<HostReq> &reqs, void *hip_stream, const uint8_t *cmp_base = nullptr) {
+    if (cmp_base) {
+        FL_TRY(hipSetDevice(cdc::store_view(fs->store).device));
+        fs->h_tot[8] = ~0ull;
+        FL_TRY(hipMemsetAsync(fs->d_stat + 2, 0xFF, 8, stream_of(fs, hip_stream)));
+    }
     {
         cdc::ScrubView sv;
         bool stale = false;
-        if (cdc::store_scrub_view(fs->store, &sv, &stale)) return run_reads_scrubbed(fs, reqs, sv, stale, hip_stream);
+        if (cdc::store_scrub_view(fs->store, &sv, &stale))
+            return run_reads_scrubbed(fs, reqs, sv, stale, hip_stream, cmp_base);
     }
     const cdc::StoreView v = cdc::store_view(fs->store);
     FL_TRY(hipSetDevice(v.device));
@@ -412,7 +440,8 @@ int run_reads(cdc_files *fs, const std::vector<HostReq> &reqs, void *hip_stream)
     FL_TRY(hipMemcpyAsync(fs->d_req, fs->h_req, nreq * sizeof(cdc::ReadReq), hipMemcpyHostToDevice, s));
     FL_TRY(cdc::launch_files_read(fs->d_req, nreq, (uint64_t)(uintptr_t)v.arena, fs->d_plan, fs->d_rcnt,
                                   fs->d_rblock, fs->d_pieces, fs->d_tstart, fs->d_pblock, max_pieces, max_tiles,
-                                  fs->h_res, s));
+                                  fs->h_res, s, (uint64_t)(uintptr_t)cmp_base, cmp_base ? fs->d_stat + 2 : nullptr));
+    if (cmp_base) FL_TRY(hipMemcpyAsync(fs->h_tot + 8, fs->d_stat + 2, 8, hipMemcpyDeviceToHost, s));
     FL_TRY(hipStreamSynchronize(s));
     return CDC_OK;
 }
@@ -442,8 +471,8 @@ int cdc_files_create(cdc_store_t *store, size_t seg_size, cdc_files_t **out) {
     fs->seg = seg_size ? seg_size : (1u << 20);
     fs->device = cdc::store_view(store).device;
     hipError_t e = hipSetDevice(fs->device);
-    if (e == hipSuccess) e = hipHostMalloc(&fs->h_tot, 4 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc(&fs->d_stat, 2 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipHostMalloc(&fs->h_tot, 12 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc(&fs->d_stat, 4 * sizeof(unsigned long long));
     if (e != hipSuccess) {
         (void)hipHostFree(fs->h_tot);
         delete fs;
@@ -646,20 +675,123 @@ int64_t cdc_file_distribution_device(cdc_fh_t *fh, uint8_t *d_digests, uint32_t 
     hipStream_t s = stream_of(fs, hip_stream);
     const uint64_t m = f->n - 1;
     if ((rc = grow_span_scratch(fs, m)) != CDC_OK) return rc;
-    if (fs->d_slots < v.slots) {
-        (void)hipFree(fs->d_cnt);
-        (void)hipFree(fs->d_first);
-        fs->d_cnt = nullptr;
-        fs->d_first = nullptr;
-        fs->d_slots = 0;
-        FL_TRY(hipMalloc(&fs->d_cnt, v.slots * 4));
-        FL_TRY(hipMalloc(&fs->d_first, v.slots * 8));
-        fs->d_slots = v.slots;
-    }
+    if ((rc = grow_slot_scratch(fs, v.slots)) != CDC_OK) return rc;
     FL_TRY(cdc::launch_files_distribution(f->t, m, fs->d_cnt, fs->d_first, fs->a_val, fs->a_block, d_digests,
                                           d_counts, d_lengths, cap, fs->h_tot + 1, s));
     FL_TRY(hipStreamSynchronize(s));
     return (int64_t)fs->h_tot[1];
+}
+
+int64_t cdc_file_verify_device(cdc_fh_t *fh, const uint8_t *d_data, size_t len, uint64_t *first_diff,
+                               void *hip_stream) {
+    FileRec *f = nullptr;
+    int rc = lookup(fh, true, &f);
+    if (rc) return rc;
+    if (len && !d_data) return fail(CDC_EINVAL, "cdc_file_verify_device: NULL data");
+    const uint64_t common = f->size < len ? f->size : (uint64_t)len;
+    uint64_t diff = ~0ull;
+    if (common) {
+        // The planner's range read of [0, common) with the dataset as its "destination": pieces past the shorter
+        // of the two never exist, so the compare stays inside [d_data, d_data + len).
+        std::vector<HostReq> reqs{
+            HostReq{f, cdc::kReadRange, 0, common, const_cast<uint8_t *>(d_data), common, nullptr}};
+        if ((rc = run_reads(fh->fs, reqs, hip_stream, d_data)) != CDC_OK) return rc;
+        diff = fh->fs->h_tot[8];
+    }
+    if (diff == ~0ull && f->size != len) diff = common;
+    if (first_diff) *first_diff = diff;
+    return diff == ~0ull ? 1 : 0;
+}
+
+int64_t cdc_files_get_to_dedup_ratio(cdc_files_t *fs, const char *name, double dedup_ratio, char *out_name,
+                                     size_t out_cap, void *hip_stream) {
+    if (!fs || !name || (out_cap && !out_name))
+        return fail(CDC_EINVAL, "cdc_files_get_to_dedup_ratio: NULL argument");
+    if (!(dedup_ratio >= 1.0)) return fail(CDC_EINVAL, "dedup ratio must be bigger than 1");  // NaN too
+    if (!std::isfinite(dedup_ratio)) return fail(CDC_EINVAL, "cdc_files_get_to_dedup_ratio: the ratio is not finite");
+    auto it = fs->files.find(name);
+    if (it == fs->files.end()) return fail(CDC_ENOTFOUND, std::string("file with name `") + name + "` not found");
+    FileRec *src = it->second;
+    const cdc::StoreView v = cdc::store_view(fs->store);
+    if (src->n && src->epoch != v.epoch)
+        return fail(CDC_ENOTFOUND, std::string("file layer: the store was cleared since '") + name + "' was written");
+    char suffix[400];  // "%.2f" of the largest double has 312 characters
+    std::snprintf(suffix, sizeof suffix, ".%.2f", dedup_ratio);
+    const std::string new_name = std::string(name) + suffix;
+    FL_TRY(hipSetDevice(v.device));
+    hipStream_t s = stream_of(fs, hip_stream);
+
+    cdc::DeviceScratch mem;
+    FileRec made;  // the new file; its table is freed again unless the call succeeds
+    made.epoch = src->epoch;
+    struct Guard {
+        FileRec *f;
+        ~Guard() {
+            if (f) free_table(f);
+        }
+    } guard{&made};
+    if (src->n >= 2) {
+        // 1. The unique list over all but the last span (the reference's zip with skip(1)).
+        const uint64_t m = src->n - 1;
+        int rc = grow_span_scratch(fs, m);
+        if (rc) return rc;
+        if ((rc = grow_slot_scratch(fs, v.slots)) != CDC_OK) return rc;
+        uint64_t *uidx = nullptr, *ulen = nullptr, *ublock = nullptr, *sidx = nullptr;
+        FL_TRY(mem.alloc(&uidx, m));
+        FL_TRY(mem.alloc(&ulen, m));
+        FL_TRY(mem.alloc(&ublock, cdc::store_scan_blocks(m) + 1));
+        FL_TRY(cdc::launch_files_ratio_unique(src->t, m, fs->d_cnt, fs->d_first, fs->a_val, fs->a_block, uidx, ulen,
+                                              ublock, fs->h_tot + 4, s));
+        FL_TRY(hipStreamSynchronize(s));
+        const uint64_t U = fs->h_tot[4], unique_length = fs->h_tot[5];
+        if (U) {
+            // 2. file_layer.rs:233-237, in f64 as written there (`as usize` saturates).
+            const double want = (double)unique_length * dedup_ratio;
+            const uint64_t total_size = want >= 18446744073709551616.0 ? ~0ull : (uint64_t)want;
+            const double rep = std::ceil((double)U * (1.0 / dedup_ratio));
+            uint64_t R = rep >= 18446744073709551616.0 ? ~0ull : (uint64_t)rep;
+            if (R > U) R = U;  // take(num_repeating) of U entries
+            uint64_t K = 0;
+            if (R) {
+                FL_TRY(cdc::launch_files_ratio_take(ulen, ublock, m, R, total_size, fs->h_tot + 6, s));
+                FL_TRY(hipStreamSynchronize(s));
+                const uint64_t C = fs->h_tot[6], j = fs->h_tot[7];
+                if (C == 0)
+                    return fail(CDC_EINVAL, "cdc_files_get_to_dedup_ratio: the repeating spans are all empty "
+                                            "(the reference's cycle would never end)");
+                if (__builtin_mul_overflow(total_size / C, R, &K) || __builtin_add_overflow(K, j, &K))
+                    return fail(CDC_ENOMEM, "cdc_files_get_to_dedup_ratio: the new span table cannot be allocated");
+            }
+            uint64_t n = 0;
+            if (__builtin_add_overflow(K, U - R, &n) || n > (1ull << 40))
+                return fail(CDC_ENOMEM, "cdc_files_get_to_dedup_ratio: the new span table cannot be allocated");
+            // 3. The new table: gather, scan, write.
+            if (n) {
+                if ((rc = reserve(&made, n, s)) != CDC_OK) return rc;
+                if ((rc = grow_span_scratch(fs, n)) != CDC_OK) return rc;
+                FL_TRY(mem.alloc(&sidx, n));
+                FL_TRY(hipMemsetAsync(fs->d_stat, 0xFF, 8, s));
+                FL_TRY(hipMemsetAsync(fs->d_stat + 1, 0, 8, s));
+                FL_TRY(cdc::launch_files_ratio_gather(src->t, made.t, uidx, K, R, n, sidx, fs->a_val, fs->a_block,
+                                                      fs->d_stat, fs->h_tot, s));
+                FL_TRY(hipMemcpyAsync(fs->h_tot + 2, fs->d_stat, 16, hipMemcpyDeviceToHost, s));
+                FL_TRY(hipStreamSynchronize(s));
+                made.n = n;
+                made.size = fs->h_tot[0];
+                if (fs->h_tot[2] != ~0ull) made.min_len = fs->h_tot[2] + 1;
+                made.zeros = fs->h_tot[3];
+            }
+        }
+    }
+    // HashMap::insert (file_layer.rs:265): the name's old file, if any, is replaced.
+    FileRec *&slot = fs->files[new_name];
+    if (slot) free_table(slot);
+    else slot = new FileRec();
+    *slot = made;
+    guard.f = nullptr;
+    const size_t need = new_name.size() + 1;
+    if (need <= out_cap) std::memcpy(out_name, new_name.c_str(), need);
+    return (int64_t)need;
 }
 
 }  // extern "C"

@@ -32,6 +32,11 @@
 // their bytes (COPY) or their re-chunked sub-chunks (RECHUNK) straight from this
 // arena, and a marking kernel writes the key runs; get then expands a digest
 // into one piece per key and feeds the same copy kernel.
+//
+// Bench fixture (the reference's CDCFixture, src/bench/mod.rs:218-275): verify
+// runs the copy's piece list through compare_kernel -- the same tiles and loads,
+// a comparison in place of the store -- and the size distribution is a
+// max-reduce, a wave-aggregated histogram and a compaction over the slots.
 #include "store.hpp"
 
 namespace cdc {
@@ -341,10 +346,133 @@ __global__ __launch_bounds__(kStThreads) void copy_kernel(const StorePiece *__re
     }
 }
 
+// ---- the compare -----------------------------------------------------------------
+// The same value in every lane, provably so for the compiler.
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// Index of the first byte in which two 16-byte blocks differ; 16 when equal.
+__device__ __forceinline__ uint32_t first_diff16(const u32x4 x, const u32x4 y) {
+    const uint32_t d0 = x.x ^ y.x, d1 = x.y ^ y.y, d2 = x.z ^ y.z, d3 = x.w ^ y.w;
+    if (d0) return (uint32_t)__builtin_ctz(d0) >> 3;
+    if (d1) return 4u + ((uint32_t)__builtin_ctz(d1) >> 3);
+    if (d2) return 8u + ((uint32_t)__builtin_ctz(d2) >> 3);
+    if (d3) return 12u + ((uint32_t)__builtin_ctz(d3) >> 3);
+    return 16u;
+}
+
+// copy_kernel with the store replaced by a comparison: piece p says that the
+// bytes [dst, dst + len) -- the caller's dataset -- should equal [src, src +
+// len) -- the arena.  Same mapping (wave per tile, tiles aligned on dst), same
+// loads: the dst side is read with aligned 16-byte loads strictly inside the
+// piece, the src side through load16, ragged heads and tails bytewise; nothing
+// is written but *diff.  A lane keeps the address of its first differing byte,
+// the wave reduces to the minimum, and one atomicMin per differing wave leaves
+// in *diff the smallest differing offset from `base` (preset to ~0).  A tile
+// that starts at or past the minimum found so far cannot lower it and is
+// skipped; that read is a plain load and changes no result.
+__global__ __launch_bounds__(kStThreads) void compare_kernel(const StorePiece *__restrict__ pieces,
+                                                             const uint64_t *__restrict__ tstart, uint64_t n,
+                                                             const uint64_t *total_ptr, uint64_t base,
+                                                             unsigned long long *diff) {
+    const uint64_t total = *total_ptr;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t wave0 = (uint64_t)blockIdx.x * kStWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t nwaves = (uint64_t)gridDim.x * kStWaves;
+    for (uint64_t w = wave0; w < total; w += nwaves) {
+        uint64_t lo = 0, hi = n;
+        while (hi - lo > 1) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (tstart[mid] <= w) lo = mid;
+            else hi = mid;
+        }
+        const StorePiece p = pieces[lo];
+        const uint64_t end = p.dst + p.len;
+        const uint64_t tb = (p.dst & ~(kStoreAlign - 1)) + (w - tstart[lo]) * kStoreTile;
+        const uint64_t te = tb + kStoreTile < end ? tb + kStoreTile : end;
+        const uint64_t found = uniform64(*reinterpret_cast<const volatile unsigned long long *>(diff));
+        if ((tb > p.dst ? tb : p.dst) - base >= found) continue;  // the same decision in every lane
+        const uint64_t shift = p.src - p.dst;  // arena address = dataset address + shift
+        const uint32_t r = (uint32_t)shift & 15u;
+        uint64_t at = ~0ull;
+        for (uint64_t a = tb + lane * 16; a < te; a += 64 * 16) {
+            if (a >= p.dst && a + 16 <= end) {
+                const uint32_t k = first_diff16(*reinterpret_cast<gload16_t>(a), load16(a + shift, r));
+                if (k < 16u && a + k < at) at = a + k;
+            } else {  // ragged head or tail of the piece
+                const uint64_t b0 = a > p.dst ? a : p.dst, b1 = a + 16 < end ? a + 16 : end;
+                for (uint64_t b = b0; b < b1; ++b)
+                    if (*reinterpret_cast<gload1_t>(b) != *reinterpret_cast<gload1_t>(b + shift)) {
+                        if (b < at) at = b;
+                        break;
+                    }
+            }
+        }
+#pragma unroll
+        for (int k = 1; k < 64; k <<= 1) {
+            const uint64_t o = __shfl_xor(at, k);
+            at = o < at ? o : at;
+        }
+        if (lane == 0 && at != ~0ull) atomicMin(diff, (unsigned long long)(at - base));
+    }
+}
+
 // ---- scrub stage -----------------------------------------------------------------
 // A slot holds a container once a chunk has been recorded as its first insert.
 __device__ __forceinline__ bool occupied(const IndexTable &t, uint64_t s) {
     return t.tag[s] != 0 && t.owner[s] != ~0ull;
+}
+
+// ---- size distribution -----------------------------------------------------------
+// *max_len = the longest container (preset to 0): it sizes the bins.
+__global__ __launch_bounds__(kStThreads) void dist_max_kernel(IndexTable t, unsigned long long *max_len) {
+    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t len = s < t.slots && occupied(t, s) ? t.length[s] : 0;
+#pragma unroll
+    for (int k = 1; k < 64; k <<= 1) {
+        const uint64_t o = __shfl_xor(len, k);
+        len = o > len ? o : len;
+    }
+    if ((threadIdx.x & 63) == 0 && len) atomicMax(max_len, (unsigned long long)len);
+}
+
+// bins[length / adjustment] += 1 per occupied slot.  The wave aggregates first:
+// the lanes that share the leader's bin retire together with one atomic, so a
+// store of equal-length containers (FSChunker) costs one atomic per wave.
+__global__ __launch_bounds__(kStThreads) void dist_hist_kernel(IndexTable t, uint64_t adjustment, uint32_t *bins) {
+    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool todo = s < t.slots && occupied(t, s);
+    const uint64_t bin = todo ? t.length[s] / adjustment : 0;
+    const uint32_t lane = threadIdx.x & 63;
+    unsigned long long left = __ballot(todo);
+    while (left) {
+        const uint32_t leader = (uint32_t)__builtin_ctzll(left);
+        const uint64_t lead_bin = __shfl(bin, (int)leader);
+        const bool mine = todo && bin == lead_bin;
+        const unsigned long long same = __ballot(mine);
+        if (lane == leader) atomicAdd(&bins[lead_bin], (uint32_t)__popcll(same));
+        if (mine) todo = false;
+        left &= ~same;
+    }
+}
+
+__global__ __launch_bounds__(kStThreads) void dist_flag_bins_kernel(const uint32_t *__restrict__ bins, uint64_t nb,
+                                                                    uint64_t *val) {
+    const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < nb) val[b] = bins[b] ? 1 : 0;
+}
+
+// val = exclusive scan of the flags: the non-empty bins in ascending size order.
+__global__ __launch_bounds__(kStThreads) void dist_emit_kernel(const uint32_t *__restrict__ bins, uint64_t nb,
+                                                               const uint64_t *__restrict__ val, uint64_t adjustment,
+                                                               uint64_t *sizes, uint32_t *counts) {
+    const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nb || !bins[b]) return;
+    sizes[val[b]] = b * adjustment;
+    counts[val[b]] = bins[b];
 }
 
 __global__ __launch_bounds__(kStThreads) void scrub_flag_kernel(IndexTable t, const uint8_t *__restrict__ kind,
@@ -591,6 +719,32 @@ hipError_t launch_store_copy(const StorePiece *pieces, const uint64_t *tstart, u
                              const uint64_t *d_total, hipStream_t s) {
     if (!n || !max_tiles) return hipSuccess;
     copy_kernel<<<copy_grid(max_tiles), kStThreads, 0, s>>>(pieces, tstart, n, 0, d_total);
+    return hipGetLastError();
+}
+
+hipError_t launch_store_compare(const StorePiece *pieces, const uint64_t *tstart, uint64_t n, uint64_t max_tiles,
+                                const uint64_t *d_total, uint64_t base, unsigned long long *d_diff, hipStream_t s) {
+    if (!n || !max_tiles) return hipSuccess;
+    compare_kernel<<<copy_grid(max_tiles), kStThreads, 0, s>>>(pieces, tstart, n, d_total, base, d_diff);
+    return hipGetLastError();
+}
+
+hipError_t launch_store_dist_max(const IndexTable &t, unsigned long long *d_max, hipStream_t s) {
+    dist_max_kernel<<<grid_of(t.slots), kStThreads, 0, s>>>(t, d_max);
+    return hipGetLastError();
+}
+
+hipError_t launch_store_dist_bins(const IndexTable &t, uint64_t adjustment, uint32_t *bins, uint64_t n_bins,
+                                  uint64_t *val, uint64_t *block_sums, unsigned long long *d_total, hipStream_t s) {
+    dist_hist_kernel<<<grid_of(t.slots), kStThreads, 0, s>>>(t, adjustment, bins);
+    dist_flag_bins_kernel<<<grid_of(n_bins), kStThreads, 0, s>>>(bins, n_bins, val);
+    scan_exclusive(val, n_bins, block_sums, d_total, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_store_dist_emit(const uint32_t *bins, uint64_t n_bins, const uint64_t *val, uint64_t adjustment,
+                                  uint64_t *d_sizes, uint32_t *d_counts, hipStream_t s) {
+    dist_emit_kernel<<<grid_of(n_bins), kStThreads, 0, s>>>(bins, n_bins, val, adjustment, d_sizes, d_counts);
     return hipGetLastError();
 }
 

@@ -69,6 +69,27 @@ hipError_t launch_store_scan(uint64_t *v, uint64_t n, uint64_t *block_sums, unsi
 hipError_t launch_store_copy(const StorePiece *pieces, const uint64_t *tstart, uint64_t n, uint64_t max_tiles,
                              const uint64_t *d_total, hipStream_t s);
 
+// The compare over the same kind of piece list (cdc_file_verify_device): piece
+// {src, dst, len} says that the caller's bytes at dst should equal the arena's
+// at src.  Nothing is written but *d_diff (device, preset to ~0): the smallest
+// dst - base at which a byte differs.  Loads on the dst side stay inside the
+// pieces; the src side follows the copy's over-read rule.
+hipError_t launch_store_compare(const StorePiece *pieces, const uint64_t *tstart, uint64_t n, uint64_t max_tiles,
+                                const uint64_t *d_total, uint64_t base, unsigned long long *d_diff, hipStream_t s);
+
+// Size distribution (CDCFixture::size_distribution, src/bench/mod.rs:218-232).
+// Step 1: *d_max (preset to 0) = the longest container over the occupied slots.
+hipError_t launch_store_dist_max(const IndexTable &t, unsigned long long *d_max, hipStream_t s);
+// Step 2: bins[length / adjustment] += 1 per occupied slot (bins: n_bins u32,
+// zeroed; aggregated within the wave before the atomics), val = the scanned
+// non-empty flags, *d_total = non-empty bins.  val: n_bins; block_sums:
+// store_scan_blocks(n_bins) + 1.
+hipError_t launch_store_dist_bins(const IndexTable &t, uint64_t adjustment, uint32_t *bins, uint64_t n_bins,
+                                  uint64_t *val, uint64_t *block_sums, unsigned long long *d_total, hipStream_t s);
+// Step 3: the non-empty bins in ascending order: {bin * adjustment, count}.
+hipError_t launch_store_dist_emit(const uint32_t *bins, uint64_t n_bins, const uint64_t *val, uint64_t adjustment,
+                                  uint64_t *d_sizes, uint32_t *d_counts, hipStream_t s);
+
 // ---- scrub stage ---------------------------------------------------------------
 // The base store's view of its containers once a target store is attached
 // (DataContainer, src/system/storage.rs:12-21): kind[slot] = 0 for a chunk, 1

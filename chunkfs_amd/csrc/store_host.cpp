@@ -251,22 +251,6 @@ int64_t put(cdc_store *st, size_t n_streams, const uint8_t *const *d_streams, co
 }
 
 // ---- scrub stage -------------------------------------------------------------------
-// Device memory of one call, freed when the call returns.
-struct Scratch {
-    std::vector<void *> ptrs;
-    ~Scratch() {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-    template <typename T>
-    hipError_t alloc(T **out, uint64_t count) {
-        void *p = nullptr;
-        const hipError_t e = hipMalloc(&p, (count ? count : 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(p);
-        *out = static_cast<T *>(p);
-        return e;
-    }
-};
-
 cdc::ScrubView scrub_view(const cdc_store *st) {
     const cdc_store *t = st->target;
     return cdc::ScrubView{st->sc.kind, st->sc.key_first, st->sc.key_count, st->sc.key_slot, st->sc.key_off,
@@ -402,7 +386,7 @@ int scrub(cdc_store *st, int scrubber, cdc_handle_t *chunker, cdc_scrub_measurem
     if (st->st.unique_chunks == st->target_containers) return finish(0);
 
     // 1. The chunk-kind containers, in slot order.
-    Scratch mem;
+    cdc::DeviceScratch mem;
     const uint64_t slots = st->t.slots;
     uint64_t *val = nullptr, *block = nullptr;
     ST_TRY(mem.alloc(&val, slots));
@@ -542,7 +526,7 @@ int scrub(cdc_store *st, int scrubber, cdc_handle_t *chunker, cdc_scrub_measurem
 }
 
 // Flags over the slots -> ranks; returns the scratch through mem.
-int rank_slots(cdc_store *st, Scratch &mem, int want_kind, uint64_t **val, uint64_t *total, hipStream_t s) {
+int rank_slots(cdc_store *st, cdc::DeviceScratch &mem, int want_kind, uint64_t **val, uint64_t *total, hipStream_t s) {
     uint64_t *block = nullptr;
     ST_TRY(mem.alloc(val, st->t.slots));
     ST_TRY(mem.alloc(&block, cdc::store_scan_blocks(st->t.slots) + 1));
@@ -786,7 +770,7 @@ int64_t cdc_store_iterate_device(cdc_store_t *st, uint8_t *d_digests, uint8_t *d
     }
     ST_TRY(hipSetDevice(st->device));
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : st->stream;
-    Scratch mem;
+    cdc::DeviceScratch mem;
     uint64_t *val = nullptr, n = 0;
     int rc = rank_slots(st, mem, -1, &val, &n, s);
     if (rc) return rc;
@@ -796,6 +780,52 @@ int64_t cdc_store_iterate_device(cdc_store_t *st, uint8_t *d_digests, uint8_t *d
     ST_TRY(hipMemsetAsync(d_key_first + n, 0, 8, s));
     ST_TRY(cdc::launch_store_iterate(st->t, scrub_view(st), val, d_digests, d_kinds, d_lengths, d_key_first, s));
     ST_TRY(cdc::launch_store_scan(d_key_first, n + 1, block, nullptr, s));
+    ST_TRY(hipStreamSynchronize(s));
+    return (int64_t)n;
+}
+
+int64_t cdc_store_size_distribution_device(cdc_store_t *st, uint64_t adjustment, uint64_t *d_sizes,
+                                           uint32_t *d_counts, size_t cap, void *hip_stream) {
+    if (!st) {
+        cdc::set_error("NULL store");
+        return CDC_EINVAL;
+    }
+    if (adjustment == 0) {
+        cdc::set_error("cdc_store_size_distribution_device: adjustment must not be 0");
+        return CDC_EINVAL;
+    }
+    if (cap && (!d_sizes || !d_counts)) {
+        cdc::set_error("cdc_store_size_distribution_device: NULL destination");
+        return CDC_EINVAL;
+    }
+    if (st->st.unique_chunks == 0) return 0;
+    ST_TRY(hipSetDevice(st->device));
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : st->stream;
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(st->d_acc) + 8;
+    ST_TRY(hipMemsetAsync(acc, 0, 8, s));
+    ST_TRY(cdc::launch_store_dist_max(st->t, acc, s));
+    uint64_t max_len = 0;
+    ST_TRY(hipMemcpyAsync(&max_len, acc, 8, hipMemcpyDeviceToHost, s));
+    ST_TRY(hipStreamSynchronize(s));
+    const uint64_t n_bins = max_len / adjustment + 1;
+    cdc::DeviceScratch mem;
+    uint32_t *bins = nullptr;
+    uint64_t *val = nullptr, *block = nullptr;
+    hipError_t e = mem.alloc(&bins, n_bins);
+    if (e == hipSuccess) e = mem.alloc(&val, n_bins);
+    if (e == hipSuccess) e = mem.alloc(&block, cdc::store_scan_blocks(n_bins) + 1);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        cdc::set_error(std::string("chunk store size distribution: bins: ") + hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE;
+    }
+    ST_TRY(hipMemsetAsync(bins, 0, n_bins * 4, s));
+    ST_TRY(cdc::launch_store_dist_bins(st->t, adjustment, bins, n_bins, val, block, acc + 1, s));
+    uint64_t n = 0;
+    ST_TRY(hipMemcpyAsync(&n, acc + 1, 8, hipMemcpyDeviceToHost, s));
+    ST_TRY(hipStreamSynchronize(s));
+    if (n > cap || n == 0) return (int64_t)n;
+    ST_TRY(cdc::launch_store_dist_emit(bins, n_bins, val, adjustment, d_sizes, d_counts, s));
     ST_TRY(hipStreamSynchronize(s));
     return (int64_t)n;
 }
@@ -816,7 +846,7 @@ int64_t cdc_store_keys_device(cdc_store_t *st, uint8_t *d_keys, size_t cap, void
     }
     ST_TRY(hipSetDevice(st->device));
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : st->stream;
-    Scratch mem;
+    cdc::DeviceScratch mem;
     uint64_t *val = nullptr, *block = nullptr;
     ST_TRY(mem.alloc(&val, st->t.slots));
     ST_TRY(mem.alloc(&block, cdc::store_scan_blocks(st->t.slots) + 1));

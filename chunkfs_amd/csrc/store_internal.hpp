@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/chunkfs_amd.h"
 #include "store.hpp"
 
@@ -38,6 +40,22 @@ int64_t store_put_slots(cdc_store *st, const uint8_t *d_data, uint64_t data_len,
 // target store was cleared since; a read that needs a target-kind container
 // must return CDC_ENOTFOUND.
 bool store_scrub_view(const cdc_store *st, ScrubView *view, bool *stale);
+
+// Device memory of one call, freed when the call returns.
+struct DeviceScratch {
+    std::vector<void *> ptrs;
+    ~DeviceScratch() {
+        for (void *p : ptrs) (void)hipFree(p);
+    }
+    template <typename T>
+    hipError_t alloc(T **out, uint64_t count) {
+        void *p = nullptr;
+        const hipError_t e = hipMalloc(&p, (count ? count : 1) * sizeof(T));
+        if (e == hipSuccess) ptrs.push_back(p);
+        *out = static_cast<T *>(p);
+        return e;
+    }
+};
 
 // The device a chunker handle is bound to (capi.cpp).
 int handle_device(const cdc_handle *h);

@@ -36,7 +36,8 @@ extern "C" {
  *    number stays 6): the scrub stage -- cdc_store_set_target,
  *    cdc_store_scrub, cdc_store_scrub_stats, cdc_store_iterate_device,
  *    cdc_store_keys_device, cdc_scrub_measurements_t, cdc_scrub_stats_t,
- *    CDC_SCRUB_*. */
+ *    CDC_SCRUB_*; the bench fixture -- cdc_files_get_to_dedup_ratio,
+ *    cdc_file_verify_device, cdc_store_size_distribution_device. */
 #define CHUNKFS_AMD_ABI_VERSION 6
 
 /* Chunk{offset,length} -- reference src/lib.rs:43-47 (usize fields; u64 here). */
@@ -645,6 +646,68 @@ int64_t cdc_file_hashes_device(cdc_fh_t *fh, uint8_t *d_digests, size_t cap);
  * of distinct digests; a return > cap means nothing was written. */
 int64_t cdc_file_distribution_device(cdc_fh_t *fh, uint8_t *d_digests, uint32_t *d_counts, uint64_t *d_lengths,
                                      size_t cap, void *hip_stream);
+
+/* ---- Bench fixture ------------------------------------------------------------------
+ * What the reference's CDCFixture (src/bench/mod.rs:66-283) needs beyond the
+ * file system calls above, on what is already in HBM: a derived file with a
+ * chosen dedup ratio, verification of a file against a dataset without reading
+ * it back, and the chunk-size histogram of the store.  Stream, epoch and error
+ * conventions are the file layer's and the store's.
+ *
+ * Three refusals the reference does not have: a NaN or infinite ratio (it would
+ * produce an empty or unbounded file), repeating spans that are all empty (its
+ * cycle would never end) and adjustment == 0 (it divides by zero). */
+
+/* FileLayer::get_to_dedup_ratio (file_layer.rs:208-268; FileSystem, mod.rs:170-178):
+ * a new file "{name}.{ratio:.2}" (printf "%.2f") made of the spans of file
+ * `name`, so that its size is about dedup_ratio times its unique bytes.
+ *   unique list: spans 0 .. n-2 of `name` (the last span is left out, as in
+ *     cdc_file_distribution_device), the first occurrence of each digest in
+ *     file order with its length: uniq[0..U), unique_length bytes in all;
+ *   total_size = (uint64)((double)unique_length * ratio),
+ *     R = (uint64)ceil((double)U * (1.0 / ratio)), in IEEE double as written there;
+ *   repeating part: cycle over uniq[0..R), taking entries while the running byte
+ *     sum stays <= total_size (entries of length 0 count): K spans;
+ *   the new file has K + (U - R) spans: span i < K is uniq[i mod R], span
+ *     i >= K is uniq[R + i - K].
+ * It replaces any file of that name (HashMap::insert); open handles on the
+ * replaced file see the new one.  The file layer's deviation applies: a span's
+ * offset is its true byte position in the new file (the reference clones each
+ * span with the offset it had in the source); read_file_complete and the digest
+ * sequence agree with the reference exactly.  The new file shares the source's
+ * store epoch and resolved locations, so it reads in the scrubbed state too.
+ * A source of 0 or 1 spans gives an empty new file.
+ * Returns the bytes the new name needs, its NUL included; a return > out_cap
+ * means the name was NOT written -- the file was still created.
+ * CDC_EINVAL: ratio < 1, NaN or infinite; R >= 1 while the first R unique spans
+ * hold no byte.  CDC_ENOTFOUND: unknown name, or the store was cleared since
+ * the source was written.  CDC_ENOMEM: the new span table cannot be allocated.
+ * A refused call changes nothing. */
+int64_t cdc_files_get_to_dedup_ratio(cdc_files_t *fs, const char *name, double dedup_ratio, char *out_name,
+                                     size_t out_cap, void *hip_stream);
+
+/* CDCFixture::verify (bench/mod.rs:241-275) without the read-back: 1 when the
+ * file's bytes equal d_data[0..len) (DEVICE, any alignment), 0 otherwise.
+ * *first_diff (HOST, nullable) receives the smallest differing byte offset,
+ * min(size, len) when the common prefix is equal but the sizes differ, ~0 when
+ * the two are equal.  The read planner's piece list feeds a compare kernel in
+ * place of the copy: 2 bytes read and none written per file byte.  The call
+ * never reads outside [d_data, d_data + len).  Epochs, stream and errors as
+ * cdc_file_read_complete_device. */
+int64_t cdc_file_verify_device(cdc_fh_t *fh, const uint8_t *d_data, size_t len, uint64_t *first_diff,
+                               void *hip_stream);
+
+/* CDCFixture::size_distribution (bench/mod.rs:218-232): over every occupied
+ * slot of the store, the count per length / adjustment * adjustment, where
+ * length is what the container restores to (as cdc_store_iterate_device
+ * reports it).  Target-kind containers are counted too: the reference's
+ * unwrap_chunk would panic on one, and a CDC fixture has none.  The non-empty
+ * bins go to d_sizes / d_counts (DEVICE, cap entries) in ascending size order.
+ * Returns the bin count; a return > cap means nothing was written.
+ * CDC_EINVAL for adjustment == 0; CDC_ENOMEM if the bins (max length /
+ * adjustment + 1 counters) cannot be allocated. */
+int64_t cdc_store_size_distribution_device(cdc_store_t *st, uint64_t adjustment, uint64_t *d_sizes,
+                                           uint32_t *d_counts, size_t cap, void *hip_stream);
 
 /* ---- Synthetic data -----------------------------------------
  * Fill a DEVICE buffer with the splitmix64 stream: little-endian u64 words,

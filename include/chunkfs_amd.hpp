@@ -254,6 +254,13 @@ class Store {
     int64_t keys_device(uint8_t *d_keys, size_t cap, void *hip_stream = nullptr) {
         return check(cdc_store_keys_device(st_, d_keys, cap, hip_stream));
     }
+    // CDCFixture::size_distribution (bench/mod.rs:218-232): the non-empty bins of
+    // length / adjustment * adjustment in ascending order; returns the bin count,
+    // > cap means nothing was written.  adjustment == 0 throws (CDC_EINVAL).
+    int64_t size_distribution_device(uint64_t adjustment, uint64_t *d_sizes, uint32_t *d_counts, size_t cap,
+                                     void *hip_stream = nullptr) {
+        return check(cdc_store_size_distribution_device(st_, adjustment, d_sizes, d_counts, cap, hip_stream));
+    }
 
   private:
     cdc_store_t *st_ = nullptr;
@@ -307,6 +314,13 @@ class File {
                                 void *hip_stream = nullptr) {
         return check(cdc_file_distribution_device(fh_, d_digests, d_counts, d_lengths, cap, hip_stream));
     }
+    // CDCFixture::verify (bench/mod.rs:241-275) without the read-back: true when
+    // the file equals d_data[0..len); *first_diff (nullable) = the smallest
+    // differing offset, min(size, len) when only the sizes differ, ~0 when equal.
+    bool verify_device(const uint8_t *d_data, size_t len, uint64_t *first_diff = nullptr,
+                       void *hip_stream = nullptr) {
+        return check(cdc_file_verify_device(fh_, d_data, len, first_diff, hip_stream)) != 0;
+    }
     cdc_file_stat_t stat() const {
         cdc_file_stat_t s{};
         check(cdc_file_stat(fh_, &s));
@@ -354,6 +368,15 @@ class Files {
     // Many ranges over many files, planned and copied as one piece list.
     void pread_batch_device(size_t n, const cdc_pread_t *reqs, uint64_t *got, void *hip_stream = nullptr) {
         check(cdc_files_pread_batch_device(fs_, n, reqs, got, hip_stream));
+    }
+    // get_to_dedup_ratio (mod.rs:170-178, file_layer.rs:208-268): derives the file
+    // "{name}.{ratio:.2}" and returns its name; span offsets in it are true byte
+    // positions.  Throws CDC_EINVAL for a ratio < 1, NaN or infinite, and when the
+    // repeating spans are all empty.
+    std::string get_to_dedup_ratio(const std::string &name, double dedup_ratio, void *hip_stream = nullptr) {
+        std::vector<char> buf(name.size() + 400);
+        check(cdc_files_get_to_dedup_ratio(fs_, name.c_str(), dedup_ratio, buf.data(), buf.size(), hip_stream));
+        return std::string(buf.data());
     }
     // clear_database (mod.rs:275-278): no files, an empty store, handles invalid.
     void clear() { check(cdc_files_clear(fs_)); }

@@ -36,6 +36,17 @@ target store, the file written again before every timed scrub:
   (j) cdc_file_read_complete_device and 4 KiB cdc_file_pread_device calls after
       RECHUNK at the default group (about avg / sub-avg times the pieces).
 
+Bench fixture, on the file of (d)-(f), in the same run:
+
+  (k) cdc_file_verify_device of the whole file against its source buffer
+      (range planner + the compare kernel: 2 bytes read, none written per byte);
+  (l) the alternative that needs no new kernel: (e) followed by a device
+      compare of the two buffers (torch.equal) -- compare (k) with it and with
+      (e) and (c);
+  (m) cdc_files_get_to_dedup_ratio at ratio 4 (the derived file is replaced by
+      every call; its span table is allocated inside the call);
+  (n) cdc_store_size_distribution_device at adjustment 1024.
+
 Prints one JSON line; --out also writes it to a file.
 """
 import argparse
@@ -249,6 +260,29 @@ def main():
             state["segments"] += 1
         assert total == n
 
+    diff = ctypes.c_uint64(0)
+    name_buf = ctypes.create_string_buffer(64)
+    d_sizes = torch.empty(64, dtype=torch.int64, device="cuda")
+    d_counts = torch.empty(64, dtype=torch.int32, device="cuda")
+
+    def do_verify():
+        got = L.cdc_file_verify_device(state["w"]._fh, P(buf.data_ptr()), n, ctypes.byref(diff), P(sp))
+        assert got == 1, f"cdc_file_verify_device: {got}, first difference at {diff.value}"
+
+    def do_read_then_compare():
+        do_fread()
+        with torch.cuda.stream(s):
+            assert torch.equal(out, buf)
+
+    def do_ratio():
+        got = L.cdc_files_get_to_dedup_ratio(fsys._h, b"bench", 4.0, name_buf, 64, P(sp))
+        assert got == len(b"bench.4.00") + 1, f"cdc_files_get_to_dedup_ratio: {got}"
+
+    def do_distribution():
+        state["bins"] = L.cdc_store_size_distribution_device(fsys.store._h, 1024, P(d_sizes.data_ptr()),
+                                                             P(d_counts.data_ptr()), 64, P(sp))
+        assert 0 < state["bins"] <= 64, f"cdc_store_size_distribution_device: {state['bins']}"
+
     t_put = timed(do_put, before=store.clear)
     out.zero_()
     t_get = timed(do_get)
@@ -265,6 +299,18 @@ def main():
     t_fsize = timed(do_fsize)
     t_fseg = timed(do_fsegments, before=reopen)
     segments = state["segments"]
+    t_verify = timed(do_verify)
+    t_rcmp = timed(do_read_then_compare)
+    out[n // 2 + 12345] ^= 0xFF  # a verify that finds nothing proves nothing: one changed byte must be named
+    torch.cuda.synchronize()
+    found = L.cdc_file_verify_device(state["w"]._fh, P(out.data_ptr()), n, ctypes.byref(diff), P(sp))
+    if found != 0 or diff.value != n // 2 + 12345:
+        raise SystemExit(f"store_bench: cdc_file_verify_device missed a changed byte ({found}, {diff.value})")
+    t_ratio = timed(do_ratio)
+    derived = fsys.stat(fsys.open_file_readonly("bench.4.00"))
+    t_dist = timed(do_distribution)
+    if int(d_counts[:state["bins"]].sum()) != k:
+        raise SystemExit("store_bench: the size distribution does not count every container")
     if not fsame:
         raise SystemExit("store_bench: cdc_file_read_complete_device did not return the bytes written")
 
@@ -295,6 +341,15 @@ def main():
         "file_read_size_only_ms": med(t_fsize), "file_read_copy_ms": med(t_fread) - med(t_fsize),
         "file_segments": segments, "file_segment_us": med(t_fseg) * 1e3 / segments,
         "file_segment_pass_ms": med(t_fseg), "file_readback_equal": fsame,
+        "verify_ms": med(t_verify), "verify_ms_min_max": [min(t_verify), max(t_verify)],
+        "verify_GiBps": rate(t_verify),
+        "read_then_compare_ms": med(t_rcmp), "read_then_compare_ms_min_max": [min(t_rcmp), max(t_rcmp)],
+        "verify_vs_read_then_compare": med(t_rcmp) / med(t_verify), "verify_vs_file_read": med(t_fread) / med(t_verify),
+        "verify_vs_memcpy": med(t_memcpy) / med(t_verify),
+        "dedup_ratio4_ms": med(t_ratio), "dedup_ratio4_ms_min_max": [min(t_ratio), max(t_ratio)],
+        "dedup_ratio4_spans": derived["spans"], "dedup_ratio4_bytes": derived["size"],
+        "size_distribution_ms": med(t_dist), "size_distribution_ms_min_max": [min(t_dist), max(t_dist)],
+        "size_distribution_bins": state["bins"],
     }
     if not a.no_scrub:
         res.update(scrub_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med, med(t_fread)))
