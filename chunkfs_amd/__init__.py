@@ -13,6 +13,7 @@ include/chunkfs_amd.h (libchunkfs_amd.so, hand-written HIP for gfx950):
                                               SeqChunker (published algorithms; parity
                                               unpinned: cdc-chunkers 0.1.3 absent)
     SuperChunker                              raises NotImplementedError
+    (none: this project's own)                AeChunker, AeMode (asymmetric extremum)
     ChunkStorage::write  system/storage.rs    write_spans()
     Database (digest set) system/database.rs  DedupIndex
     Database + retrieve / read_file_complete  ChunkStore
@@ -40,7 +41,7 @@ SEG_SIZE = MB  # src/lib.rs:39
 __all__ = [
     "KB", "MB", "GB", "SEG_SIZE", "Chunk", "SizeParams", "Chunker", "FastChunker",
     "FSChunker", "RabinChunker", "SuperChunker", "UltraChunker", "LeapChunker",
-    "SeqChunker", "OperationMode", "SeqConfig", "CdcError", "write_spans", "StreamWriter", "version",
+    "SeqChunker", "OperationMode", "SeqConfig", "AeChunker", "AeMode", "CdcError", "write_spans", "StreamWriter", "version",
     "DedupIndex", "ChunkStore", "FileSystem", "FileHandle",
     "CopyScrubber", "DumbScrubber", "RechunkScrubber", "ScrubMeasurements",
 ]
@@ -370,6 +371,41 @@ class SeqChunker(Chunker):
         check(L.cdc_create_seq(self.mode, self.config.seq_length, self.config.jump_trigger,
                                self.config.jump_size, sizes.min, sizes.avg, sizes.max, device, ctypes.byref(h)))
         self._h = h
+        self.device = device
+
+
+class AeMode:
+    """Which extremum AE looks for."""
+    Max = 0
+    Min = 1
+
+
+def ae_default_window(avg):
+    """cdc_ae_default_window (include/chunkfs_amd_cdc_params.h): avg = (e - 1) window."""
+    return max(1, int(avg) * 100000 // 171828)
+
+
+class AeChunker(Chunker):
+    """AE, the asymmetric extremum chunker (Zhang et al., INFOCOM 2015; not in
+    the reference): a cut `window` positions after the first position whose
+    4-byte big-endian value nothing in the window after it beats.  The rule is
+    restated in include/chunkfs_amd.h (cdc_create_ae) and DESIGN.md "AE".
+    window=None takes the default for sizes.avg."""
+
+    _algo = "ae"
+
+    def __init__(self, sizes=None, window=None, mode=AeMode.Max, device=0):
+        if sizes is None:
+            raise TypeError("AeChunker: pass SizeParams explicitly")
+        self.sizes, self.mode = sizes, int(mode)
+        self.window = ae_default_window(sizes.avg) if window is None else int(window)
+        if self.window < 1 or self.window >= 1 << 32:  # (0 would ask the C ABI for the default)
+            raise CdcError(_lib.CDC_EINVAL, "AeChunker: window must be >= 1")
+        L = lib()
+        h = ctypes.c_void_p()
+        check(L.cdc_create_ae(self.mode, self.window, sizes.min, sizes.avg, sizes.max, device, ctypes.byref(h)))
+        self._h = h
+        self._pending = []
         self.device = device
 
 

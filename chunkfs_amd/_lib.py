@@ -19,11 +19,11 @@ CDC_ENOTFOUND = -5
 CDC_EEXIST = -6
 CDC_EPERM = -7
 
-ALGO = {"fast": 0, "fixed": 1, "rabin": 2, "super": 3, "ultra": 4, "leap": 5, "seq": 6}
+ALGO = {"fast": 0, "fixed": 1, "rabin": 2, "super": 3, "ultra": 4, "leap": 5, "seq": 6, "ae": 7}
 
 # Every symbol include/chunkfs_amd.h declares (tests check the export table).
 EXPORTS = [
-    "cdc_create", "cdc_create_seq", "cdc_destroy", "cdc_chunk_data", "cdc_estimate_chunk_count",
+    "cdc_create", "cdc_create_seq", "cdc_create_ae", "cdc_destroy", "cdc_chunk_data", "cdc_estimate_chunk_count",
     "cdc_max_chunk_count", "cdc_describe", "cdc_last_error", "cdc_set_gear", "cdc_set_rabin_poly",
     "cdc_chunk_batch_device", "cdc_chunk_batch_device_async", "cdc_batch_sync", "cdc_batch_max_chunks",
     "cdc_last_timing",
@@ -143,6 +143,8 @@ def lib():
     u32 = ctypes.c_uint32
     L.cdc_create_seq.argtypes = [u32, u32, u32, u32, u32, u32, u32, ctypes.c_int, ctypes.POINTER(P)]
     L.cdc_create_seq.restype = ctypes.c_int
+    L.cdc_create_ae.argtypes = [u32, u32, u32, u32, u32, ctypes.c_int, ctypes.POINTER(P)]
+    L.cdc_create_ae.restype = ctypes.c_int
     L.cdc_destroy.argtypes = [P]
     L.cdc_destroy.restype = None
     L.cdc_chunk_data.argtypes = [P, P, sz, ctypes.POINTER(cdc_chunk_t), sz]

@@ -43,6 +43,19 @@ int cdc_create_seq(uint32_t mode, uint32_t seq_length, uint32_t jump_trigger, ui
     return CDC_OK;
 }
 
+int cdc_create_ae(uint32_t mode, uint32_t window, uint32_t min, uint32_t avg, uint32_t max, int device,
+                  cdc_handle_t **out) {
+    if (!out) {
+        cdc::set_error("cdc_create_ae: out is NULL");
+        return CDC_EINVAL;
+    }
+    cdc::Engine *e = nullptr;
+    const int rc = cdc::Engine::create_ae(mode, window, min, avg, max, device, &e);
+    if (rc != CDC_OK) return rc;
+    *out = new cdc_handle{e};
+    return CDC_OK;
+}
+
 void cdc_destroy(cdc_handle_t *h) {
     if (!h) return;
     delete h->engine;

@@ -69,6 +69,7 @@ int Engine::create(cdc_algo_t algo, uint32_t min, uint32_t avg, uint32_t max,
         const uint32_t seq[4] = {0, CDC_SEQ_LENGTH, CDC_SEQ_JUMP_TRIGGER, CDC_SEQ_JUMP_SIZE};
         return create_walk(algo, seq, min, avg, max, device, out);
     }
+    if (algo == CDC_ALGO_AE) return create_ae(CDC_AE_MODE_MAX, 0, min, avg, max, device, out);
     if (algo != CDC_ALGO_FASTCDC && algo != CDC_ALGO_FIXED) {
         set_error("SuperCDC is not implemented on MI355X: its chunk records (supercdc.rs:10, 37-50) "
                   "follow cdc-chunkers 0.1.3, absent offline (SURVEY.md §8c)");
@@ -1315,13 +1316,20 @@ int Engine::create_seq(const uint32_t seq[4], uint32_t min, uint32_t avg, uint32
     return create_walk(CDC_ALGO_SEQ, seq, min, avg, max, device, out);
 }
 
-int Engine::create_walk(cdc_algo_t algo, const uint32_t seq[4], uint32_t min, uint32_t avg, uint32_t max,
+int Engine::create_ae(uint32_t mode, uint32_t window, uint32_t min, uint32_t avg, uint32_t max, int device,
+                      Engine **out) {
+    const uint32_t cfg[4] = {mode, window, 0, 0};
+    return create_walk(CDC_ALGO_AE, cfg, min, avg, max, device, out);
+}
+
+int Engine::create_walk(cdc_algo_t algo, const uint32_t seq_in[4], uint32_t min, uint32_t avg, uint32_t max,
                         int device, Engine **out) {
     if (!out) {
         set_error("cdc_create: out is NULL");
         return CDC_EINVAL;
     }
     *out = nullptr;
+    uint32_t seq[4] = {seq_in[0], seq_in[1], seq_in[2], seq_in[3]};
     // Size rules (oracle_cdc_check): 0 < min <= avg <= max, and the
     // bytes each rule reads before the first tested position.
     if (min == 0 || min > avg || avg > max || (algo == CDC_ALGO_ULTRA && min < 8) ||
@@ -1333,6 +1341,13 @@ int Engine::create_walk(cdc_algo_t algo, const uint32_t seq[4], uint32_t min, ui
         set_error("invalid SeqCDC config: mode 0/1, seq_length > 0, jump_trigger > 0, jump_size > 0");
         return CDC_EINVAL;
     }
+    if (algo == CDC_ALGO_AE) {  // seq = {mode, window}; window 0: the default for avg
+        if (seq[1] == 0) seq[1] = cdc_ae_default_window(avg);
+        if (seq[0] > 1 || (uint64_t)seq[1] + 1 > max) {
+            set_error("invalid AE config: mode 0 (Max) / 1 (Min), 1 <= window and window + 1 <= max");
+            return CDC_EINVAL;
+        }
+    }
     Engine *e = new Engine();
     e->algo_ = algo;
     e->min_ = min;
@@ -1340,10 +1355,14 @@ int Engine::create_walk(cdc_algo_t algo, const uint32_t seq[4], uint32_t min, ui
     e->max_ = max;
     e->device_ = device;
     const char *name = algo == CDC_ALGO_RABIN ? "RabinCDC" : algo == CDC_ALGO_ULTRA ? "UltraCDC"
-                     : algo == CDC_ALGO_LEAP ? "LeapCDC" : "SeqCDC";
+                     : algo == CDC_ALGO_LEAP ? "LeapCDC" : algo == CDC_ALGO_AE ? "AE" : "SeqCDC";
     char buf[256];
     // impl Debug (rabin.rs:28-32, ultra.rs:24-28, leap.rs:24-28, seq.rs:34-38)
-    if (algo == CDC_ALGO_SEQ)
+    if (algo == CDC_ALGO_AE)
+        std::snprintf(buf, sizeof buf,
+                      "%s, sizes: SizeParams { min: %u, avg: %u, max: %u }, window: %u, mode: %s [MI355X gfx950]", name,
+                      min, avg, max, seq[1], seq[0] ? "Min" : "Max");
+    else if (algo == CDC_ALGO_SEQ)
         std::snprintf(buf, sizeof buf, "%s, sizes: SizeParams { min: %u, avg: %u, max: %u }, mode: %s [MI355X gfx950]",
                       name, min, avg, max, seq[0] ? "Decreasing" : "Increasing");
     else
@@ -1378,6 +1397,10 @@ int Engine::init_walk(const uint32_t *seq) {
     wp.seq_len = seq[1];
     wp.seq_trig = seq[2];
     wp.seq_jump = seq[3];
+    if (algo_ == CDC_ALGO_AE) {  // (create_walk resolved the default window)
+        wp.ae_mode = seq[0];
+        wp.ae_window = seq[1];
+    }
     // Segments of 2^seg_log2 bytes (one lane each) and a warm-up of `warm`
     // bytes; CHUNKFS_AMD_WALK="seg_log2,warm_over_avg" overrides (experiments).
     // Defaults (tools/walk_bench.py sweeps on MI355X): segments of
@@ -1390,11 +1413,12 @@ int Engine::init_walk(const uint32_t *seq) {
     // window (min >= 48), UltraCDC, LeapCDC, and SeqCDC when its run length
     // fits a 64-bit step (seq_length <= 63).  CHUNKFS_AMD_WALK_BYTES=1 forces
     // the byte walks (A/B experiments).
+    // AE has no byte walk: always its R bitmap, CHUNKFS_AMD_WALK_BYTES or not.
     wp.nbm = algo_ == CDC_ALGO_RABIN ? (min_ >= CDC_RABIN_WINDOW ? 1u : 0u)
            : algo_ == CDC_ALGO_ULTRA ? 3u : algo_ == CDC_ALGO_LEAP ? 2u
-           : (wp.seq_len <= 63 ? 1u : 0u);
+           : algo_ == CDC_ALGO_AE ? 1u : (wp.seq_len <= 63 ? 1u : 0u);
     if (const char *b = std::getenv("CHUNKFS_AMD_WALK_BYTES"))
-        if (std::atoi(b) != 0) wp.nbm = 0;
+        if (std::atoi(b) != 0 && algo_ != CDC_ALGO_AE) wp.nbm = 0;
     // Bitmap mode walks with a wave per segment (walk.hip wwalk_kernel), byte
     // mode with a lane per segment (walk_kernel).
     // Lane walks: 32 KiB segments whatever the average (profiles/r02ak).
@@ -1429,6 +1453,7 @@ int Engine::init_walk(const uint32_t *seq) {
             warm_mult = b;
         }
     }
+    if (algo_ == CDC_ALGO_AE && seg_log2_ < 12) seg_log2_ = 12;  // its bitmap pass steps 4 KiB at a time
     wp.warm = warm_mult * avg_;
     // CHUNKFS_AMD_AHEAD="after,max" overrides the run-ahead schedule (experiments).
     if (const char *a = std::getenv("CHUNKFS_AMD_AHEAD")) {
@@ -1523,6 +1548,9 @@ int Engine::ensure_walk_workspace(uint64_t segs, size_t n) {
     if (const char *q = std::getenv("CHUNKFS_AMD_QUIET")) rsum = rsum && std::atoi(q) != 0;
     const size_t oRS = take(rsum ? S * (size_t)wp_.seg_words / 8 * (algo_ == CDC_ALGO_RABIN ? 2 : 1) : 0);  // quiet-run summary
     const size_t oQS = take(rsum ? S : 0);  // and per segment
+    const bool ae = algo_ == CDC_ALGO_AE;  // AE: per-word and per-64-word maxima
+    const size_t oM64 = take(ae ? S * (size_t)wp_.seg_words * 4 : 0);
+    const size_t oM4k = take(ae ? S * (size_t)wp_.seg_words / 64 * 4 : 0);
     const size_t o_ptrs = take(N * 8), o_lens = take(N * 8), o_sb = take((N + 1) * 8);
     (void)hipFree(wws_);
     wws_ = nullptr;
@@ -1550,6 +1578,8 @@ int Engine::ensure_walk_workspace(uint64_t segs, size_t n) {
     wp_.jt8 = jt ? reinterpret_cast<uint16_t *>(b + oJ8) : nullptr;
     wp_.rsum = rsum ? reinterpret_cast<uint64_t *>(b + oRS) : nullptr;
     wp_.qseg = rsum ? reinterpret_cast<uint8_t *>(b + oQS) : nullptr;
+    wp_.ae_m64 = ae ? reinterpret_cast<uint32_t *>(b + oM64) : nullptr;
+    wp_.ae_m4k = ae ? reinterpret_cast<uint32_t *>(b + oM4k) : nullptr;
     d_ptrs_ = reinterpret_cast<const uint8_t **>(b + o_ptrs);
     d_lens_ = reinterpret_cast<uint64_t *>(b + o_lens);
     d_span_base_ = reinterpret_cast<uint64_t *>(b + o_sb);

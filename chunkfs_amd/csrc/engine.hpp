@@ -85,6 +85,10 @@ class Engine {
     // seq_length, jump_trigger, jump_size} (mode 0 increasing, 1 decreasing).
     static int create_seq(const uint32_t seq[4], uint32_t min, uint32_t avg, uint32_t max,
                           int device, Engine **out);
+    // AE (DESIGN.md "AE"): mode 0 = Max, 1 = Min; window 0 = the default
+    // (cdc_ae_default_window).  The pair travels in create_walk's seq[0..1].
+    static int create_ae(uint32_t mode, uint32_t window, uint32_t min, uint32_t avg, uint32_t max, int device,
+                         Engine **out);
     ~Engine();
 
     // chunk_data on a host buffer; with `digests` (32 B per chunk, cap
@@ -186,7 +190,7 @@ class Engine {
     bool wk_any_ = false;     // a walk batch is in flight
     uint64_t wk_seq_ = 0;     // walk batches submitted
     bool walk_async_ = true;  // CHUNKFS_AMD_WALK_ASYNC=0: walk batches complete inside the call
-    uint32_t seq_cfg_[4] = {0, 0, 0, 0};  // create_walk's SeqCDC configuration (for the contexts)
+    uint32_t seq_cfg_[4] = {0, 0, 0, 0};  // create_walk's SeqCDC configuration / AE {mode, window} (for the contexts)
     uint64_t rabin_poly_ = 0;             // set_rabin_poly's polynomial (0: the default), for the contexts
     // One small FastCDC stream in one launch (small.hip): CDC_OK, kSmallFallback
     // (a budget was exceeded: run the regular pipeline) or a CDC_E* code.
@@ -200,7 +204,7 @@ class Engine {
                   uint8_t *feed_dst = nullptr, uint32_t feed_slot = 0);
     int run_fixed(const StreamTable &st, size_t n, const uint64_t *lens,
                   cdc_chunk_t *d_out, uint64_t *first, hipStream_t s);
-    // Rabin / Ultra / Leap / Seq: the segment-walk engine (walk.hip).
+    // Rabin / Ultra / Leap / Seq / AE: the segment-walk engine (walk.hip).
     bool is_walk() const { return algo_ != CDC_ALGO_FASTCDC && algo_ != CDC_ALGO_FIXED; }
     int init_walk(const uint32_t *seq);
     int load_walk_tables(uint64_t rabin_poly);

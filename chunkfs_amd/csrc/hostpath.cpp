@@ -601,6 +601,18 @@ int Engine::write_segment(const uint8_t *data, size_t len) {
         data += n;
         len -= n;
     }
+    // AE reads zeros past the end of the buffer it is given, so its cuts
+    // depend on where StorageWriter::write's buffer (rest ++ this segment)
+    // ends: every segment is chunked as its own buffer, like the reference's
+    // loop, instead of a 256 MiB window at a time.  (A segment larger than the
+    // window counts as several.)
+    if (algo_ == CDC_ALGO_AE && W.fill) {
+        const int rc = write_window(false);
+        if (rc) {
+            W.failed = true;
+            return rc;
+        }
+    }
     W.segments += 1;
     return CDC_OK;
 }

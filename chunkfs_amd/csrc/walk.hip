@@ -9,6 +9,10 @@
 //
 // Kernels, one launch each, all on the handle's stream:
 //   *bits_kernel   per-position predicate bitmaps (data-parallel pass)
+//   ae_max / ae_bits / ae_small_kernel
+//                  AE: the R bitmap, a sliding-window maximum ("AE: the R
+//                  bitmap" below; the rule is this project's restatement,
+//                  DESIGN.md "AE", bitmap mode only)
 //   jtab_kernel    LeapCDC: per-word orbit tables
 //   qseg_kernel    per segment: wholly quiet in which kinds (quiet runs)
 //   wwalk_kernel   wave per segment over the bitmaps: warm-up walk, then the
@@ -1078,9 +1082,37 @@ __device__ uint64_t wcut_leap(const WBm &B, uint64_t s, uint64_t n, const WalkPa
     }
 }
 
+// AE over bitmap 0 (R(p): no better value in (p, p + window], DESIGN.md "AE"):
+// the cut from s is decided by the first R position p* at or after s + skip;
+// p* + window inside the chunk's reach cuts after it, anything else is the
+// clamp.  Only positions whose whole window lies before s + L are asked for,
+// so bits of windows that the stream end clips are never read.
+__device__ uint64_t wcut_ae(const WBm &B, uint64_t s, uint64_t n, const WalkParams &wp, uint32_t lane) {
+    if (n <= wp.min) return n;
+    const uint64_t L = n < wp.max ? n : wp.max;
+    const uint64_t w = wp.ae_window;
+    const uint64_t skip = wp.min > w + 1 ? wp.min - (w + 1) : 0;
+    if (L < skip + w + 1) return L;
+    const uint64_t lo = s + skip, hi = s + L - 1 - w;
+    const uint64_t klo = lo >> 6, khi = hi >> 6;
+    for (uint64_t k0 = klo; k0 <= khi; k0 += 64) {
+        const uint64_t k = k0 + lane;
+        uint64_t x = k <= khi ? B.word(1, 0, k) : 0ull;
+        if (k == klo) x &= ~0ull << (lo & 63);
+        if (k == khi && (hi & 63) != 63) x &= (2ull << (hi & 63)) - 1;
+        const uint64_t m = __ballot(x != 0);
+        if (m) {
+            const uint32_t f = (uint32_t)__builtin_ctzll(m);
+            return (k0 + f) * 64 + (uint64_t)__builtin_ctzll(rdlane64(x, f)) + w + 1 - s;
+        }
+    }
+    return L;
+}
+
 template <int kAlgo>
 __device__ __forceinline__ uint64_t wcut(const WBm &B, uint64_t s, uint64_t n, const WalkParams &wp, uint32_t lane) {
     if constexpr (kAlgo == 2) return wcut_rabin(B, s, n, wp, lane);
+    else if constexpr (kAlgo == 7) return wcut_ae(B, s, n, wp, lane);
     else if constexpr (kAlgo == 6) return wcut_seq(B, s, n, wp, lane);
     else if constexpr (kAlgo == 5) return wcut_leap(B, s, n, wp, lane);
     else return wcut_ultra(B, s, n, wp, lane);
@@ -2033,6 +2065,229 @@ __global__ __launch_bounds__(256) void lbits_kernel(const StreamTable st, const 
     }
 }
 
+// ---- AE: the R bitmap --------------------------------------------------------
+// R(p): no value in (p, p + window] -- as far as the stream reaches -- is
+// better than v(p), v(p) the big-endian 32-bit value of the four bytes at p
+// (bytes at or past the stream end read 0).  Min mode runs as Max mode on the
+// complemented values, so "better" is ">" throughout and 0 is the value that
+// never wins (positions past the stream end).
+//
+// Windows of up to kAeSmallWindow positions: ae_small_kernel compares every
+// position with its window directly, values staged in LDS.
+// Wider windows (always past the end of the position's own 64-position word),
+// two launches:
+//   ae_max_kernel   per word the maximum of its values (ae_m64), per 64 words
+//                   the maximum of those (ae_m4k);
+//   ae_bits_kernel  lane per word: the word's suffix maxima are the only
+//                   positions that can be R; each survivor, lowest value first,
+//                   is checked against the maxima of the following whole words
+//                   (64 at a time where ae_m4k allows) and, where the window's
+//                   last, partial word holds a larger maximum, against that
+//                   part's values themselves.  The survivors' values rise from
+//                   the word's end to its start, so one forward scan of the
+//                   maxima serves all of them: window / 64 + 64 steps per word
+//                   at the worst (constant data), a few on random data.
+// ae_bits_kernel loads the stream a second time instead of keeping 4 bytes per
+// position between the launches.
+constexpr uint32_t kAeSmallWindow = 62;
+constexpr uint32_t kAeTile = 1024;  // positions per step of ae_small_kernel
+constexpr uint32_t kAePre = 3;      // ae_bits_kernel: following words whose maxima are loaded up front
+
+// v(4 k + r) from the dwords lo (bytes 4 k .. 4 k + 3) and hi (the next four).
+__device__ __forceinline__ uint32_t ae_val(uint32_t lo, uint32_t hi, uint32_t r) {
+    return __builtin_bswap32(__builtin_amdgcn_alignbit(hi, lo, 8 * r));
+}
+
+// The 68 bytes from p0 (a multiple of 64) as dwords.
+__device__ __forceinline__ void ae_load(uint32_t (&d)[17], const uint8_t *base, uint64_t len, uint64_t p0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint4 v = load16_guarded(base, p0 + 16 * k, len);
+        d[4 * k] = v.x; d[4 * k + 1] = v.y; d[4 * k + 2] = v.z; d[4 * k + 3] = v.w;
+    }
+    d[16] = load16_guarded(base, p0 + 64, len).x;
+}
+
+// Maximum of the (flipped) values of positions [a, b], b < len.
+__device__ uint32_t ae_span_max(const uint8_t *base, uint64_t len, uint64_t a, uint64_t b, uint32_t flip) {
+    uint32_t m = 0;
+    for (uint64_t q = a; q <= b; ++q) {
+        uint32_t v = 0;
+        for (uint32_t j = 0; j < 4; ++j) v = (v << 8) | (q + j < len ? (uint32_t)((gw_u8 *)base)[q + j] : 0u);
+        m = max(m, v ^ flip);
+    }
+    return m;
+}
+
+__global__ __launch_bounds__(256) void ae_max_kernel(const StreamTable st, const WalkParams wp) {
+    const uint32_t lane = threadIdx.x & 63;
+    Piece pc;
+    if (!piece_of(st, wp, (uint64_t)blockIdx.x * 4 + wave_id(), pc)) return;
+    const uint64_t len = st.lens[pc.si];
+    const uint8_t *base = st.ptrs[pc.si];
+    const uint32_t flip = wp.ae_mode ? ~0u : 0u;
+    const uint32_t reps = (uint32_t)((1ull << wp.piece_log2) >> 12);
+    for (uint32_t it = 0; it < reps; ++it) {
+        const uint64_t P0 = pc.off + 4096ull * it;
+        if (P0 >= len) return;  // (wave-uniform)
+        const uint64_t p0 = P0 + 64ull * lane;
+        uint32_t m = 0;
+        if (p0 < len) {
+            uint32_t d[17];
+            ae_load(d, base, len, p0);
+            const uint32_t nv = (uint32_t)min(len - p0, (uint64_t)64);
+#pragma unroll
+            for (int i = 0; i < 64; ++i) {
+                const uint32_t v = ae_val(d[i >> 2], d[(i >> 2) + 1], i & 3) ^ flip;
+                m = max(m, (uint32_t)i < nv ? v : 0u);
+            }
+            wp.ae_m64[pc.wbase + 64ull * it + lane] = m;
+        }
+        uint32_t wm = m;
+        for (int o = 32; o; o >>= 1) wm = max(wm, (uint32_t)__shfl_xor((int)wm, o));
+        if (lane == 0) wp.ae_m4k[(pc.wbase >> 6) + it] = wm;
+    }
+}
+
+__global__ __launch_bounds__(256) void ae_bits_kernel(const StreamTable st, const WalkParams wp) {
+    // the lane's 17 dwords again, for the survivors' values (stride 17: the
+    // lanes' slots start on different banks)
+    __shared__ uint32_t stash[256 * 17];
+    const uint32_t lane = threadIdx.x & 63;
+    Piece pc;
+    if (!piece_of(st, wp, (uint64_t)blockIdx.x * 4 + wave_id(), pc)) return;
+    const uint64_t len = st.lens[pc.si];
+    const uint8_t *base = st.ptrs[pc.si];
+    const uint32_t flip = wp.ae_mode ? ~0u : 0u;
+    const uint64_t w = wp.ae_window;
+    const uint64_t sbase = st.span_base[pc.si] * (uint64_t)wp.seg_words;  // the stream's first word
+    const uint32_t *m64 = wp.ae_m64 + sbase;
+    const uint32_t *m4k = wp.ae_m4k + (sbase >> 6);
+    uint32_t *my = stash + threadIdx.x * 17;
+    const uint64_t nk = (len + 63) >> 6;
+    const uint32_t npre = (uint32_t)min((w + 1) / 64 - 1, (uint64_t)kAePre);
+    const uint32_t reps = (uint32_t)((1ull << wp.piece_log2) >> 12);
+    for (uint32_t it = 0; it < reps; ++it) {
+        const uint64_t P0 = pc.off + 4096ull * it;
+        if (P0 >= len) return;  // (wave-uniform)
+        const uint64_t p0 = P0 + 64ull * lane;
+        if (p0 >= len) continue;
+        uint32_t d[17];
+        ae_load(d, base, len, p0);
+        // The next npre words lie inside the window of every position of this
+        // word (window >= 64 (npre + 1) - 1; past the stream end: nothing to
+        // beat), so their maxima -- loaded with the bytes -- thin the
+        // survivors out before any scan: ~0.7 / 0.4 / 0.3 survivors per word
+        // on random data with 1 / 2 / 3 words, 4.7 with none.
+        const uint64_t k = p0 >> 6;
+        uint32_t mpre = 0;
+#pragma unroll
+        for (uint32_t t = 1; t <= kAePre; ++t)
+            if (t <= npre && k + t < nk) mpre = max(mpre, m64[k + t]);
+#pragma unroll
+        for (int q = 0; q < 17; ++q) my[q] = d[q];
+        const uint32_t nv = (uint32_t)min(len - p0, (uint64_t)64);
+        // survivors: v(i) >= every later value of the word and of those words
+        uint32_t sm = mpre, c0 = 0, c1 = 0;
+#pragma unroll
+        for (int i = 63; i >= 0; --i) {
+            const uint32_t v = ae_val(d[i >> 2], d[(i >> 2) + 1], i & 3) ^ flip;
+            const bool in = (uint32_t)i < nv;
+            const uint32_t bit = in && v >= sm ? 1u : 0u;
+            if (i < 32) c0 |= bit << i;
+            else c1 |= bit << (i - 32);
+            sm = in ? max(sm, v) : sm;
+        }
+        uint64_t c = ((uint64_t)c1 << 32) | c0, r = 0;
+        uint64_t j = k + 1 + npre;  // every word of [k + 1, j) has a maximum <= the survivor's value
+        uint64_t jc = ~0ull;
+        uint32_t mjc = 0;
+        auto m64_at = [&](uint64_t jj) -> uint32_t {
+            if (jj != jc) {
+                jc = jj;
+                mjc = m64[jj];
+            }
+            return mjc;
+        };
+        while (c) {
+            const uint32_t i = 63u - (uint32_t)__builtin_clzll(c);
+            c &= ~(1ull << i);
+            const uint32_t x = ae_val(my[i >> 2], my[(i >> 2) + 1], i & 3) ^ flip;
+            const uint64_t qe = min(p0 + i + w, len - 1);  // the window's last position
+            const uint64_t kl = qe >> 6;
+            bool pass = true;
+            if (kl != k) {
+                while (j < kl) {
+                    if ((j & 63) == 0 && j + 64 <= kl && m4k[j >> 6] <= x) {
+                        j += 64;
+                    } else if (j + 8 <= kl) {
+                        // eight maxima per round trip (a position that is R
+                        // scans its whole window: one dependent load per word
+                        // made the pass 1.94 ms per GiB at window 4767)
+                        uint32_t a[8];
+#pragma unroll
+                        for (uint32_t t = 0; t < 8; ++t) a[t] = m64[j + t];
+                        uint32_t t8 = 8;
+#pragma unroll
+                        for (uint32_t t = 8; t-- > 0;) t8 = a[t] > x ? t : t8;
+                        j += t8;
+                        if (t8 < 8) break;
+                    } else if (m64_at(j) <= x) {
+                        ++j;
+                    } else {
+                        break;
+                    }
+                }
+                if (j < kl) pass = false;
+                else if (j == kl) {
+                    if (m64_at(kl) <= x) ++j;
+                    else pass = ae_span_max(base, len, kl << 6, qe, flip) <= x;
+                }
+            }
+            if (pass) r |= 1ull << i;
+        }
+        wp.bm[pc.wbase + 64ull * it + lane] = r;
+    }
+}
+
+__global__ __launch_bounds__(256) void ae_small_kernel(const StreamTable st, const WalkParams wp) {
+    __shared__ uint32_t vs_all[4][kAeTile + 64];
+    const uint32_t lane = threadIdx.x & 63;
+    Piece pc;
+    if (!piece_of(st, wp, (uint64_t)blockIdx.x * 4 + wave_id(), pc)) return;
+    uint32_t *vs = vs_all[wave_id()];
+    const uint64_t len = st.lens[pc.si];
+    const uint8_t *base = st.ptrs[pc.si];
+    const uint32_t flip = wp.ae_mode ? ~0u : 0u;
+    const uint32_t w = wp.ae_window;  // <= kAeSmallWindow
+    const uint32_t steps = (uint32_t)((1ull << wp.piece_log2) / kAeTile);
+    for (uint32_t t = 0; t < steps; ++t) {
+        const uint64_t P0 = pc.off + (uint64_t)kAeTile * t;
+        if (P0 >= len) return;  // (wave-uniform)
+        // values of [P0, P0 + kAeTile + 64), 16 positions per lane and round
+        for (uint32_t ch = lane; ch < (kAeTile + 64) / 16; ch += 64) {
+            const uint64_t a = P0 + 16ull * ch;
+            const uint4 A = load16_guarded(base, a, len);
+            const uint32_t d[5] = {A.x, A.y, A.z, A.w, load16_guarded(base, a + 16, len).x};
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                vs[16 * ch + q] = a + q < len ? ae_val(d[q >> 2], d[(q >> 2) + 1], q & 3) ^ flip : 0u;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (uint32_t u = 0; u < kAeTile / 64; ++u) {
+            const uint32_t idx = 64 * u + lane;
+            const uint32_t x = vs[idx];
+            bool ok = P0 + idx < len;
+            for (uint32_t q = 1; q <= w; ++q) ok = ok && vs[idx + q] <= x;
+            const uint64_t m = __ballot(ok);
+            if (lane == 0 && P0 + 64ull * u < len) wp.bm[pc.wbase + (kAeTile / 64) * t + u] = m;
+        }
+        __builtin_amdgcn_wave_barrier();  // (the values are rewritten next step)
+    }
+}
+
 // ---- prefix and output -----------------------------------------------------
 
 __device__ __forceinline__ uint64_t block_exclusive(uint64_t v, uint64_t *sh, uint64_t &total) {
@@ -2268,7 +2523,12 @@ hipError_t launch_bits(const StreamTable &st, const WalkParams &wp, hipStream_t 
         lbits_kernel<<<(unsigned)((pieces + 3) / 4), 256, 0, s>>>(st, wp);
     else if (wp.algo == 5) bits_kernel<5><<<blocks, kWalkBlock, 0, s>>>(st, wp);
     else if (wp.algo == 6) bits_kernel<6><<<blocks, kWalkBlock, 0, s>>>(st, wp);
-    else return hipErrorInvalidValue;
+    else if (wp.algo == 7 && wp.piece_log2 >= 12 && wp.ae_window <= kAeSmallWindow)
+        ae_small_kernel<<<(unsigned)((pieces + 3) / 4), 256, 0, s>>>(st, wp);
+    else if (wp.algo == 7 && wp.piece_log2 >= 12 && wp.ae_m64 && wp.ae_m4k) {
+        ae_max_kernel<<<(unsigned)((pieces + 3) / 4), 256, 0, s>>>(st, wp);
+        ae_bits_kernel<<<(unsigned)((pieces + 3) / 4), 256, 0, s>>>(st, wp);
+    } else return hipErrorInvalidValue;
     if (wp.algo == 5 && wp.jt && wp.piece_log2 >= 12)  // LeapCDC word tables
         jtab_kernel<<<(unsigned)((pieces + 3) / 4), 256, 0, s>>>(st, wp);
     if (wp.rsum && wp.qseg) {
@@ -2287,6 +2547,7 @@ hipError_t launch_walk(const StreamTable &st, const WalkParams &wp, const WalkSt
         if (wp.algo == 2) wwalk_kernel<2><<<blocks, 256, 0, s>>>(st, wp, ws);
         else if (wp.algo == 5) wwalk_kernel<5><<<blocks, 256, 0, s>>>(st, wp, ws);
         else if (wp.algo == 6) wwalk_kernel<6><<<blocks, 256, 0, s>>>(st, wp, ws);
+        else if (wp.algo == 7) wwalk_kernel<7><<<blocks, 256, 0, s>>>(st, wp, ws);
         else wwalk_kernel<4><<<blocks, 256, 0, s>>>(st, wp, ws);
         return hipGetLastError();
     }
@@ -2323,6 +2584,7 @@ hipError_t launch_fix(const StreamTable &st, const WalkParams &wp, const WalkSta
         if (wp.algo == 2) wfix_kernel<2><<<blocks, 256, 0, s>>>(st, wp, ws);
         else if (wp.algo == 5) wfix_kernel<5><<<blocks, 256, 0, s>>>(st, wp, ws);
         else if (wp.algo == 6) wfix_kernel<6><<<blocks, 256, 0, s>>>(st, wp, ws);
+        else if (wp.algo == 7) wfix_kernel<7><<<blocks, 256, 0, s>>>(st, wp, ws);
         else wfix_kernel<4><<<blocks, 256, 0, s>>>(st, wp, ws);
         return hipGetLastError();
     }
@@ -2335,6 +2597,7 @@ hipError_t launch_serial(const StreamTable &st, const WalkParams &wp, const Walk
         if (wp.algo == 2) wserial_kernel<2><<<blocks, 256, 0, s>>>(st, wp, ws);
         else if (wp.algo == 5) wserial_kernel<5><<<blocks, 256, 0, s>>>(st, wp, ws);
         else if (wp.algo == 6) wserial_kernel<6><<<blocks, 256, 0, s>>>(st, wp, ws);
+        else if (wp.algo == 7) wserial_kernel<7><<<blocks, 256, 0, s>>>(st, wp, ws);
         else wserial_kernel<4><<<blocks, 256, 0, s>>>(st, wp, ws);
         return hipGetLastError();
     }

@@ -1,5 +1,7 @@
 // walk.hpp -- the segment-walk engine for Rabin / UltraCDC / LeapCDC / SeqCDC
-// (reference src/chunkers/{rabin,ultra,leap,seq}.rs; DESIGN.md "Segment walk").
+// (reference src/chunkers/{rabin,ultra,leap,seq}.rs; DESIGN.md "Segment walk")
+// and AE (this project's restatement of the published rule, DESIGN.md "AE";
+// bitmap mode only).
 //
 // Every stream of the batch is cut into segments of 2^seg_log2 bytes (a chunk
 // may span whole segments: they then hold no start, E = X).  One wave (bitmap
@@ -37,7 +39,7 @@ __host__ __device__ __forceinline__ int round_verdict(unsigned long long ch, uns
 constexpr unsigned kFirstGroupRounds = 1;
 
 struct WalkParams {
-    uint32_t algo;            // cdc_algo_t: 2 rabin, 4 ultra, 5 leap, 6 seq
+    uint32_t algo;            // cdc_algo_t: 2 rabin, 4 ultra, 5 leap, 6 seq, 7 ae
     uint32_t min, avg, max;
     uint64_t rabin_mask;      // (1 << round(log2 avg)) - 1
     uint32_t rabin_shift;     // deg(poly) - 8
@@ -51,7 +53,7 @@ struct WalkParams {
     // per 64-bit word:
     // word k of bitmap b of segment g at bm[(g * seg_words + k) * nbm + b].
     uint64_t *bm;
-    uint32_t nbm;             // 0 = byte mode (lane walks); Rabin, Seq 1, Ultra 3 (mask_s, mask_l, 8-byte repeat), Leap 2
+    uint32_t nbm;             // 0 = byte mode (lane walks); Rabin, Seq, AE 1, Ultra 3 (mask_s, mask_l, 8-byte repeat), Leap 2
     uint32_t seg_words;       // 64-bit words per segment and bitmap (segment bytes / 64)
     uint32_t piece_log2;      // the data-parallel passes run over pieces of 2^piece_log2 bytes (<= segment)
     uint32_t bits_fine;       // bitmap pass: lane per 64-position word (Ultra, Leap, Seq)
@@ -78,6 +80,13 @@ struct WalkParams {
     // pass.  A fix-up round lets one chain cross a stretch of such segments
     // whole (walk.hip serial_run); nullptr with rsum.
     uint8_t *qseg;
+    // AE: the window in positions (>= 1, window + 1 <= max) and the mode (0 =
+    // Max, 1 = Min), and -- for windows wider than a 64-position word -- the
+    // bitmap pass's auxiliary maxima (walk.hip "AE: the R bitmap"): per bitmap
+    // word the maximum value of its positions, ae_m64[g * seg_words + k], and
+    // per 64 words the maximum of those, ae_m4k[(g * seg_words + k) >> 6].
+    uint32_t ae_window, ae_mode;
+    uint32_t *ae_m64, *ae_m4k;
 };
 
 struct WalkState {

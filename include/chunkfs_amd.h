@@ -37,7 +37,8 @@ extern "C" {
  *    cdc_store_scrub, cdc_store_scrub_stats, cdc_store_iterate_device,
  *    cdc_store_keys_device, cdc_scrub_measurements_t, cdc_scrub_stats_t,
  *    CDC_SCRUB_*; the bench fixture -- cdc_files_get_to_dedup_ratio,
- *    cdc_file_verify_device, cdc_store_size_distribution_device. */
+ *    cdc_file_verify_device, cdc_store_size_distribution_device; the AE
+ *    chunker -- CDC_ALGO_AE, cdc_create_ae. */
 #define CHUNKFS_AMD_ABI_VERSION 6
 
 /* Chunk{offset,length} -- reference src/lib.rs:43-47 (usize fields; u64 here). */
@@ -55,7 +56,9 @@ typedef enum cdc_algo {
     CDC_ALGO_ULTRA = 4,   /* UltraChunker (src/chunkers/ultra.rs)    -- parity unpinned */
     CDC_ALGO_LEAP = 5,    /* LeapChunker  (src/chunkers/leap.rs)     -- leap structure of the paper,
                              stand-in eligibility function (chunkfs_amd_cdc_params.h) */
-    CDC_ALGO_SEQ = 6      /* SeqChunker   (src/chunkers/seq.rs)      -- parity unpinned */
+    CDC_ALGO_SEQ = 6,     /* SeqChunker   (src/chunkers/seq.rs)      -- parity unpinned */
+    CDC_ALGO_AE = 7       /* AE, asymmetric extremum (not in the reference: this project's
+                             restatement of the published rule, DESIGN.md "AE") */
 } cdc_algo_t;
 
 #define CDC_OK 0
@@ -83,6 +86,8 @@ typedef struct cdc_handle cdc_handle_t;
  *                     Sizes: 0 < min <= avg <= max; Ultra min >= 8, Leap min >= 32.
  *   CDC_ALGO_SEQ:     SeqChunker with OperationMode::Increasing and the default
  *                     Config (cdc_create_seq for the full constructor).
+ *   CDC_ALGO_AE:      AE in Max mode with the default window (cdc_create_ae
+ *                     for the full constructor).
  *   CDC_ALGO_SUPER:   CDC_ENOTSUP.
  * Returns CDC_OK and *out, or a negative code. */
 int cdc_create(cdc_algo_t algo, uint32_t min, uint32_t avg, uint32_t max,
@@ -95,6 +100,25 @@ int cdc_create(cdc_algo_t algo, uint32_t min, uint32_t avg, uint32_t max,
 int cdc_create_seq(uint32_t mode, uint32_t seq_length, uint32_t jump_trigger,
                    uint32_t jump_size, uint32_t min, uint32_t avg, uint32_t max,
                    int device, cdc_handle_t **out);
+
+/* AE, the asymmetric extremum chunker (Zhang et al., INFOCOM 2015), restated
+ * by this project (parity with any crate unpinned).  v(i) is the big-endian
+ * 32-bit value of the bytes i .. i+3, bytes at or past the end of the buffer of
+ * the call (in a device batch: of the stream) reading 0; "better" is > in Max
+ * mode (mode 0) and < in Min mode (mode 1).  A chunk starting at s with n
+ * bytes left: n <= min ends it at n; otherwise, with L = min(n, max) and M
+ * starting at s + (min > window + 1 ? min - (window + 1) : 0), positions i =
+ * M+1 .. s+L-1 in order either move M to i (v(i) strictly better than v(M)) or,
+ * at i == M + window, cut after i; no such i: the chunk is L long.
+ * window == 0 takes the default, max(1, avg * 100000 / 171828)
+ * (cdc_ae_default_window in chunkfs_amd_cdc_params.h: avg = (e - 1) window).
+ * CDC_EINVAL unless 0 < min <= avg <= max, window + 1 <= max and mode <= 1.
+ * The zero padding makes the last three values of a buffer depend on where it
+ * ends: the streaming write path (1 MiB segments, each its own buffer) follows
+ * the reference's StorageWriter loop over this rule and is NOT claimed equal
+ * to one cdc_chunk_data over the whole write. */
+int cdc_create_ae(uint32_t mode, uint32_t window, uint32_t min, uint32_t avg,
+                  uint32_t max, int device, cdc_handle_t **out);
 
 /* Drop(Chunker). */
 void cdc_destroy(cdc_handle_t *h);

@@ -8,6 +8,7 @@
 //   FastChunker                     chunkers/fast.rs        chunkfs_amd::FastChunker
 //   FSChunker                       chunkers/fixed_size.rs  chunkfs_amd::FSChunker
 //   Rabin/Ultra/Leap/SeqChunker     chunkers/{rabin,ultra,leap,seq}.rs  same names
+//   (none: this project's own)      --                                  AeChunker, AeMode
 //   ChunkStorage::write spans       system/storage.rs:78-103  Chunker::write_spans
 //   Database + ChunkStorage::retrieve  system/database.rs, storage.rs:141-157  chunkfs_amd::Store
 //   FileSystem / FileLayer / FileHandle  system/mod.rs, file_layer.rs  chunkfs_amd::Files, File
@@ -183,6 +184,29 @@ class SeqChunker : public Chunker {
         check(cdc_create_seq((uint32_t)mode, config.seq_length, config.jump_trigger, config.jump_size,
                              (uint32_t)sizes.min, (uint32_t)sizes.avg, (uint32_t)sizes.max, device, &h_));
     }
+};
+
+// AE, the asymmetric extremum chunker (include/chunkfs_amd.h cdc_create_ae;
+// not in the reference).  window 0 = the default for sizes.avg.
+enum class AeMode : uint32_t { Max = 0, Min = 1 };
+
+class AeChunker : public Chunker {
+  public:
+    explicit AeChunker(SizeParams sizes, uint32_t window = 0, AeMode mode = AeMode::Max, int device = 0)
+        : Chunker(), window_(window), mode_(mode) {
+        if (!window_) {
+            const uint64_t w = (uint64_t)sizes.avg * 100000ull / 171828ull;
+            window_ = w ? (uint32_t)w : 1u;
+        }
+        check(cdc_create_ae((uint32_t)mode, window_, (uint32_t)sizes.min, (uint32_t)sizes.avg, (uint32_t)sizes.max,
+                            device, &h_));
+    }
+    uint32_t window() const { return window_; }
+    AeMode mode() const { return mode_; }
+
+  private:
+    uint32_t window_;
+    AeMode mode_;
 };
 
 // ChunkerRef (src/lib.rs:89): shared handle to one chunker.

@@ -88,6 +88,17 @@ static const uint32_t CDC_LEAP_THRESHOLD[33] = {
 #define CDC_SEQ_JUMP_TRIGGER 50u
 #define CDC_SEQ_JUMP_SIZE 256u
 
+/* AE (asymmetric extremum): the operation mode (which extremum) and the
+ * default window for an average size, avg = (e - 1) * window with min ignored
+ * (e - 1 = 1.71828), never below 1. */
+#define CDC_AE_MODE_MAX 0u
+#define CDC_AE_MODE_MIN 1u
+static inline uint32_t cdc_ae_default_window(uint32_t avg)
+{
+    const uint64_t w = (uint64_t)avg * 100000ull / 171828ull;
+    return w ? (uint32_t)w : 1u;
+}
+
 /* round(log2(x)) in integers (x >= 1), shared so host and oracle agree. */
 static inline uint32_t cdc_log2_round(uint64_t x)
 {
