@@ -16,10 +16,10 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "../../include/chunkfs_amd_cdc_params.h"
 #include "../../include/chunkfs_amd_tables.h"
 #include "fastcdc.hpp"
 #include "sha256.hpp"
+#include "walk_engine.hpp"
 
 namespace cdc {
 
@@ -36,27 +36,10 @@ constexpr uint32_t kMaxSpanLog2 = 17;  // ... and at most 128 KiB unless the max
 constexpr uint32_t kMinimumMin = 64, kMinimumMax = 1048576;
 constexpr uint32_t kAverageMin = 256, kAverageMax = 4194304;
 constexpr uint32_t kMaximumMin = 1024, kMaximumMax = 16777216;
-
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-uint32_t ceil_log2(uint64_t x) {
-    uint32_t r = 0;
-    while ((1ull << r) < x) ++r;
-    return r;
-}
 }  // namespace
 
 void set_error(const std::string &msg) { g_last_error = msg; }
 const char *last_error() { return g_last_error.c_str(); }
-
-#define HIP_TRY(expr)                                                          \
-    do {                                                                       \
-        hipError_t e_ = (expr);                                                \
-        if (e_ != hipSuccess) {                                                \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(e_));      \
-            return CDC_EDEVICE;                                                \
-        }                                                                      \
-    } while (0)
 
 int Engine::create(cdc_algo_t algo, uint32_t min, uint32_t avg, uint32_t max,
                    int device, Engine **out) {
@@ -65,11 +48,11 @@ int Engine::create(cdc_algo_t algo, uint32_t min, uint32_t avg, uint32_t max,
         return CDC_EINVAL;
     }
     *out = nullptr;
-    if (algo == CDC_ALGO_RABIN || algo == CDC_ALGO_ULTRA || algo == CDC_ALGO_LEAP || algo == CDC_ALGO_SEQ) {
-        const uint32_t seq[4] = {0, CDC_SEQ_LENGTH, CDC_SEQ_JUMP_TRIGGER, CDC_SEQ_JUMP_SIZE};
-        return create_walk(algo, seq, min, avg, max, device, out);
+    if (algo == CDC_ALGO_RABIN || algo == CDC_ALGO_ULTRA || algo == CDC_ALGO_LEAP || algo == CDC_ALGO_SEQ ||
+        algo == CDC_ALGO_AE) {
+        WalkConfig cfg;  // (the rule's defaults)
+        return create_walk(algo, cfg, min, avg, max, device, out);
     }
-    if (algo == CDC_ALGO_AE) return create_ae(CDC_AE_MODE_MAX, 0, min, avg, max, device, out);
     if (algo != CDC_ALGO_FASTCDC && algo != CDC_ALGO_FIXED) {
         set_error("SuperCDC is not implemented on MI355X: its chunk records (supercdc.rs:10, 37-50) "
                   "follow cdc-chunkers 0.1.3, absent offline (SURVEY.md §8c)");
@@ -197,81 +180,19 @@ int Engine::init() {
     num_cus_ = prop.multiProcessorCount;
     HIP_TRY(hipStreamCreateWithFlags(&own_stream_, hipStreamNonBlocking));
     for (auto &ev : ev_) HIP_TRY(hipEventCreate(&ev));
-    for (auto &slot : tev_)
-        for (auto &ev : slot) HIP_TRY(hipEventCreate(&ev));
+    if (algo_ == CDC_ALGO_FASTCDC)  // (no other handle records or reads the ring: timing_back refuses it)
+        for (auto &slot : tev_)
+            for (auto &ev : slot) HIP_TRY(hipEventCreate(&ev));
     HIP_TRY(hipMalloc(&d_gear_, 256 * sizeof(uint64_t)));
     HIP_TRY(hipMalloc(&d_counter_, (1 + kShaBuckets) * sizeof(unsigned long long)));  // SHA-256 counter + histogram
     HIP_TRY(hipMemcpy(d_gear_, CHUNKFS_AMD_GEAR, 256 * sizeof(uint64_t), hipMemcpyHostToDevice));
     return CDC_OK;
 }
 
-// A walk context and the host thread that runs its batches (Engine::walk_submit).
-struct Engine::WalkWorker {
-    Engine *ctx = nullptr;  // owned: an engine with the handle's parameters
-    int device = 0;
-    std::thread th;
-    std::mutex m;
-    std::condition_variable cv;
-    bool has_job = false, stop = false;
-    bool done = true;    // no batch posted or running
-    bool fresh = false;  // ran a batch since the last drain
-    uint64_t seq = 0;    // that batch's number
-    std::vector<const uint8_t *> ptrs;
-    std::vector<uint64_t> lens;
-    cdc_chunk_t *out = nullptr;
-    size_t cap = 0;
-    uint64_t *first = nullptr;
-    hipEvent_t after = nullptr;  // recorded on the caller's stream at submit: the batch's input is complete there
-    int64_t rc = 0;
-    std::string err;
-
-    void loop() {
-        (void)hipSetDevice(device);
-        std::unique_lock<std::mutex> lk(m);
-        for (;;) {
-            cv.wait(lk, [&] { return stop || has_job; });
-            if (has_job) {  // (a stop request waits for the batch in hand)
-                has_job = false;
-                lk.unlock();
-                // the context's stream runs nothing of this batch before the
-                // caller's stream reached the submit
-                int64_t r = CDC_OK;
-                if (hipStreamWaitEvent(ctx->own_stream_, after, 0) != hipSuccess) {
-                    set_error("walk batch: hipStreamWaitEvent on the caller's stream failed");
-                    r = CDC_EDEVICE;
-                }
-                if (r == CDC_OK)
-                    r = ctx->chunk_batch_device(ptrs.size(), ptrs.data(), lens.data(), out, cap, first, nullptr);
-                std::string e = r < 0 ? std::string(last_error()) : std::string();
-                lk.lock();
-                rc = r;
-                err = std::move(e);
-                done = true;
-                cv.notify_all();
-                continue;
-            }
-            return;
-        }
-    }
-    void wait_done(std::unique_lock<std::mutex> &lk) {
-        cv.wait(lk, [&] { return done; });
-    }
-    ~WalkWorker() {
-        {
-            std::lock_guard<std::mutex> g(m);
-            stop = true;
-        }
-        cv.notify_all();
-        if (th.joinable()) th.join();
-        if (after) (void)hipEventDestroy(after);
-        delete ctx;
-    }
-};
-
 Engine::~Engine() {
     if (device_ >= 0) (void)hipSetDevice(device_);
-    if (fb_any_) (void)fast_drain();
-    for (auto &w : ww_) w.reset();
+    if (in_flight()) (void)drain();
+    walk_.reset();
     if (own_stream_) (void)hipStreamSynchronize(own_stream_);
     if (res_stream_) (void)hipStreamSynchronize(res_stream_);
     (void)hipFree(ws_);
@@ -284,8 +205,6 @@ Engine::~Engine() {
     (void)hipHostFree(h_sha_tab_);
     (void)hipFree(d_sha_order_);
     (void)hipFree(d_counter_);
-    (void)hipFree(d_wtabs_);
-    (void)hipFree(wws_);
     (void)hipHostFree(h_stage_);
     if (copy_stream_) (void)hipStreamSynchronize(copy_stream_);
     (void)hipHostFree(h_ring_);
@@ -316,7 +235,7 @@ int Engine::set_gear(const uint64_t *gear) {
         set_error("gear is NULL");
         return CDC_EINVAL;
     }
-    if (fb_any_) {  // the batches in flight finish with the table they were submitted with
+    if (in_flight()) {  // the batches in flight finish with the table they were submitted with
         const int64_t r = drain_implicit();
         if (r < 0) return (int)r;
     }
@@ -351,12 +270,15 @@ int Engine::ensure_host_staging(size_t n) {
     h_stage_ = nullptr;
     const size_t want = n + 64;
     // Per slot: ptrs[W] lens[W] span_base[W] tails[W] | stats ++ first[n+1]
-    // (fixed: first[n+1]) -- stream tables 4 n, device-written stats / flags
-    // ++ first[n+1] (n + 32), the walk's flags[4] and fix-up round flag blocks
-    // (4 x walk::kMaxFixRounds).  Slots 1-2: more FastCDC batches in flight.
-    h_stage_per_ = 5 * want + 36 + 4 * walk::kMaxFixRounds;
+    // (fixed: first[n+1]) -- stream tables 4 n, device-written stats ++
+    // first[n+1] (n + 32).  Slots 1-2: more FastCDC batches in flight.
+    h_stage_per_ = 5 * want + 32;
     HIP_TRY(placement().host_malloc(&h_stage_, kHostSlots * h_stage_per_ * sizeof(uint64_t), hipHostMallocCoherent));
     h_stage_streams_ = want;
+    uint64_t *h = static_cast<uint64_t *>(h_stage_);
+    fixed_tab_.h_ptrs = h;
+    fixed_tab_.h_lens = h + want;
+    fixed_tab_.h_sb = h + 2 * want;
     for (int k = 0; k < kSlots; ++k) fs_[k].tables.clear();
     return CDC_OK;
 }
@@ -399,7 +321,6 @@ int Engine::ensure_workspace(uint64_t spans, size_t n) {
     ws_streams_ = 0;
     HIP_TRY(hipMalloc(&ws_, off));
     ++ws_gen_;
-    ws_bytes_ = off;
     ws_spans_ = S;
     ws_streams_ = N;
     char *b = static_cast<char *>(ws_);
@@ -417,15 +338,14 @@ int Engine::ensure_workspace(uint64_t spans, size_t n) {
     }
     cand_ = fs_[0].cand;
     d_first_ = reinterpret_cast<uint64_t *>(b + o_first);
-    d_ptrs_ = fs_[0].d_ptrs;  // (the fixed-size path)
-    d_lens_ = fs_[0].d_lens;
-    d_span_base_ = fs_[0].d_sb;
+    fixed_tab_.d_ptrs = fs_[0].d_ptrs;
+    fixed_tab_.d_lens = fs_[0].d_lens;
+    fixed_tab_.d_sb = fs_[0].d_sb;
     ch3_.smax = (uint32_t)smax;
     ch3_.starts = reinterpret_cast<uint64_t *>(b + o_starts);
     uint64_t *desc = reinterpret_cast<uint64_t *>(b + o_desc);
     rs3_ = p3::Resolve{desc, desc + nb, desc + 2 * nb, desc + 3 * nb, desc + 4 * nb, desc + 5 * nb, 0};
     HIP_TRY(hipMemset(desc, 0, 6 * nb * 8));  // no stale status word can carry a live generation
-    d_tails_ = fs_[0].d_tails;
     return CDC_OK;
 }
 
@@ -444,9 +364,9 @@ int64_t Engine::chunk_batch_device_async(size_t n, const uint8_t *const *d_strea
 
 int64_t Engine::batch_sync() {
     HIP_TRY(hipSetDevice(device_));
-    if (fb_any_) {
+    if (in_flight()) {
         held_valid_ = false;
-        return fast_drain();
+        return drain();
     }
     if (held_valid_) {  // an implicit drain already completed them: its result
         held_valid_ = false;
@@ -460,101 +380,19 @@ int64_t Engine::batch_sync() {
 // chunk count, or the error of a failed collection -- is what the next
 // cdc_batch_sync returns.
 int64_t Engine::drain_implicit() {
-    if (!fb_any_) return 0;
-    held_ = fast_drain();
+    if (!in_flight()) return 0;
+    held_ = drain();
     held_valid_ = true;
     return held_;
 }
 
-// Batch k of the async walk pipeline goes to context k % walk_ctx_ (2 by
-// default), once that context's previous batch is done; a failure of that batch fails this
-// call (after the other context is drained), as FastCDC's collection does.
-int64_t Engine::walk_submit(size_t n, const uint8_t *const *d_streams, const uint64_t *lens, cdc_chunk_t *d_out,
-                            size_t out_cap, uint64_t *first, hipStream_t s) {
-    const int c = (int)(wk_seq_ % (uint64_t)walk_ctx_);
-    if (!ww_[c]) {
-        Engine *e = nullptr;
-        int rc = create_walk(algo_, seq_cfg_, min_, avg_, max_, device_, &e);
-        if (rc) return rc;
-        e->walk_async_ = false;
-        if (rabin_poly_) rc = e->set_rabin_poly(rabin_poly_);
-        if (rc) {
-            delete e;
-            return rc;
-        }
-        std::unique_ptr<WalkWorker> w(new WalkWorker());
-        w->ctx = e;
-        w->device = device_;
-        HIP_TRY(hipEventCreateWithFlags(&w->after, hipEventDisableTiming));
-        WalkWorker *wp = w.get();
-        w->th = std::thread([wp] { wp->loop(); });
-        ww_[c] = std::move(w);
-    }
-    WalkWorker &w = *ww_[c];
-    {
-        std::unique_lock<std::mutex> lk(w.m);
-        w.wait_done(lk);
-        if (w.fresh && w.rc < 0) {
-            const int64_t rc = w.rc;
-            const std::string msg = w.err;
-            lk.unlock();
-            (void)walk_drain();
-            set_error(msg);
-            return rc;
-        }
-        // (the context's previous batch is done: its wait on this event is long past)
-        HIP_TRY(hipEventRecord(w.after, s));
-        w.ptrs.assign(d_streams, d_streams + n);
-        w.lens.assign(lens, lens + n);
-        w.out = d_out;
-        w.cap = out_cap;
-        w.first = first;
-        w.seq = wk_seq_;
-        w.rc = 0;
-        w.err.clear();
-        w.done = false;
-        w.fresh = true;
-        w.has_job = true;
-    }
-    w.cv.notify_all();
-    ++wk_seq_;
-    wk_any_ = true;
-    fb_any_ = true;
-    return 0;
-}
+bool Engine::in_flight() const { return fb_any_ || (walk_ && walk_->in_flight()); }
 
-// Every walk batch in flight completed: the last one's chunk count (its
-// context's timing becomes this handle's), or the first failure.
-int64_t Engine::walk_drain() {
-    int64_t res = 0, err = 0;
-    std::string msg;
-    uint64_t last = 0;
-    bool any = false;
-    for (auto &wp : ww_) {
-        if (!wp) continue;
-        WalkWorker &w = *wp;
-        std::unique_lock<std::mutex> lk(w.m);
-        w.wait_done(lk);
-        if (!w.fresh) continue;
-        w.fresh = false;
-        if (w.rc < 0 && !err) {
-            err = w.rc;
-            msg = w.err;
-        }
-        if (!any || w.seq > last) {
-            any = true;
-            last = w.seq;
-            res = w.rc;
-            timing_ = w.ctx->timing_;
-        }
-    }
-    wk_any_ = false;
-    fb_any_ = false;
-    if (err) {
-        set_error(msg);
-        return err;
-    }
-    return res;
+int64_t Engine::drain() {
+    if (!is_walk()) return fast_drain();
+    const int64_t r = walk_->drain();
+    timing_ = walk_->timing();  // (the last batch's, from its context)
+    return r;
 }
 
 int64_t Engine::batch_device(size_t n, const uint8_t *const *d_streams, const uint64_t *lens, cdc_chunk_t *d_out,
@@ -588,12 +426,24 @@ int64_t Engine::batch_device(size_t n, const uint8_t *const *d_streams, const ui
         set_error("out_cap < cdc_batch_max_chunks()");
         return CDC_EINVAL;
     }
-    // FastCDC multi-megabyte batches are pipelined; everything else runs to
-    // completion here, after the batches in flight.
-    if (async && is_walk() && walk_async_ && n > 0 && bytes > kSmallBatch)
-        return walk_submit(n, d_streams, lens, d_out, out_cap, first, s);
+    // Multi-megabyte async batches go to the walk contexts or into the
+    // FastCDC pipeline; everything else runs to completion here, after the
+    // batches in flight.
+    if (is_walk()) {
+        if (async && walk_->takes_async(n, bytes))
+            return walk_->submit(n, d_streams, lens, d_out, out_cap, first, s, placement());
+        if (in_flight()) {
+            const int64_t r = drain_implicit();
+            if (r < 0) return r;
+        }
+        const int64_t r = walk_->chunk_batch(n, d_streams, lens, d_out, out_cap, first, s, placement());
+        const double hash_ms = timing_.hash_ms;  // (reported with the batch it hashed)
+        timing_ = walk_->timing();
+        timing_.hash_ms = hash_ms;
+        return r;
+    }
     const bool pipe = algo_ == CDC_ALGO_FASTCDC && n > 0 && bytes > kSmallBatch;
-    if (!pipe && fb_any_) {
+    if (!pipe && in_flight()) {
         const int64_t r = drain_implicit();
         if (r < 0) return r;
     }
@@ -612,7 +462,6 @@ int64_t Engine::batch_device(size_t n, const uint8_t *const *d_streams, const ui
     timing_.hash_ms = hash_ms;
     timing_.bytes = bytes;
     timing_.path = CDC_PATH_EMPTY;
-    out_cap_ = out_cap;
     if (n == 0) {
         if (first) first[0] = 0;
         return 0;
@@ -633,48 +482,13 @@ int64_t Engine::batch_device(size_t n, const uint8_t *const *d_streams, const ui
         if (r < 0) return r;
         return fast_drain();
     }
-    uint64_t *h = static_cast<uint64_t *>(h_stage_);
-    uint64_t *h_ptrs = h, *h_lens = h + h_stage_streams_, *h_sb = h + 2 * h_stage_streams_;
-    const uint32_t sl2 = is_walk() ? seg_log2_ : 0;
-    uint64_t spans = 0;
-    for (size_t i = 0; i < n; ++i) {
-        h_ptrs[i] = reinterpret_cast<uint64_t>(d_streams[i]);
-        h_lens[i] = lens[i];
-        h_sb[i] = spans;
-        if (is_walk()) spans += (lens[i] + (1ull << sl2) - 1) >> sl2;  // segments
-    }
-    h_sb[n] = spans;
-    if (algo_ != CDC_ALGO_FIXED && spans == 0) {  // every stream is empty
-        for (size_t i = 0; i <= n; ++i) first[i] = 0;
-        return 0;
-    }
-    rc = is_walk() ? ensure_walk_workspace(spans, n) : ensure_workspace(spans, n);
+    // Fixed-size: the streams own no spans; tables in staging slot 0.
+    fixed_tab_.fill(n, d_streams, lens, 0);
+    rc = ensure_workspace(0, n);
     if (rc) return rc;
-    // Small batches (the host path's per-segment calls) read the tables from
-    // the pinned staging block itself: the kernels' few table loads cross
-    // PCIe, but no copy sits on the call's critical path.  Larger batches
-    // re-upload the three per-stream tables only when they change (repeated
-    // batches over the same device buffers skip the H2D copies).
-    const bool zero_copy = bytes <= kSmallBatch && n <= kZeroCopyStreams;
-    const bool same = zero_copy || (ws_gen_ == tables_gen_ && tables_.size() == 2 * n &&
-                                    std::memcmp(tables_.data(), h_ptrs, n * 8) == 0 &&
-                                    std::memcmp(tables_.data() + n, h_lens, n * 8) == 0);
-    if (!same) {
-        HIP_TRY(hipMemcpyAsync(d_ptrs_, h_ptrs, n * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_lens_, h_lens, n * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_span_base_, h_sb, (n + 1) * 8, hipMemcpyHostToDevice, s));
-        tables_.assign(h_ptrs, h_ptrs + n);
-        tables_.insert(tables_.end(), h_lens, h_lens + n);
-        tables_gen_ = ws_gen_;
-    }
-    StreamTable st{};
-    st.ptrs = zero_copy ? reinterpret_cast<const uint8_t *const *>(h_ptrs) : d_ptrs_;
-    st.lens = zero_copy ? h_lens : d_lens_;
-    st.span_base = zero_copy ? h_sb : d_span_base_;
-    st.n = (uint32_t)n;
-    st.span_log2 = sl2;
-    st.total_spans = spans;
-    rc = is_walk() ? run_walk(st, d_out, n, first, s) : run_fixed(st, n, lens, d_out, first, s);
+    StreamTable st;
+    rc = fixed_tab_.publish(n, bytes, 0, 0, ws_gen_, s, st);
+    if (!rc) rc = run_fixed(st, n, lens, d_out, first, s);
     if (rc) return rc;
     return (int64_t)first[n];
 }
@@ -844,7 +658,6 @@ int64_t Engine::fast_submit(size_t n, const uint8_t *const *d_streams, const uin
 // count.
 int64_t Engine::fast_drain() {
     if (!fb_any_) return 0;
-    if (wk_any_) return walk_drain();
     const uint64_t last = fb_seq_ - 1;
     int rc = CDC_OK;
     int64_t total = 0;
@@ -1051,7 +864,7 @@ int Engine::run_small(const uint8_t *data, uint64_t len, cdc_chunk_t *d_out, siz
 // FastCDC batch events: [0] before its scan launch, [1] after it (before the
 // resolve), [2] after the resolve.
 const cdc_timing_t &Engine::timing() {
-    if (fb_any_) (void)drain_implicit();  // (a failure is held for the next cdc_batch_sync)
+    if (in_flight()) (void)drain_implicit();  // (a failure is held for the next cdc_batch_sync)
     if (timing_pending_) {
         timing_pending_ = false;
         (void)timing_back((uint32_t)(fast_batches_ - 1 - timing_seq_), timing_);
@@ -1060,7 +873,7 @@ const cdc_timing_t &Engine::timing() {
 }
 
 int Engine::timing_back(uint32_t back, cdc_timing_t &out) {
-    if (fb_any_) (void)drain_implicit();
+    if (in_flight()) (void)drain_implicit();
     if (algo_ != CDC_ALGO_FASTCDC || back >= kTimeRing || back >= fast_batches_) {
         set_error("cdc_debug_timing_back: no such FastCDC batch in the event ring");
         return CDC_EINVAL;
@@ -1173,7 +986,7 @@ int Engine::sha256_batch(size_t n, const uint8_t *const *d_streams, const uint64
         return CDC_EINVAL;
     }
     HIP_TRY(hipSetDevice(device_));
-    if (fb_any_) {  // (the chunks it hashes are usually the last batch's)
+    if (in_flight()) {  // (the chunks it hashes are usually the last batch's)
         const int64_t r = drain_implicit();
         if (r < 0) return (int)r;
     }
@@ -1225,7 +1038,7 @@ int Engine::sha256_batch(size_t n, const uint8_t *const *d_streams, const uint64
 }
 
 int64_t Engine::debug_copy(int what, void *out, size_t max_bytes) {
-    if (fb_any_) {
+    if (in_flight()) {
         const int64_t r = drain_implicit();
         if (r < 0) return r;
     }
@@ -1254,7 +1067,7 @@ int64_t Engine::debug_copy(int what, void *out, size_t max_bytes) {
 
 int Engine::read_bw(const uint8_t *d_buf, size_t len, int reps, double *ms) {
     HIP_TRY(hipSetDevice(device_));
-    if (fb_any_) {
+    if (in_flight()) {
         const int64_t r = drain_implicit();
         if (r < 0) return (int)r;
     }
@@ -1286,26 +1099,7 @@ int Engine::fill_splitmix64(uint8_t *d_buf, size_t len, uint64_t seed, hipStream
     return CDC_OK;
 }
 
-// ---- Rabin / UltraCDC / LeapCDC / SeqCDC: the segment-walk engine ----------
-
-namespace {
-// GF(2) remainder modulo the Rabin polynomial (host-side table build).
-uint64_t gf2_mod(uint64_t x, uint64_t p) {
-    const int dp = 63 - __builtin_clzll(p);
-    while (x) {
-        const int dx = 63 - __builtin_clzll(x);
-        if (dx < dp) break;
-        x ^= p << (dx - dp);
-    }
-    return x;
-}
-
-uint64_t splitmix_word(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-}  // namespace
+// ---- Rabin / UltraCDC / LeapCDC / SeqCDC / AE handles (walk_engine.cpp) ----
 
 int Engine::create_seq(const uint32_t seq[4], uint32_t min, uint32_t avg, uint32_t max, int device,
                        Engine **out) {
@@ -1313,184 +1107,46 @@ int Engine::create_seq(const uint32_t seq[4], uint32_t min, uint32_t avg, uint32
         set_error("cdc_create_seq: config is NULL");
         return CDC_EINVAL;
     }
-    return create_walk(CDC_ALGO_SEQ, seq, min, avg, max, device, out);
+    WalkConfig cfg;
+    cfg.seq_mode = seq[0];
+    cfg.seq_length = seq[1];
+    cfg.seq_jump_trigger = seq[2];
+    cfg.seq_jump_size = seq[3];
+    return create_walk(CDC_ALGO_SEQ, cfg, min, avg, max, device, out);
 }
 
 int Engine::create_ae(uint32_t mode, uint32_t window, uint32_t min, uint32_t avg, uint32_t max, int device,
                       Engine **out) {
-    const uint32_t cfg[4] = {mode, window, 0, 0};
+    WalkConfig cfg;
+    cfg.ae_mode = mode;
+    cfg.ae_window = window;
     return create_walk(CDC_ALGO_AE, cfg, min, avg, max, device, out);
 }
 
-int Engine::create_walk(cdc_algo_t algo, const uint32_t seq_in[4], uint32_t min, uint32_t avg, uint32_t max,
-                        int device, Engine **out) {
+int Engine::create_walk(cdc_algo_t algo, WalkConfig &cfg, uint32_t min, uint32_t avg, uint32_t max, int device,
+                        Engine **out) {
     if (!out) {
         set_error("cdc_create: out is NULL");
         return CDC_EINVAL;
     }
     *out = nullptr;
-    uint32_t seq[4] = {seq_in[0], seq_in[1], seq_in[2], seq_in[3]};
-    // Size rules (oracle_cdc_check): 0 < min <= avg <= max, and the
-    // bytes each rule reads before the first tested position.
-    if (min == 0 || min > avg || avg > max || (algo == CDC_ALGO_ULTRA && min < 8) ||
-        (algo == CDC_ALGO_LEAP && min < 32) || (algo == CDC_ALGO_RABIN && avg < 2)) {
-        set_error("invalid sizes: need 0 < min <= avg <= max (UltraCDC min >= 8, LeapCDC min >= 32)");
-        return CDC_EINVAL;
-    }
-    if (algo == CDC_ALGO_SEQ && (seq[0] > 1 || seq[1] == 0 || seq[2] == 0 || seq[3] == 0)) {
-        set_error("invalid SeqCDC config: mode 0/1, seq_length > 0, jump_trigger > 0, jump_size > 0");
-        return CDC_EINVAL;
-    }
-    if (algo == CDC_ALGO_AE) {  // seq = {mode, window}; window 0: the default for avg
-        if (seq[1] == 0) seq[1] = cdc_ae_default_window(avg);
-        if (seq[0] > 1 || (uint64_t)seq[1] + 1 > max) {
-            set_error("invalid AE config: mode 0 (Max) / 1 (Min), 1 <= window and window + 1 <= max");
-            return CDC_EINVAL;
-        }
-    }
+    std::string describe;
+    int rc = WalkEngine::validate(algo, min, avg, max, cfg, describe);  // (before any HIP call)
+    if (rc != CDC_OK) return rc;
     Engine *e = new Engine();
     e->algo_ = algo;
     e->min_ = min;
     e->avg_ = avg;
     e->max_ = max;
     e->device_ = device;
-    const char *name = algo == CDC_ALGO_RABIN ? "RabinCDC" : algo == CDC_ALGO_ULTRA ? "UltraCDC"
-                     : algo == CDC_ALGO_LEAP ? "LeapCDC" : algo == CDC_ALGO_AE ? "AE" : "SeqCDC";
-    char buf[256];
-    // impl Debug (rabin.rs:28-32, ultra.rs:24-28, leap.rs:24-28, seq.rs:34-38)
-    if (algo == CDC_ALGO_AE)
-        std::snprintf(buf, sizeof buf,
-                      "%s, sizes: SizeParams { min: %u, avg: %u, max: %u }, window: %u, mode: %s [MI355X gfx950]", name,
-                      min, avg, max, seq[1], seq[0] ? "Min" : "Max");
-    else if (algo == CDC_ALGO_SEQ)
-        std::snprintf(buf, sizeof buf, "%s, sizes: SizeParams { min: %u, avg: %u, max: %u }, mode: %s [MI355X gfx950]",
-                      name, min, avg, max, seq[0] ? "Decreasing" : "Increasing");
-    else
-        std::snprintf(buf, sizeof buf, "%s, sizes: SizeParams { min: %u, avg: %u, max: %u } [MI355X gfx950]", name,
-                      min, avg, max);
-    e->describe_ = buf;
-    for (int i = 0; i < 4; ++i) e->seq_cfg_[i] = seq[i];
-    if (const char *v = std::getenv("CHUNKFS_AMD_WALK_ASYNC")) e->walk_async_ = std::atoi(v) != 0;
-    if (const char *v = std::getenv("CHUNKFS_AMD_WALK_CTX")) e->walk_ctx_ = std::max(2, std::min(kWalkCtxMax, std::atoi(v)));
-    int rc = e->init();
-    if (rc == CDC_OK) rc = e->init_walk(seq);
+    e->describe_ = describe;
+    rc = e->init();
+    if (rc == CDC_OK) rc = WalkEngine::create(algo, min, avg, max, cfg, device, e->walk_);
     if (rc != CDC_OK) {
         delete e;
         return rc;
     }
     *out = e;
-    return CDC_OK;
-}
-
-int Engine::init_walk(const uint32_t *seq) {
-    walk::WalkParams &wp = wp_;
-    wp.algo = (uint32_t)algo_;
-    wp.min = min_;
-    wp.avg = avg_;
-    wp.max = max_;
-    wp.rabin_mask = (1ull << cdc_log2_round(avg_)) - 1;
-
-    const uint64_t lspan = avg_ > min_ ? (uint64_t)(avg_ - min_) : 1;
-    const uint32_t lb = cdc_log2_round(lspan);
-    wp.leap_thr = CDC_LEAP_THRESHOLD[lb > 32 ? 32 : lb];
-    wp.seq_mode = seq[0];
-    wp.seq_len = seq[1];
-    wp.seq_trig = seq[2];
-    wp.seq_jump = seq[3];
-    if (algo_ == CDC_ALGO_AE) {  // (create_walk resolved the default window)
-        wp.ae_mode = seq[0];
-        wp.ae_window = seq[1];
-    }
-    // Segments of 2^seg_log2 bytes (one lane each) and a warm-up of `warm`
-    // bytes; CHUNKFS_AMD_WALK="seg_log2,warm_over_avg" overrides (experiments).
-    // Defaults (tools/walk_bench.py sweeps on MI355X): segments of
-    // 32 KiB whatever the average (at avg 64 KiB, 32 KiB segments beat 256 KiB
-    // ones for every rule: more lanes, a shorter walk per lane and cheaper
-    // fix-up re-walks; profiles/r02ak_walk_avg64k_segments.log), a warm-up of
-    // 8 avg (a chain from an arbitrary start merges with the true one within a
-    // few content-defined cuts).
-    // Bitmap mode: Rabin when every tested digest is a full
-    // window (min >= 48), UltraCDC, LeapCDC, and SeqCDC when its run length
-    // fits a 64-bit step (seq_length <= 63).  CHUNKFS_AMD_WALK_BYTES=1 forces
-    // the byte walks (A/B experiments).
-    // AE has no byte walk: always its R bitmap, CHUNKFS_AMD_WALK_BYTES or not.
-    wp.nbm = algo_ == CDC_ALGO_RABIN ? (min_ >= CDC_RABIN_WINDOW ? 1u : 0u)
-           : algo_ == CDC_ALGO_ULTRA ? 3u : algo_ == CDC_ALGO_LEAP ? 2u
-           : algo_ == CDC_ALGO_AE ? 1u : (wp.seq_len <= 63 ? 1u : 0u);
-    if (const char *b = std::getenv("CHUNKFS_AMD_WALK_BYTES"))
-        if (std::atoi(b) != 0 && algo_ != CDC_ALGO_AE) wp.nbm = 0;
-    // Bitmap mode walks with a wave per segment (walk.hip wwalk_kernel), byte
-    // mode with a lane per segment (walk_kernel).
-    // Lane walks: 32 KiB segments whatever the average (profiles/r02ak).
-    // Wave walks: 128 KiB (Rabin, Leap) / 256 KiB segments, 8 avg warm-up
-    // (profiles/r03_walk/r03w_walk_seg_sweep.txt: a wave walks thousands of
-    // positions per step, so fewer, longer segments cut the warm-up share).
-    // Warm-up, in averages: chains from an arbitrary start merge within a few
-    // content-defined cuts.  Lane walks: 8 avg, SeqCDC 16
-    // (profiles/r02ag_walk_warm_sweep.log).  Wave walks: Rabin 8, UltraCDC and
-    // SeqCDC 16, LeapCDC 24 (its chains merge slowest; the fix-up rounds a
-    // shorter warm-up leaves cost more than the walk it saves,
-    // profiles/r03_walk/r03ab_walk_warm_ahead_sweep.txt).
-    uint64_t warm_mult = !wp.nbm ? (algo_ == CDC_ALGO_SEQ ? 16 : 8)
-                       : algo_ == CDC_ALGO_RABIN ? 8 : algo_ == CDC_ALGO_LEAP ? 24 : 16;
-    // Segments: lane walks 32 KiB whatever the average (profiles/r02ak).  Wave
-    // walks: at least 128 KiB (Rabin) / 256 KiB and at least the warm-up, so
-    // that the warm-up stays a fraction of each wave's walk (a wave walks
-    // thousands of positions per step; r03w_walk_seg_sweep.txt), up to 4 MiB.
-    seg_log2_ = !wp.nbm ? 15 : algo_ == CDC_ALGO_RABIN ? 17 : 18;
-    if (wp.nbm) {
-        const uint32_t wl = ceil_log2(warm_mult * avg_);
-        if (wl > seg_log2_) seg_log2_ = wl < 22 ? wl : 22;
-    }
-    // The per-segment start list holds segment/min + 2 entries: keep it <= ~4k
-    // (tiny min), and segments >= 4 KiB.
-    const uint32_t lmin = 63 - (uint32_t)__builtin_clzll((uint64_t)min_) + 12;
-    if (seg_log2_ > lmin) seg_log2_ = lmin < 12 ? 12 : lmin;
-    if (const char *w = std::getenv("CHUNKFS_AMD_WALK")) {
-        unsigned a = 0, b = 0;
-        if (std::sscanf(w, "%u,%u", &a, &b) == 2 && a >= 10 && a <= 30) {
-            seg_log2_ = a;
-            warm_mult = b;
-        }
-    }
-    if (algo_ == CDC_ALGO_AE && seg_log2_ < 12) seg_log2_ = 12;  // its bitmap pass steps 4 KiB at a time
-    wp.warm = warm_mult * avg_;
-    // CHUNKFS_AMD_AHEAD="after,max" overrides the run-ahead schedule (experiments).
-    if (const char *a = std::getenv("CHUNKFS_AMD_AHEAD")) {
-        unsigned x = 0, y = 0;
-        if (std::sscanf(a, "%u,%u", &x, &y) == 2 && y >= 1) {
-            ahead_after_ = x;
-            ahead_max_ = y;
-        }
-    }
-    wp.ahead = 1;
-    wp.bits_fine = 1;
-    if (const char *f = std::getenv("CHUNKFS_AMD_BITS_FINE")) wp.bits_fine = std::atoi(f) != 0 ? 1u : 0u;
-    if (const char *f = std::getenv("CHUNKFS_AMD_WALK_FUSED")) walk_fused_ = std::atoi(f) != 0;
-    wp.cap = (uint32_t)((1ull << seg_log2_) / min_ + 2);
-    wp.seg_words = (uint32_t)((1ull << seg_log2_) / 64);
-    wp.piece_log2 = seg_log2_ < 15 ? seg_log2_ : 15;  // data-parallel passes: 32 KiB pieces
-    wp.bm = nullptr;
-    HIP_TRY(hipMalloc(&d_wtabs_, 768 * sizeof(uint64_t)));
-    wp.tabs = d_wtabs_;
-    return load_walk_tables(CDC_RABIN_POLY);
-}
-
-// Tables: Rabin mod/out of polynomial P (appending a byte; sliding one out of
-// the window), LeapCDC window-hash table; and the digest's top-byte shift.
-int Engine::load_walk_tables(uint64_t P) {
-    uint64_t t[768];
-    const int deg = 63 - __builtin_clzll(P);
-    for (uint64_t b = 0; b < 256; ++b) {
-        t[b] = gf2_mod(b << deg, P) | (b << deg);
-        uint64_t h = b;
-        for (uint32_t i = 1; i < CDC_RABIN_WINDOW; ++i) h = gf2_mod(h << 8, P);
-        t[256 + b] = h;
-        t[512 + b] = splitmix_word(CDC_LEAP_SEED + (b + 1) * 0x9E3779B97F4A7C15ull);
-    }
-    HIP_TRY(hipSetDevice(device_));
-    HIP_TRY(hipMemcpy(d_wtabs_, t, sizeof t, hipMemcpyHostToDevice));
-    wp_.rabin_shift = (uint32_t)deg - 8;
     return CDC_OK;
 }
 
@@ -1509,232 +1165,12 @@ int Engine::set_rabin_poly(uint64_t P) {
         return CDC_EINVAL;
     }
     HIP_TRY(hipSetDevice(device_));
-    if (fb_any_) {  // the batches in flight finish with the polynomial they were submitted with
+    if (in_flight()) {  // the batches in flight finish with the polynomial they were submitted with
         const int64_t r = drain_implicit();
         if (r < 0) return (int)r;
     }
     HIP_TRY(hipStreamSynchronize(own_stream_));
-    rabin_poly_ = P;
-    for (auto &w : ww_) w.reset();  // (the contexts are made again, with this polynomial)
-    // The degree decides the bitmap kernel and whether it writes the quiet-run
-    // summary (walk::bits_write_summary): the workspace is laid out again.
-    (void)hipFree(wws_);
-    wws_ = nullptr;
-    wws_segs_ = 0;
-    wws_streams_ = 0;
-    return load_walk_tables(P);
-}
-
-int Engine::ensure_walk_workspace(uint64_t segs, size_t n) {
-    if (wws_ && segs <= wws_segs_ && n <= wws_streams_) return CDC_OK;
-    const uint64_t S = segs > wws_segs_ ? segs + segs / 4 + 16 : wws_segs_;
-    const size_t N = n > wws_streams_ ? n + 64 : wws_streams_;
-    const uint64_t nb = S / walk::kScanBlock + 2;
-    const size_t A = 256;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, A);
-        return o;
-    };
-    const size_t oE = take(S * 8), oX = take(S * 8), oXs = take(S * 8), oEs = take(S * 8), oP = take((S + 1) * 8);
-    const size_t oN = take(S * 4), oL = take(S * (size_t)wp_.cap * 8), oB = take((nb + 1) * 8);
-    const size_t oF = take((N + 1) * 8), oG = take((4 + 4 * walk::kMaxFixRounds) * 8), oGo = take(16);
-    const size_t oBM = take(S * (size_t)wp_.seg_words * wp_.nbm * 8);  // predicate bitmaps
-    const bool jt = algo_ == CDC_ALGO_LEAP && wp_.nbm;
-    const size_t oJT = take(jt ? S * (size_t)wp_.seg_words * 24 : 0);  // LeapCDC word tables
-    const size_t oJ8 = take(jt ? S * (size_t)wp_.seg_words * 6 : 0);   // and 512-position block tables
-    bool rsum = walk::bits_write_summary(wp_);  // quiet runs (CHUNKFS_AMD_QUIET=0: off, A/B)
-    if (const char *q = std::getenv("CHUNKFS_AMD_QUIET")) rsum = rsum && std::atoi(q) != 0;
-    const size_t oRS = take(rsum ? S * (size_t)wp_.seg_words / 8 * (algo_ == CDC_ALGO_RABIN ? 2 : 1) : 0);  // quiet-run summary
-    const size_t oQS = take(rsum ? S : 0);  // and per segment
-    const bool ae = algo_ == CDC_ALGO_AE;  // AE: per-word and per-64-word maxima
-    const size_t oM64 = take(ae ? S * (size_t)wp_.seg_words * 4 : 0);
-    const size_t oM4k = take(ae ? S * (size_t)wp_.seg_words / 64 * 4 : 0);
-    const size_t o_ptrs = take(N * 8), o_lens = take(N * 8), o_sb = take((N + 1) * 8);
-    (void)hipFree(wws_);
-    wws_ = nullptr;
-    wws_segs_ = 0;
-    wws_streams_ = 0;
-    HIP_TRY(hipMalloc(&wws_, off));
-    ++ws_gen_;  // the stream tables move: re-upload them
-    wws_segs_ = S;
-    wws_streams_ = N;
-    char *b = static_cast<char *>(wws_);
-    wst_.E = reinterpret_cast<uint64_t *>(b + oE);
-    wst_.X = reinterpret_cast<uint64_t *>(b + oX);
-    wst_.Xs = reinterpret_cast<uint64_t *>(b + oXs);
-    wst_.Es = reinterpret_cast<uint64_t *>(b + oEs);
-    wst_.P = reinterpret_cast<uint64_t *>(b + oP);
-    wst_.N = reinterpret_cast<uint32_t *>(b + oN);
-    wst_.list = reinterpret_cast<uint64_t *>(b + oL);
-    wst_.bsum = reinterpret_cast<uint64_t *>(b + oB);
-    wst_.first = reinterpret_cast<uint64_t *>(b + oF);
-    wst_.flags = reinterpret_cast<unsigned long long *>(b + oG);
-    walk_go_ = reinterpret_cast<uint64_t *>(b + oGo);
-    walk_flags_clean_ = false;  // (fresh memory: the next call initialises the flag blocks)
-    wp_.bm = wp_.nbm ? reinterpret_cast<uint64_t *>(b + oBM) : nullptr;
-    wp_.jt = jt ? reinterpret_cast<uint8_t *>(b + oJT) : nullptr;
-    wp_.jt8 = jt ? reinterpret_cast<uint16_t *>(b + oJ8) : nullptr;
-    wp_.rsum = rsum ? reinterpret_cast<uint64_t *>(b + oRS) : nullptr;
-    wp_.qseg = rsum ? reinterpret_cast<uint8_t *>(b + oQS) : nullptr;
-    wp_.ae_m64 = ae ? reinterpret_cast<uint32_t *>(b + oM64) : nullptr;
-    wp_.ae_m4k = ae ? reinterpret_cast<uint32_t *>(b + oM4k) : nullptr;
-    d_ptrs_ = reinterpret_cast<const uint8_t **>(b + o_ptrs);
-    d_lens_ = reinterpret_cast<uint64_t *>(b + o_lens);
-    d_span_base_ = reinterpret_cast<uint64_t *>(b + o_sb);
-    return CDC_OK;
-}
-
-int Engine::run_walk(const StreamTable &st, cdc_chunk_t *d_out, size_t n, uint64_t *first, hipStream_t s) {
-    uint64_t *h = static_cast<uint64_t *>(h_stage_);
-    uint64_t *h_first = h + 4 * h_stage_streams_ + 4;  // first[n+1]
-    uint64_t *h_flags = h + 5 * h_stage_streams_ + 32;  // flags[4] ++ the round blocks, one copy
-    uint64_t *h_rf = h_flags + 4;
-    const uint32_t R = max_rounds_ < walk::kMaxFixRounds ? max_rounds_ : walk::kMaxFixRounds;
-    HIP_TRY(hipEventRecord(ev_[0], s));
-    // (the previous call's end kernel resets the flag blocks when it ends
-    // the call: then no init launch here)
-    if (!walk_flags_clean_) HIP_TRY(walk::launch_flags_init(wst_.flags, R, s));
-    walk_flags_clean_ = false;
-    static const bool diag = std::getenv("CHUNKFS_AMD_WALKDIAG") != nullptr;  // phase times
-    auto lap = [&](const char *what) -> int {
-        if (!diag) return CDC_OK;
-        static auto t_last = std::chrono::steady_clock::now();
-        HIP_TRY(hipStreamSynchronize(s));
-        const auto t = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "  walkdiag %-6s %9.3f ms\n", what,
-                     std::chrono::duration<double, std::milli>(t - t_last).count());
-        t_last = t;
-        return CDC_OK;
-    };
-    (void)lap("start");
-    HIP_TRY(walk::launch_bits(st, wp_, s));
-    (void)lap("bits");
-    HIP_TRY(walk::launch_walk(st, wp_, wst_, s));
-    (void)lap("walk");
-    HIP_TRY(hipEventRecord(ev_[1], s));
-    // Jacobi rounds: re-walk every segment whose entry is not its predecessor's
-    // exit, until none is.  Rounds are launched in groups without a host sync:
-    // round r counts into its own flag block (rf + 4 r) and returns at once on
-    // the device when round r-1 changed no exit (WalkState::gate), so the host
-    // waits once per group instead of once per round.
-    // The output is queued right behind the first group, gated on the device
-    // by the same rule (walk::launch_emit's egate): when that group settles
-    // -- the common case -- the call needs one host wait, not two.
-    // The first group is one round: on random data the first round settles
-    // every segment (its re-walks meet the old chains), and the gated no-op
-    // rounds after it cost ~14 us each (snapshot + fix launches).
-    constexpr uint32_t kGroup = 4;
-    unsigned long long *rf = wst_.flags + 4;
-    uint64_t rewalked = 0, round_errors = 0;
-    bool settled = false, quiet_stop = false, queued = false, fused = false;
-    uint32_t launched = 0, last_round = 0;
-    while (launched < R && !settled) {
-        const uint32_t grp = launched == 0 ? walk::kFirstGroupRounds : kGroup;
-        const uint32_t end = launched + grp < R ? launched + grp : R;
-        for (uint32_t r = launched; r < end; ++r) {
-            // Plain Jacobi for the first ahead_after_ rounds, then run-ahead
-            // re-walks (walk.hip fix_kernel) so long non-merging stretches
-            // settle before the serial pass would be needed.
-            wp_.ahead = r < ahead_after_ ? 1u : ahead_max_;
-            walk::WalkState ws = wst_;
-            ws.flags = rf + 4 * r;
-            ws.gate = r ? rf + 4 * (r - 1) : nullptr;
-            const auto t0 = std::chrono::steady_clock::now();
-            HIP_TRY(walk::launch_fix(st, wp_, ws, s, r != 0));  // (round 0's snapshot: written by the walk)
-            if (diag) {
-                HIP_TRY(hipStreamSynchronize(s));
-                std::fprintf(stderr, "  walkdiag round %u %.3f ms\n", r,
-                             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-            }
-        }
-        queued = launched == 0 && !diag;
-        launched = end;
-        // Fused end (walk::launch_finish_emit): the prefix, first[] and the
-        // flag blocks go straight into the host staging block -- no D2H
-        // copies -- and the flags are reset for the next call when it ends
-        // this one.
-        fused = queued && walk_fused_ && walk::finish_fits(st);
-        if (fused) {
-            HIP_TRY(walk::launch_finish_emit(st, wp_, wst_, d_out, out_cap_, s, rf, launched, launched, walk_go_,
-                                             h_first, h_flags));
-        } else {
-            if (queued) {
-                HIP_TRY(walk::launch_emit(st, wp_, wst_, d_out, out_cap_, s, rf, launched));
-                HIP_TRY(hipMemcpyAsync(h_first, wst_.first, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-            }
-            HIP_TRY(hipMemcpyAsync(h_flags, wst_.flags, (4 + (size_t)launched * 4) * 8, hipMemcpyDeviceToHost, s));
-        }
-        if (queued) HIP_TRY(hipEventRecord(ev_[2], s));
-        HIP_TRY(hipStreamSynchronize(s));
-        // The first round that settled everything, or whose changed exits
-        // were mostly quiet-run re-walks (zero-filled / constant regions:
-        // chains there keep their phase, so each round moves the true one a
-        // single segment; the in-order pass takes such a region in one go).
-        // Later rounds of the group returned at once on the device (the same
-        // rule, walk.hip round_stops).
-        for (uint32_t r = 0; r < launched; ++r) {
-            const int v = walk::round_verdict(h_rf[4 * r], h_rf[4 * r + 3] >> 32);  // (walk.hpp: shared rule)
-            if (v == walk::kRoundSettled) {
-                settled = true;
-                break;
-            }
-            if (v == walk::kRoundQuiet) {
-                last_round = r;
-                quiet_stop = true;
-                break;
-            }
-        }
-        if (quiet_stop) break;
-    }
-    for (uint32_t r = 0; r < launched; ++r) {
-        round_errors += h_rf[4 * r + 1];
-        rewalked += h_rf[4 * r + 3] & 0xFFFFFFFFull;
-    }
-    if (diag) {
-        std::fprintf(stderr, "  walkdiag rounds %u settled %d:", launched, (int)settled);
-        for (uint32_t r = 0; r < launched && r < 24; ++r)
-            std::fprintf(stderr, " %llu/%llu", (unsigned long long)h_rf[4 * r + 3], (unsigned long long)h_rf[4 * r]);
-        std::fprintf(stderr, "\n");
-    }
-    // Chains that never merge (periodic data): one exact in-order pass from
-    // the lowest segment the last round changed.
-    if (!settled) {
-        const uint32_t lr = quiet_stop ? last_round : launched - 1;  // the last round that ran
-        HIP_TRY(hipMemcpyAsync(wst_.flags + 2, rf + 4 * lr + 2, 8, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(walk::launch_serial(st, wp_, wst_, s));
-    }
-    (void)lap("fixup");
-    // The gated output queued after the first group ran on the device exactly
-    // when that group settled by the same rule (emit_skips), i.e. when the
-    // loop stopped after it: launched == kFirstGroupRounds.
-    const bool gated_ran = queued && settled && launched == walk::kFirstGroupRounds;
-    walk_flags_clean_ = gated_ran && fused;  // (finish_kernel reset them)
-    if (!gated_ran) {  // (else the gated output already ran)
-        HIP_TRY(walk::launch_emit(st, wp_, wst_, d_out, out_cap_, s));
-        HIP_TRY(hipMemcpyAsync(h_flags, wst_.flags, 4 * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h_first, wst_.first, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipEventRecord(ev_[2], s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    if (h_flags[1] + round_errors != 0) {
-        set_error("segment walk: chunk list or output bound exceeded (internal error)");
-        return CDC_EDEVICE;
-    }
-    std::memcpy(first, h_first, (n + 1) * 8);
-    float t01 = 0, t12 = 0, t02 = 0;
-    HIP_TRY(hipEventElapsedTime(&t01, ev_[0], ev_[1]));
-    HIP_TRY(hipEventElapsedTime(&t12, ev_[1], ev_[2]));
-    HIP_TRY(hipEventElapsedTime(&t02, ev_[0], ev_[2]));
-    timing_.scan_ms = t01;
-    timing_.resolve_ms = t12;
-    timing_.total_ms = t02;
-    timing_.fixup_iterations = (uint32_t)rewalked;
-    timing_.overflow_spans = settled ? 0u : 1u;
-    timing_.path = CDC_PATH_WALK;
-    timing_.timed = 1;
-    return CDC_OK;
+    return walk_->set_rabin_poly(P);
 }
 
 }  // namespace cdc

@@ -2,8 +2,10 @@
 //
 // One Engine = one chunker handle bound to one GPU: the FastChunker /
 // FSChunker object of reference src/chunkers/{fast,fixed_size}.rs with its
-// device workspace.  Not thread-safe (the reference serialises through a
-// Mutex, src/lib.rs:89-90).
+// device workspace, the FastCDC batch pipeline and the host boundary
+// (hostpath.cpp).  A handle of a segment-walk rule (Rabin / Ultra / Leap /
+// Seq / AE) chunks through its WalkEngine (walk_engine.hpp).  Not thread-safe
+// (the reference serialises through a Mutex, src/lib.rs:89-90).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,32 +17,20 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/chunkfs_amd.h"
-#include "cdc_kernels.hpp"
 #include "fastcdc.hpp"
+#include "host_common.hpp"
 #include "small.hpp"
-#include "walk.hpp"
 
 namespace cdc {
+
+class WalkEngine;
+struct WalkConfig;
 
 // Pageable -> pinned copies of the host path split over a few threads (one
 // core copies ~20 GB/s, below what the H2D DMA takes).  One pool per process
 // (CopyPool::shared), helpers spin briefly after a job (the next 1 MiB segment
 // usually follows within microseconds), then sleep.  copy() returns when
 // every part is done (hostpath.cpp).
-// Where the host side of the boundary runs (hostpath.cpp): the device's PCIe
-// address, NUMA node and link; the node's CPUs this process may use.
-struct HostPlacement {
-    std::string pci, link, link_max;
-    int node = -1;
-    int allowed = 0;          // CPUs in this process's affinity mask
-    std::vector<int> cpus;    // of them, those on `node`
-    bool enabled = false;     // pinned memory and copy helpers placed on `node`
-    static HostPlacement probe(int device);
-    hipError_t host_malloc(void **ptr, size_t bytes, unsigned flags) const;
-    static int node_of(const void *addr);  // NUMA node of the page at addr (-1: unknown)
-};
-
 class CopyPool {
   public:
     CopyPool(unsigned threads, unsigned spin_us, const std::vector<int> &cpus);
@@ -86,7 +76,7 @@ class Engine {
     static int create_seq(const uint32_t seq[4], uint32_t min, uint32_t avg, uint32_t max,
                           int device, Engine **out);
     // AE (DESIGN.md "AE"): mode 0 = Max, 1 = Min; window 0 = the default
-    // (cdc_ae_default_window).  The pair travels in create_walk's seq[0..1].
+    // (cdc_ae_default_window).
     static int create_ae(uint32_t mode, uint32_t window, uint32_t min, uint32_t avg, uint32_t max, int device,
                          Engine **out);
     ~Engine();
@@ -120,9 +110,10 @@ class Engine {
     int64_t chunk_batch_device(size_t n, const uint8_t *const *d_streams,
                                const uint64_t *lens, cdc_chunk_t *d_out,
                                size_t out_cap, uint64_t *first, hipStream_t stream);
-    // The same, enqueued (cdc_chunk_batch_device_async): FastCDC batches of
-    // more than 8 MiB go back to back on the stream with no host wait, first[]
-    // filled by batch_sync().  Other algorithms run synchronously.
+    // The same, enqueued (cdc_chunk_batch_device_async): batches of more than
+    // 8 MiB return before they complete, first[] filled by batch_sync() --
+    // FastCDC's go back to back on the stream with no host wait, a walk rule's
+    // to the WalkEngine's contexts.  Fixed-size batches run synchronously.
     int64_t chunk_batch_device_async(size_t n, const uint8_t *const *d_streams, const uint64_t *lens,
                                      cdc_chunk_t *d_out, size_t out_cap, uint64_t *first, hipStream_t stream);
     // Waits for every enqueued batch (resolving the last one); the total chunk
@@ -157,8 +148,8 @@ class Engine {
 
   private:
     Engine() = default;
-    static int create_walk(cdc_algo_t algo, const uint32_t seq[4], uint32_t min, uint32_t avg, uint32_t max,
-                           int device, Engine **out);
+    static int create_walk(cdc_algo_t algo, WalkConfig &cfg, uint32_t min, uint32_t avg, uint32_t max, int device,
+                           Engine **out);
     int init();
     int ensure_workspace(uint64_t spans, size_t n);
     int ensure_host_staging(size_t n);
@@ -171,27 +162,12 @@ class Engine {
                         size_t out_cap, uint64_t *first, uint64_t bytes, hipStream_t s, bool timed, bool two_stream);
     int fast_collect(int rec);
     int64_t fast_drain();
-    int64_t drain_implicit();  // fast_drain for another call: its result is kept for batch_sync
-    // Async batches of the segment-walk algorithms (Rabin / Ultra / Leap /
-    // Seq): two contexts -- engines with this handle's parameters, each with
-    // its own stream and workspace -- run alternate batches synchronously,
-    // each on its own host worker thread, so one batch's walks and fix-up
-    // rounds overlap the next batch's bitmap pass on the device (a walk call
-    // keeps host logic between its kernels: the round loop).
-    // The batch is ordered after the work already on `s` (the caller's stream):
-    // an event recorded there, which the context's stream waits for.
-    int64_t walk_submit(size_t n, const uint8_t *const *d_streams, const uint64_t *lens, cdc_chunk_t *d_out,
-                        size_t out_cap, uint64_t *first, hipStream_t s);
-    int64_t walk_drain();  // fast_drain's part for these batches
-    struct WalkWorker;
-    static constexpr int kWalkCtxMax = 4;
-    std::unique_ptr<WalkWorker> ww_[kWalkCtxMax];
-    int walk_ctx_ = 2;        // contexts in use (CHUNKFS_AMD_WALK_CTX, 2..4)
-    bool wk_any_ = false;     // a walk batch is in flight
-    uint64_t wk_seq_ = 0;     // walk batches submitted
-    bool walk_async_ = true;  // CHUNKFS_AMD_WALK_ASYNC=0: walk batches complete inside the call
-    uint32_t seq_cfg_[4] = {0, 0, 0, 0};  // create_walk's SeqCDC configuration / AE {mode, window} (for the contexts)
-    uint64_t rabin_poly_ = 0;             // set_rabin_poly's polynomial (0: the default), for the contexts
+    // "A batch is in flight", whichever backend took it: FastCDC's pipeline
+    // (fb_any_) or the walk contexts.  drain() completes them (fast_drain /
+    // WalkEngine::drain: the last batch's chunk count or the first failure).
+    bool in_flight() const;
+    int64_t drain();
+    int64_t drain_implicit();  // drain for another call: its result is kept for batch_sync
     // One small FastCDC stream in one launch (small.hip): CDC_OK, kSmallFallback
     // (a budget was exceeded: run the regular pipeline) or a CDC_E* code.
     static constexpr int kSmallFallback = 1;
@@ -204,12 +180,9 @@ class Engine {
                   uint8_t *feed_dst = nullptr, uint32_t feed_slot = 0);
     int run_fixed(const StreamTable &st, size_t n, const uint64_t *lens,
                   cdc_chunk_t *d_out, uint64_t *first, hipStream_t s);
-    // Rabin / Ultra / Leap / Seq / AE: the segment-walk engine (walk.hip).
-    bool is_walk() const { return algo_ != CDC_ALGO_FASTCDC && algo_ != CDC_ALGO_FIXED; }
-    int init_walk(const uint32_t *seq);
-    int load_walk_tables(uint64_t rabin_poly);
-    int ensure_walk_workspace(uint64_t segs, size_t n);
-    int run_walk(const StreamTable &st, cdc_chunk_t *d_out, size_t n, uint64_t *first, hipStream_t s);
+    // Rabin / Ultra / Leap / Seq / AE: the segment-walk engine (walk_engine.hpp).
+    bool is_walk() const { return walk_ != nullptr; }
+    std::unique_ptr<WalkEngine> walk_;
     // Host boundary (hostpath.cpp).
     int ensure_ring();
     int ensure_host_out(size_t chunks);
@@ -224,18 +197,13 @@ class Engine {
     FastParams fp_{};
     uint32_t span_log2_ = 16;
     uint32_t small_span_log2_ = 16;                       // spans of batches <= kSmallBatch bytes
-    static constexpr uint64_t kSmallBatch = uint64_t(8) << 20;
-    // Batches this small with few streams read their stream tables straight
-    // from the pinned staging block (no H2D copies: each small copy costs a
-    // ~10 us DMA on the call's critical path).
-    static constexpr size_t kZeroCopyStreams = 64;
     uint32_t cap_ = 0, smax_ = 0;
     std::string describe_;
 
     hipStream_t own_stream_ = nullptr;
     hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
     // FastCDC batches: events (start, scan end, resolve end) in a ring of
-    // kTimeRing slots, batch k in slot k % kTimeRing.
+    // kTimeRing slots, batch k in slot k % kTimeRing (FastCDC handles only).
     static constexpr uint32_t kTimeRing = 64;
     hipEvent_t tev_[kTimeRing][3] = {};
     uint64_t fast_batches_ = 0;
@@ -243,14 +211,12 @@ class Engine {
 
     // Workspace arena (grow-only).
     void *ws_ = nullptr;
-    size_t ws_bytes_ = 0;
     uint64_t ws_spans_ = 0;
     size_t ws_streams_ = 0;
     Candidates cand_{};            // the last FastCDC batch's (debug_copy)
     p3::Chains ch3_{};             // chunk starts spilled past the resolve's LDS
     p3::Resolve rs3_{};            // look-back descriptors (generation-tagged, never re-zeroed)
     uint64_t res_gen_ = 0;
-    uint64_t *d_tails_ = nullptr;  // [streams] ragged last span ids (walk engine: unused)
     // FastCDC batches in flight: device tables and candidates in four slots
     // (slot = sequence number % 4) whose uploaded tables are kept to skip
     // unchanged H2D copies; host staging in three slots (batch record k % 3,
@@ -284,7 +250,7 @@ class Engine {
     uint64_t timing_seq_ = 0;       // the batch timing_ describes
     uint64_t fb_seq_ = 0;           // batches submitted
     hipStream_t fb_stream_ = nullptr;  // the stream of the batches in flight
-    bool fb_any_ = false;           // a batch is in flight
+    bool fb_any_ = false;           // a FastCDC batch is in flight
     bool fb_two_stream_ = false;    // ... with their resolves on res_stream_
     // Async batches on two streams (default, CHUNKFS_AMD_OVERLAP=1): batch k's
     // resolve on res_stream_ behind scan_ev_[slot k], batch k+1's scan on the
@@ -303,17 +269,13 @@ class Engine {
     hipEvent_t res_done_[3] = {};  // untimed batch k's resolve end on res_stream_ (slot k % 3)
     int64_t held_ = 0;              // result of the last implicit drain (drain_implicit)
     bool held_valid_ = false;
-    const uint64_t *cur_tails_ = nullptr;  // this batch's: d_tails_ or the staging block's
-    uint32_t n_tails_ = 0;
     uint64_t *d_first_ = nullptr;  // [n+1] (fixed-size path)
-    const uint8_t **d_ptrs_ = nullptr;
-    uint64_t *d_lens_ = nullptr;
-    uint64_t *d_span_base_ = nullptr;
+    CallTables fixed_tab_;         // the fixed-size path's stream tables: host staging slot 0, device slot 0
 
     // Pinned, device-visible (coherent) host staging: the small per-call
     // tables going in, stats ++ first[n+1] coming back (written by the
     // resolve kernel directly, no copy).
-    void *h_stage_ = nullptr;       // slot 0 (the small and walk paths use its layout too), then slots 1-2
+    void *h_stage_ = nullptr;       // slot 0 (the small and fixed-size paths use its layout too), then slots 1-2
     size_t h_stage_streams_ = 0, h_stage_per_ = 0;
 
     // Host path (hostpath.cpp): pinned upload ring (slot k reused once its
@@ -368,10 +330,7 @@ class Engine {
     cdc_timing_t timing_{};
     bool timing_pending_ = false;  // FastCDC events not read yet (see timing())
 
-    // Last uploaded stream tables (ptrs ++ lens) and the workspace generation
-    // they were uploaded into.
-    std::vector<uint64_t> tables_;
-    uint64_t ws_gen_ = 0, tables_gen_ = ~0ull;
+    uint64_t ws_gen_ = 0;  // workspace generation: uploaded stream tables are valid within one
     // Small-stream path (small.hip): on unless CHUNKFS_AMD_SMALL=0; its input
     // straight from the pinned ring slot (no H2D copy) unless CHUNKFS_AMD_SMALL_ZC=0.
     bool small_on_ = false, small_zc_ = true;
@@ -387,25 +346,6 @@ class Engine {
     uint64_t small_seq_ = 0;      // launch sequence number (feed words, block publication tags)
     double small_copy_s_ = 0;     // the last streamed call's host copy time
     uint64_t last_spans_ = 0;  // spans of the last FastCDC batch (debug_copy)
-    uint64_t out_cap_ = 0;     // capacity of the current batch's output (resolve bound)
-
-    // Segment-walk engine state (Rabin / Ultra / Leap / Seq).
-    walk::WalkParams wp_{};
-    uint32_t seg_log2_ = 14;
-    uint32_t max_rounds_ = 16;     // Jacobi fix-up rounds before the serial pass
-    uint32_t ahead_after_ = 8;     // rounds of plain Jacobi before run-ahead re-walks
-    uint32_t ahead_max_ = 64;      // segments one lane may re-walk in a run-ahead round
-    uint64_t *d_wtabs_ = nullptr;  // [768] rabin mod/out + leap hash tables
-    void *wws_ = nullptr;          // walk workspace arena (grow-only)
-    uint64_t wws_segs_ = 0;
-    size_t wws_streams_ = 0;
-    walk::WalkState wst_{};
-    uint64_t *walk_go_ = nullptr;     // finish_kernel's verdict word for the gated emit
-    bool walk_flags_clean_ = false;   // the flag blocks hold the init pattern (the last call's end kernel reset them)
-    bool walk_fused_ = true;          // fused end kernel (CHUNKFS_AMD_WALK_FUSED=0: sum / prefix / first + copies, A/B)
 };
-
-void set_error(const std::string &msg);
-const char *last_error();
 
 }  // namespace cdc

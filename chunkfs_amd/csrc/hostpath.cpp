@@ -40,15 +40,6 @@
 
 namespace cdc {
 
-#define HIP_TRY(expr)                                                          \
-    do {                                                                       \
-        hipError_t e_ = (expr);                                                \
-        if (e_ != hipSuccess) {                                                \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(e_));      \
-            return CDC_EDEVICE;                                                \
-        }                                                                      \
-    } while (0)
-
 namespace {
 size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 double now_s() {
@@ -371,7 +362,7 @@ int64_t Engine::chunk_host(const uint8_t *data, size_t len, cdc_chunk_t *out, si
     }
     if (len == 0) return 0;  // FastCDC iterator yields nothing; FSChunker loop never runs
     HIP_TRY(hipSetDevice(device_));
-    if (fb_any_) {  // async batches first: the small path reuses host staging block 0
+    if (in_flight()) {  // async batches first: the small path reuses host staging block 0
         const int64_t r = drain_implicit();
         if (r < 0) return r;
     }

@@ -2309,7 +2309,7 @@ __device__ __forceinline__ uint64_t block_exclusive(uint64_t v, uint64_t *sh, ui
 // The output kernels queued behind the first group of fix-up rounds (egate:
 // its first flag block, egn rounds) run only when one of those rounds settled
 // every segment before any round handed off to the in-order pass -- the
-// host's rule in Engine::run_walk, which otherwise re-queues them.
+// host's rule in WalkEngine::run, which otherwise re-queues them.
 __device__ __forceinline__ bool emit_skips(const unsigned long long *egate, uint32_t egn) {
     if (!egate) return false;
     for (uint32_t r = 0; r < egn; ++r) {

@@ -28,14 +28,14 @@ namespace walk {
 // Settled: nothing changed.  Quiet: mostly quiet runs -- chains there keep
 // their phase and each round moves the true one a single segment, so the
 // in-order pass takes over.  One rule for the host's round loop
-// (Engine::run_walk), the device's round gate (round_stops) and the gated
+// (WalkEngine::run), the device's round gate (round_stops) and the gated
 // output after the first group (emit_skips).
 enum : int { kRoundSettled = 0, kRoundQuiet = 1, kRoundGoOn = 2 };
 __host__ __device__ __forceinline__ int round_verdict(unsigned long long ch, unsigned long long q) {
     return ch == 0 ? kRoundSettled : (2 * q >= ch ? kRoundQuiet : kRoundGoOn);
 }
 // Rounds in the first group of fix-up launches, behind which the output is
-// queued and gated on the device (Engine::run_walk; emit_skips).
+// queued and gated on the device (WalkEngine::run; emit_skips).
 constexpr unsigned kFirstGroupRounds = 1;
 
 struct WalkParams {
@@ -129,7 +129,7 @@ hipError_t launch_fix(const StreamTable &st, const WalkParams &wp, const WalkSta
 hipError_t launch_serial(const StreamTable &st, const WalkParams &wp, const WalkState &ws, hipStream_t s);
 // Prefix of N, first[], and the Chunk{offset,length} output.  egate (the
 // first of egate_rounds round flag blocks) non-null: every kernel returns at
-// once unless those rounds settled (the host's rule, run_walk), so the output
+// once unless those rounds settled (the host's rule, WalkEngine::run), so the output
 // can be queued behind the first group of rounds without a host round trip.
 hipError_t launch_emit(const StreamTable &st, const WalkParams &wp, const WalkState &ws, void *d_out,
                        uint64_t out_cap, hipStream_t s, const unsigned long long *egate = nullptr,
