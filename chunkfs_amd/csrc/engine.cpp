@@ -72,6 +72,16 @@ int Engine::create(cdc_algo_t algo, uint32_t min, uint32_t avg, uint32_t max,
             delete e;
             return CDC_EINVAL;
         }
+        // The rule has no defined answer below these orderings: with max < min
+        // every chunk is max bytes, more than the len / min + 1 that the output
+        // and the workspace are sized for; with max < avg the published first
+        // loop runs to a centre past the clipped remainder.  (min > avg is
+        // well defined: the first loop is empty.)
+        if (max < min || max < avg) {
+            set_error("FastCDC sizes out of order: max must be >= min and >= avg");
+            delete e;
+            return CDC_EINVAL;
+        }
         const unsigned bits = (unsigned)std::lround(std::log2((double)avg));
         FastParams &fp = e->fp_;
         fp.min = min;
@@ -346,6 +356,10 @@ int Engine::ensure_workspace(uint64_t spans, size_t n) {
     uint64_t *desc = reinterpret_cast<uint64_t *>(b + o_desc);
     rs3_ = p3::Resolve{desc, desc + nb, desc + 2 * nb, desc + 3 * nb, desc + 4 * nb, desc + 5 * nb, 0};
     HIP_TRY(hipMemset(desc, 0, 6 * nb * 8));  // no stale status word can carry a live generation
+    // The fill runs on the null stream, which the non-blocking streams the
+    // kernels are launched on are not ordered against: it must have landed
+    // before the first resolve publishes a status word.
+    HIP_TRY(hipStreamSynchronize(nullptr));
     return CDC_OK;
 }
 
@@ -761,7 +775,10 @@ int Engine::run_small(const uint8_t *data, uint64_t len, cdc_chunk_t *d_out, siz
                       uint32_t feed_slot) {
     if (!small_mem_) {
         HIP_TRY(hipMalloc(&small_mem_, small::scratch_bytes() + small::copy_bytes() + small::bstamp_bytes()));
-        HIP_TRY(hipMemset(small_mem_, 0, small::scratch_bytes()));  // the ticket starts at 0
+        // The ticket starts at 0.  On the launch's own stream: a fill on the
+        // null stream is not ordered against a non-blocking stream, and one
+        // that landed late would zero records the blocks have published.
+        HIP_TRY(hipMemsetAsync(small_mem_, 0, small::scratch_bytes(), s));
         uint32_t *b = static_cast<uint32_t *>(small_mem_);
         small_ws_.brec = reinterpret_cast<uint64_t *>(b);
         small_ws_.bcnt = b + 2 * small::kMaxBlocks * small::kBlockRecCap;

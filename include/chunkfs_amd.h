@@ -75,6 +75,12 @@ typedef struct cdc_handle cdc_handle_t;
 /* Create a chunker bound to one GPU.
  *   CDC_ALGO_FASTCDC: FastChunker::new(SizeParams{min,avg,max}) (fast.rs:11-15);
  *                     v2020 FastCDC, Level1 normalization (fast.rs:37).
+ *                     Sizes: min 64..1 MiB, avg 256..4 MiB, max 1 KiB..16 MiB
+ *                     (the crate's asserts), and max >= min and max >= avg:
+ *                     below either the rule has no defined answer (max < min
+ *                     cuts more chunks than cdc_max_chunk_count promises),
+ *                     so such sizes are CDC_EINVAL.  min > avg, min == max
+ *                     and avg == max are valid.
  *   CDC_ALGO_FIXED:   FSChunker::new(min) (fixed_size.rs:19-23); avg/max ignored.
  *   CDC_ALGO_RABIN / _ULTRA / _LEAP: RabinChunker / UltraChunker / LeapChunker
  *                     ::new(SizeParams{min,avg,max}) (rabin.rs:13-20,

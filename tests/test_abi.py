@@ -86,6 +86,31 @@ def test_invalid_sizes_rejected_before_device():
     assert ei.value.code == -1
 
 
+@pytest.mark.parametrize("sizes", [(1048576, 256, 1024), (2048, 1024, 1024), (64, 4194304, 1024)])
+def test_fastcdc_max_below_min_or_avg_rejected_before_device(sizes):
+    """Each size is inside its own range, but max < min or max < avg: the rule
+    has no defined answer there (and max < min yields more chunks than
+    cdc_max_chunk_count promises), so cdc_create refuses and names the rule."""
+    import chunkfs_amd
+    with pytest.raises(chunkfs_amd.CdcError) as ei:
+        chunkfs_amd.FastChunker(chunkfs_amd.SizeParams(*sizes))
+    assert ei.value.code == -1
+    assert "max must be >= min and >= avg" in str(ei.value)
+
+
+@pytest.mark.parametrize("sizes", [(8192, 4096, 16384), (3000, 3000, 3000), (2000, 3000, 3000)])
+def test_fastcdc_valid_orderings_pass_validation(sizes):
+    """min > avg, min == max and avg == max are well defined: the size check
+    lets them through.  With a GPU the handle is created; without one the
+    create goes on to the device and fails there, with any code but
+    CDC_EINVAL."""
+    import chunkfs_amd
+    try:
+        chunkfs_amd.FastChunker(chunkfs_amd.SizeParams(*sizes)).close()
+    except chunkfs_amd.CdcError as e:
+        assert e.code != -1, f"valid sizes {sizes} refused as invalid: {e}"
+
+
 def test_unsupported_algorithms_raise():
     import chunkfs_amd
     with pytest.raises(NotImplementedError):
