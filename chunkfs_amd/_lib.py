@@ -45,7 +45,7 @@ EXPORTS = [
 # include/chunkfs_amd_debug.h (diagnostics, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["cdc_debug_pipeline", "cdc_debug_record_cap", "cdc_debug_copy", "cdc_debug_host_stats",
                  "cdc_debug_read_bw", "cdc_debug_host_placement",
-                 "cdc_debug_timing_back"]
+                 "cdc_debug_timing_back", "cdc_debug_walk_params"]
 
 
 class CdcError(RuntimeError):
@@ -185,6 +185,8 @@ def lib():
     L.cdc_debug_host_stats.restype = ctypes.c_int
     L.cdc_debug_timing_back.argtypes = [P, ctypes.c_uint32, ctypes.POINTER(cdc_timing_t), sz]
     L.cdc_debug_timing_back.restype = ctypes.c_int
+    L.cdc_debug_walk_params.argtypes = [P, ctypes.POINTER(ctypes.c_uint64), sz]
+    L.cdc_debug_walk_params.restype = ctypes.c_int
     L.cdc_sha256_chunks_device.argtypes = [P, P, P, sz, P, P]
     L.cdc_sha256_chunks_device.restype = ctypes.c_int
     L.cdc_sha256_batch_device.argtypes = [P, sz, P, P, P, P, P]

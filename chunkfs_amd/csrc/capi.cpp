@@ -247,6 +247,16 @@ int64_t cdc_debug_copy(cdc_handle_t *h, int what, void *out, size_t max_bytes) {
     return h->engine->debug_copy(what, out, max_bytes);
 }
 
+int cdc_debug_walk_params(const cdc_handle_t *h, uint64_t *v, size_t n) {
+    if (!h || (n && !v)) return (int)bad_handle();
+    const int rc = h->engine->walk_params(v, n);
+    if (rc < 0) {
+        cdc::set_error("cdc_debug_walk_params: not a segment-walk handle (Rabin / UltraCDC / LeapCDC / SeqCDC / AE)");
+        return CDC_EINVAL;
+    }
+    return rc;
+}
+
 const char *cdc_version(void) { return "chunkfs_amd 0.8 gfx950 abi 6"; }
 
 uint32_t cdc_abi_version(void) { return CHUNKFS_AMD_ABI_VERSION; }

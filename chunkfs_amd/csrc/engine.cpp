@@ -402,6 +402,8 @@ int64_t Engine::drain_implicit() {
 
 bool Engine::in_flight() const { return fb_any_ || (walk_ && walk_->in_flight()); }
 
+int Engine::walk_params(uint64_t *v, size_t n) const { return walk_ ? walk_->debug_params(v, n) : -1; }
+
 int64_t Engine::drain() {
     if (!is_walk()) return fast_drain();
     const int64_t r = walk_->drain();

@@ -143,6 +143,9 @@ class Engine {
     // last FastCDC batch to the host.  what: 0 = per-span candidate counts
     // (u32), 1 = candidate records (u32, cap per span).  Returns bytes copied.
     int64_t debug_copy(int what, void *out, size_t max_bytes);
+    // What the walk engine derived and how its last synchronous batch ended
+    // (WalkEngine::debug_params); -1 for a handle that is not a walk handle.
+    int walk_params(uint64_t *v, size_t n) const;
     uint32_t record_cap() const { return cap_; }
     int pipeline() const { return 3; }  // (one FastCDC pipeline: scan + resolve)
 

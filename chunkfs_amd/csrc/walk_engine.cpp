@@ -41,7 +41,7 @@ int WalkEngine::validate(cdc_algo_t algo, uint32_t min, uint32_t avg, uint32_t m
     // bytes each rule reads before the first tested position.
     if (min == 0 || min > avg || avg > max || (algo == CDC_ALGO_ULTRA && min < 8) ||
         (algo == CDC_ALGO_LEAP && min < 32) || (algo == CDC_ALGO_RABIN && avg < 2)) {
-        set_error("invalid sizes: need 0 < min <= avg <= max (UltraCDC min >= 8, LeapCDC min >= 32)");
+        set_error("invalid sizes: need 0 < min <= avg <= max (UltraCDC min >= 8, LeapCDC min >= 32, RabinCDC avg >= 2)");
         return CDC_EINVAL;
     }
     if (algo == CDC_ALGO_SEQ &&
@@ -306,6 +306,8 @@ int64_t WalkEngine::chunk_batch(size_t n, const uint8_t *const *d_streams, const
                                 size_t out_cap, uint64_t *first, hipStream_t s, const HostPlacement &place) {
     timing_ = cdc_timing_t{};
     timing_.path = CDC_PATH_EMPTY;
+    last_segs_ = 0;
+    last_end_ = 0;
     for (size_t i = 0; i < n; ++i) timing_.bytes += lens[i];
     if (n == 0) {
         if (first) first[0] = 0;
@@ -318,6 +320,7 @@ int64_t WalkEngine::chunk_batch(size_t n, const uint8_t *const *d_streams, const
         for (size_t i = 0; i <= n; ++i) first[i] = 0;
         return 0;
     }
+    last_segs_ = segs;
     rc = ensure_workspace(segs, n);
     if (rc) return rc;
     StreamTable st;
@@ -452,6 +455,7 @@ int WalkEngine::run(const StreamTable &st, cdc_chunk_t *d_out, uint64_t out_cap,
     // loop stopped after it: launched == kFirstGroupRounds.
     const bool gated_ran = queued && settled && launched == walk::kFirstGroupRounds;
     flags_clean_ = gated_ran && fused;  // (finish_kernel reset them)
+    last_end_ = gated_ran ? (fused ? 0u : 1u) : 2u;
     if (!gated_ran) {  // (else the gated output already ran)
         HIP_TRY(walk::launch_emit(st, wp_, st_, d_out, out_cap, s));
         HIP_TRY(hipMemcpyAsync(h_flags, st_.flags, 4 * 8, hipMemcpyDeviceToHost, s));
@@ -476,6 +480,13 @@ int WalkEngine::run(const StreamTable &st, cdc_chunk_t *d_out, uint64_t out_cap,
     timing_.path = CDC_PATH_WALK;
     timing_.timed = 1;
     return CDC_OK;
+}
+
+int WalkEngine::debug_params(uint64_t *v, size_t n) const {
+    const uint64_t w[kDebugWords] = {wp_.nbm, seg_log2_, wp_.warm, wp_.cap, wp_.piece_log2,
+                                     wp_.rabin_mask, wp_.leap_thr, last_segs_, last_end_};
+    for (size_t i = 0; i < n && i < (size_t)kDebugWords; ++i) v[i] = w[i];
+    return kDebugWords;
 }
 
 // ---- async batches ---------------------------------------------------------

@@ -63,6 +63,12 @@ class WalkEngine {
     // workspace laid out again, the contexts made again at their next batch.
     int set_rabin_poly(uint64_t poly);
 
+    // Debug (include/chunkfs_amd_debug.h cdc_debug_walk_params): what init()
+    // derived, then the segment count of the last synchronous batch and how
+    // it ended, into v[0..n).  Returns the values the engine has (kDebugWords).
+    static constexpr int kDebugWords = 9;
+    int debug_params(uint64_t *v, size_t n) const;
+
   private:
     WalkEngine() = default;
     int init();
@@ -104,6 +110,8 @@ class WalkEngine {
     CallTables tab_;
 
     cdc_timing_t timing_{};
+    uint64_t last_segs_ = 0;   // debug_params: segments of the last synchronous batch
+    uint32_t last_end_ = 0;    // ... and its end: 0 fused finish + gated emit, 1 gated emit, 2 ungated emit
 
     // Async contexts (submit / drain).
     struct Worker;

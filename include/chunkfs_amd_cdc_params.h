@@ -99,12 +99,15 @@ static inline uint32_t cdc_ae_default_window(uint32_t avg)
     return w ? (uint32_t)w : 1u;
 }
 
-/* round(log2(x)) in integers (x >= 1), shared so host and oracle agree. */
+/* round(log2(x)) in integers (1 <= x < 2^32: every size and size difference),
+ * shared so host and oracle agree.  With b = floor(log2 x), log2 x >= b + 1/2
+ * exactly when x^2 >= 2^(2b+1); no integer x sits on a half, so no tie rule.
+ * (12 up to 5792, 13 from 5793: 2^12.5 = 5792.6.) */
 static inline uint32_t cdc_log2_round(uint64_t x)
 {
     uint32_t b = 63u - (uint32_t)__builtin_clzll(x);
-    if (b > 0 && b < 63 && x - (1ull << b) >= (1ull << b) / 2) ++b;
-    return b;
+    if (b < 32) return x * x >= (1ull << (2 * b + 1)) ? b + 1 : b;
+    return b;  /* (not reached from 32-bit sizes) */
 }
 
 #endif

@@ -43,6 +43,24 @@ int cdc_debug_host_stats(const cdc_handle_t *h, double *v, size_t n);
  * (CHUNKFS_AMD_EVENT_EVERY=k: one in k), the others report 0 ms.
  * CDC_EINVAL when that batch is not in the ring. */
 int cdc_debug_timing_back(cdc_handle_t *h, uint32_t back, cdc_timing_t *t, size_t t_size);
+/* Segment-walk handles (Rabin / UltraCDC / LeapCDC / SeqCDC / AE): what the
+ * engine derived from the sizes at creation, into v[0..n), in this order:
+ *   0 nbm         predicate bitmaps per segment (0 = byte mode)
+ *   1 seg_log2    segments are 2^seg_log2 bytes
+ *   2 warm        warm-up bytes before a segment
+ *   3 cap         chunk starts recorded per segment
+ *   4 piece_log2  the data-parallel passes run over 2^piece_log2-byte pieces
+ *   5 rabin_mask  (1 << round(log2 avg)) - 1
+ *   6 leap_thr    the CDC_LEAP_THRESHOLD entry in use
+ * then, of the handle's last synchronous batch (0, 0 before one, and after
+ * a batch with no bytes):
+ *   7 its segment count
+ *   8 how it ended: 0 = the fused end kernel and the gated output behind the
+ *     first fix-up round, 1 = the gated output without the fused kernel, 2 =
+ *     the ungated output after further rounds or the in-order pass.
+ * Returns the number of values the library has (9; at most n are written), or
+ * CDC_EINVAL for a FastCDC or fixed-size handle. */
+int cdc_debug_walk_params(const cdc_handle_t *h, uint64_t *v, size_t n);
 /* Measured-achievable HBM read rate on the handle's device: a read-only
  * reduction kernel (16-byte coalesced loads, every byte once) over the DEVICE
  * buffer d_buf[len], `reps` timed launches after one warm-up; *ms = the

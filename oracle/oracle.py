@@ -270,10 +270,9 @@ def _cdc_params():
 
 
 def _log2_round(x):
+    """round(log2 x), x >= 1: up exactly when x^2 >= 2^(2b+1), b = floor(log2 x)."""
     b = x.bit_length() - 1
-    if 0 < b < 63 and x - (1 << b) >= (1 << b) // 2:
-        b += 1
-    return b
+    return b + 1 if x * x >= 1 << (2 * b + 1) else b
 
 
 def _polmod(x, p):
