@@ -99,6 +99,18 @@ def _as_buffer(data):
     return arr.ctypes.data_as(ctypes.c_void_p), arr.size, arr
 
 
+def pack_offsets(lengths, align=16):
+    """Where buffers of these lengths go in one staging buffer, each at a
+    multiple of `align`, in order and without overlap: (offsets, total bytes).
+    A buffer of length 0 takes no room."""
+    offsets, at = [], 0
+    for n in lengths:
+        at = -(-at // align) * align
+        offsets.append(at)
+        at += int(n)
+    return offsets, at
+
+
 class Chunker:
     """The Chunker trait (src/lib.rs:74-86), backed by one GPU handle.
 
@@ -877,6 +889,62 @@ class FileSystem:
             torch.cuda.synchronize(t.device)  # the call runs on the store's stream, not torch's
         return check(lib().cdc_file_write_device(handle._fh, handle.chunker._h, _ptr(t.data_ptr()), t.numel(),
                                                  _ptr(stream)))
+
+    def write_to_files(self, handles, datas, stream=None):
+        """cdc_files_write_batch_device: write_to_file(handles[i], datas[i]) for
+        every i, in order, as one call -- one chunk batch, one hash batch, one
+        put, one append, and the same files and store as the loop would leave.
+        Each of `datas` is host bytes or a CUDA uint8 tensor, mixed freely; the
+        host buffers go up in ONE upload, packed at 16-byte-aligned offsets
+        (pack_offsets).  All handles write through the chunker of the first.
+        Returns the list of span counts.  A refused call (CdcError) changes
+        nothing; a read-only handle raises CDC_EPERM before anything is uploaded."""
+        import torch
+        handles, datas = list(handles), list(datas)
+        if len(handles) != len(datas):
+            raise ValueError("write_to_files: as many datas as handles")
+        for h in handles:
+            if h.chunker is None:
+                self.stat(h)  # CDC_ENOTFOUND first, as write_to_file
+                raise CdcError(_lib.CDC_EPERM, "file handle is read-only")
+        if not handles:
+            return []
+        chunker = handles[0].chunker
+        if any(h.chunker is not chunker for h in handles):
+            raise ValueError("write_to_files: one chunker per call")
+        dev = f"cuda:{self.device}"
+        host, tensors = {}, {}
+        for i, data in enumerate(datas):
+            if isinstance(data, torch.Tensor):
+                t = data.contiguous().view(torch.uint8).reshape(-1)
+                if t.is_cuda:
+                    tensors[i] = t if t.data_ptr() % 16 == 0 or t.numel() == 0 else t.clone()
+                else:
+                    host[i] = t.numpy()
+            else:
+                host[i] = _as_buffer(data)[2]
+        order = sorted(host)
+        offsets, total = pack_offsets([host[i].size for i in order])
+        staged = None
+        if total:
+            staging = np.empty(total, dtype=np.uint8)
+            for i, at in zip(order, offsets):
+                staging[at:at + host[i].size] = host[i]
+            staged = torch.from_numpy(staging).to(dev)
+        reqs = (_lib.cdc_fwrite_t * len(handles))()
+        for i, h in enumerate(handles):
+            reqs[i].fh = h._fh.value
+            if i in tensors:
+                reqs[i].len = tensors[i].numel()
+                reqs[i].d_data = tensors[i].data_ptr() if reqs[i].len else None
+        for i, at in zip(order, offsets):
+            reqs[i].len = host[i].size
+            reqs[i].d_data = staged.data_ptr() + at if reqs[i].len else None
+        if stream is None:
+            torch.cuda.synchronize(dev)  # the call runs on the store's stream, not torch's
+        spans = (ctypes.c_uint64 * len(handles))()
+        check(lib().cdc_files_write_batch_device(self._h, chunker._h, len(handles), reqs, spans, _ptr(stream)))
+        return [int(x) for x in spans]
 
     def write_from_stream(self, handle, reader):
         """FileSystem::write_from_stream (mod.rs:116-134): reads `reader` (an

@@ -39,13 +39,14 @@ EXPORTS = [
     "cdc_files_create_file", "cdc_files_open", "cdc_file_close", "cdc_file_stat", "cdc_file_write_device",
     "cdc_file_append_device", "cdc_file_read_complete_device", "cdc_file_read_device", "cdc_file_pread_device",
     "cdc_files_pread_batch_device", "cdc_file_hashes_device", "cdc_file_distribution_device",
+    "cdc_files_write_batch_device",
     "cdc_files_get_to_dedup_ratio", "cdc_file_verify_device", "cdc_store_size_distribution_device",
     "cdc_fill_splitmix64_device", "cdc_version", "cdc_abi_version",
 ]
 # include/chunkfs_amd_debug.h (diagnostics, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["cdc_debug_pipeline", "cdc_debug_record_cap", "cdc_debug_copy", "cdc_debug_host_stats",
                  "cdc_debug_read_bw", "cdc_debug_host_placement",
-                 "cdc_debug_timing_back", "cdc_debug_walk_params"]
+                 "cdc_debug_timing_back", "cdc_debug_walk_params", "cdc_debug_files_table_blocks"]
 
 
 class CdcError(RuntimeError):
@@ -90,6 +91,10 @@ class cdc_file_stat_t(ctypes.Structure):
 class cdc_pread_t(ctypes.Structure):
     _fields_ = [("fh", ctypes.c_void_p), ("offset", ctypes.c_uint64), ("len", ctypes.c_uint64),
                 ("d_dst", ctypes.c_void_p)]
+
+
+class cdc_fwrite_t(ctypes.Structure):
+    _fields_ = [("fh", ctypes.c_void_p), ("d_data", ctypes.c_void_p), ("len", ctypes.c_uint64)]
 
 
 class cdc_timing_t(ctypes.Structure):
@@ -259,6 +264,8 @@ def lib():
     L.cdc_file_pread_device.restype = ctypes.c_int64
     L.cdc_files_pread_batch_device.argtypes = [P, sz, ctypes.POINTER(cdc_pread_t), u64p, P]
     L.cdc_files_pread_batch_device.restype = ctypes.c_int
+    L.cdc_files_write_batch_device.argtypes = [P, P, sz, ctypes.POINTER(cdc_fwrite_t), u64p, P]
+    L.cdc_files_write_batch_device.restype = ctypes.c_int64
     L.cdc_file_hashes_device.argtypes = [P, P, sz]
     L.cdc_file_hashes_device.restype = ctypes.c_int64
     L.cdc_file_distribution_device.argtypes = [P, P, P, P, sz, P]
@@ -281,6 +288,8 @@ def lib():
     L.cdc_debug_host_placement.restype = ctypes.c_int64
     L.cdc_debug_copy.argtypes = [P, ctypes.c_int, P, sz]
     L.cdc_debug_copy.restype = ctypes.c_int64
+    L.cdc_debug_files_table_blocks.argtypes = [P]
+    L.cdc_debug_files_table_blocks.restype = ctypes.c_int64
     L.cdc_version.argtypes = []
     L.cdc_version.restype = ctypes.c_char_p
     L.cdc_abi_version.argtypes = []

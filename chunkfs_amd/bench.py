@@ -130,6 +130,16 @@ class CDCFixture:
         self.fs.write_from_stream(handle, data)
         self.fs.close_file(handle)
 
+    def fill_with_many(self, datas, chunker):
+        """Fills the store with every one of `datas` (host bytes or CUDA uint8
+        tensors), each in a file of its own, by ONE write_to_files; returns the
+        files' names in the order of `datas`."""
+        made = [self._init_file(chunker) for _ in datas]
+        self.fs.write_to_files([h for h, _ in made], datas)
+        for h, _ in made:
+            self.fs.close_file(h)
+        return [name for _, name in made]
+
     def measure(self, dataset, chunker):
         """One measurement of `dataset` with `chunker` (bench/mod.rs:93-140)."""
         chunker_name = repr(chunker)

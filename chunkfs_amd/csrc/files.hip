@@ -120,6 +120,99 @@ __global__ __launch_bounds__(kFlThreads) void append_kernel(SpanTable t, uint64_
     dst[1] = src[1];
 }
 
+// ---- segmented append (cdc_files_write_batch_device) -----------------------------
+// The m spans of one put belong to nfiles files: file f owns spans [first[f],
+// first[f + 1]).  Files without spans make runs of equal entries in first[]; the
+// owner of span i is the last f with first[f] <= i (i < first[nfiles], so that f
+// has first[f + 1] > i).
+__device__ __forceinline__ uint64_t file_of_span(const uint64_t *__restrict__ first, uint64_t nfiles, uint64_t i) {
+    uint64_t a = 0, b = nfiles;
+    while (b - a > 1) {
+        const uint64_t mid = (a + b) >> 1;
+        if (first[mid] <= i) a = mid;
+        else b = mid;
+    }
+    return a;
+}
+
+// span_len_kernel with per-file statistics.  A wave's lanes may belong to
+// several files: the lanes that share the leader's file reduce together and
+// retire with one atomic each (as dist_hist_kernel does on the leader's bin).
+__global__ __launch_bounds__(kFlThreads) void batch_len_kernel(const uint32_t *__restrict__ slot_of,
+                                                               const uint64_t *__restrict__ tbl_length,
+                                                               const uint64_t *__restrict__ first, uint64_t nfiles,
+                                                               uint64_t m, uint64_t *val, AppendStat *stat) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool todo = i < m;
+    uint64_t least = ~0ull, zeros = 0, f = 0;
+    if (todo) {
+        const uint32_t s = slot_of[i];
+        const uint64_t len = s == kNoSlot ? 0 : tbl_length[s];
+        val[i] = len;
+        least = len - 1;
+        zeros = len == 0;
+        f = file_of_span(first, nfiles, i);
+    }
+    const uint32_t lane = threadIdx.x & 63;
+    unsigned long long left = __ballot(todo);
+    while (left) {  // wave-uniform: every lane takes part in the shuffles
+        const uint32_t leader = (uint32_t)__builtin_ctzll(left);
+        const uint64_t lead_file = __shfl(f, (int)leader);
+        const bool mine = todo && f == lead_file;
+        const unsigned long long same = __ballot(mine);
+        uint64_t l = mine ? least : ~0ull, z = mine ? zeros : 0;
+#pragma unroll
+        for (int k = 1; k < 64; k <<= 1) {
+            const uint64_t o = __shfl_xor(l, k);
+            l = o < l ? o : l;
+            z += __shfl_xor(z, k);
+        }
+        if (lane == leader) {
+            if (l != ~0ull) atomicMin(&stat[lead_file].least, (unsigned long long)l);
+            if (z) atomicAdd(&stat[lead_file].zeros, (unsigned long long)z);
+        }
+        if (mine) todo = false;
+        left &= ~same;
+    }
+}
+
+// val = exclusive scan of all m lengths, *total their sum.  Threads [0, m): span
+// i of file f goes to entry n0_f + (i - first[f]) at offset size0_f + val[i] -
+// val[first[f]].  Threads [m, m + nfiles): file f's closing offset and byte
+// total; a file without spans is left alone (it may have no table).
+__global__ __launch_bounds__(kFlThreads) void batch_append_kernel(const AppendDst *__restrict__ dst,
+                                                                  const uint64_t *__restrict__ first,
+                                                                  uint64_t nfiles, uint64_t m,
+                                                                  const uint32_t *__restrict__ slot_of,
+                                                                  const uint64_t *__restrict__ tbl_loc,
+                                                                  const uint8_t *__restrict__ digests,
+                                                                  const uint64_t *__restrict__ val,
+                                                                  const uint64_t *__restrict__ total,
+                                                                  AppendStat *stat) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m + nfiles) return;
+    if (i >= m) {
+        const uint64_t f = i - m, lo = first[f], hi = first[f + 1];
+        if (hi == lo) return;
+        const AppendDst d = dst[f];
+        const uint64_t bytes = (hi < m ? val[hi] : *total) - val[lo];
+        d.t.off[d.n0 + (hi - lo)] = d.size0 + bytes;
+        stat[f].bytes = bytes;
+        return;
+    }
+    const uint64_t f = file_of_span(first, nfiles, i), lo = first[f];
+    const AppendDst d = dst[f];
+    const uint64_t j = d.n0 + (i - lo);
+    const uint32_t s = slot_of[i];
+    d.t.off[j] = d.size0 + (val[i] - val[lo]);
+    d.t.slot[j] = s;
+    d.t.loc[j] = s == kNoSlot ? 0 : tbl_loc[s];
+    const uint4 *src = reinterpret_cast<const uint4 *>(digests + 32 * i);
+    uint4 *to = reinterpret_cast<uint4 *>(d.t.digest + 32 * j);
+    to[0] = src[0];
+    to[1] = src[1];
+}
+
 // ---- the range planner ---------------------------------------------------------
 // single (nullable; a call of one request): the scan over one count is the
 // count itself, so it goes straight to *single and the request's first piece is 0.
@@ -484,6 +577,20 @@ hipError_t launch_files_append(const SpanTable &t, uint64_t n0, uint64_t size0, 
     if (e != hipSuccess) return e;
     append_kernel<<<grid_of(n + 1), kFlThreads, 0, s>>>(t, n0, size0, slot_of, tbl_loc, d_digests, n, val,
                                                         block_sums + store_scan_blocks(n));
+    return hipGetLastError();
+}
+
+hipError_t launch_files_append_batch(const AppendDst *d_dst, const uint64_t *d_first, uint64_t nfiles, uint64_t m,
+                                     const uint32_t *slot_of, const uint64_t *tbl_length, const uint64_t *tbl_loc,
+                                     const uint8_t *d_digests, uint64_t *val, uint64_t *block_sums,
+                                     AppendStat *d_stat, hipStream_t s) {
+    if (!m) return hipSuccess;
+    batch_len_kernel<<<grid_of(m), kFlThreads, 0, s>>>(slot_of, tbl_length, d_first, nfiles, m, val, d_stat);
+    const hipError_t e = launch_store_scan(val, m, block_sums, nullptr, s);
+    if (e != hipSuccess) return e;
+    batch_append_kernel<<<grid_of(m + nfiles), kFlThreads, 0, s>>>(d_dst, d_first, nfiles, m, slot_of, tbl_loc,
+                                                                   d_digests, val, block_sums + store_scan_blocks(m),
+                                                                   d_stat);
     return hipGetLastError();
 }
 

@@ -59,6 +59,29 @@ hipError_t launch_files_append(const SpanTable &t, uint64_t n0, uint64_t size0, 
                                uint64_t n, uint64_t *val, uint64_t *block_sums, unsigned long long *d_stat,
                                unsigned long long *h_total, hipStream_t s);
 
+// The segmented append of cdc_files_write_batch_device: the m = first[nfiles]
+// spans of one batch put go to nfiles tables in one pass.  File f owns spans
+// [first[f], first[f + 1]) (files without spans make runs of equal entries) and
+// receives them from entry n0 on, its offsets continuing from size0; its table
+// must have room for n0 + first[f + 1] - first[f] spans.
+struct AppendDst {
+    SpanTable t;
+    uint64_t n0;
+    uint64_t size0;
+};
+// Per file, preset to {0, ~0, 0}: bytes appended, min(length - 1) over the spans
+// of length > 0, spans of length 0 (launch_files_append's *h_total and d_stat).
+struct AppendStat {
+    unsigned long long bytes, least, zeros;
+};
+// d_dst / d_first / d_stat: device arrays of nfiles, nfiles + 1, nfiles entries;
+// slot_of .. block_sums as launch_files_append, over the m spans.  One scan over
+// all m lengths, no host wait; the caller copies d_stat back.
+hipError_t launch_files_append_batch(const AppendDst *d_dst, const uint64_t *d_first, uint64_t nfiles, uint64_t m,
+                                     const uint32_t *slot_of, const uint64_t *tbl_length, const uint64_t *tbl_loc,
+                                     const uint8_t *d_digests, uint64_t *val, uint64_t *block_sums,
+                                     AppendStat *d_stat, hipStream_t s);
+
 // The range planner and the copy: nreq requests -> span ranges -> pieces ->
 // tiles -> copy_kernel, with no host wait in between.  max_pieces / max_tiles
 // are host-side bounds (they size grids and scratch; a bound below the true

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/chunkfs_amd.h"
+#include "../../include/chunkfs_amd_debug.h"
 #include "engine.hpp"
 #include "files.hpp"
 #include "store.hpp"
@@ -30,12 +31,65 @@ struct FileRec {
     cdc::SpanTable t{};
 };
 
+// Span tables are carved out of larger device blocks, so that a new file costs
+// no device allocation.  Capacities double from 64 spans: class c holds 64 << c.
+// A table is one run of bytes, digest first (16-byte aligned for the uint4
+// stores), then off, loc (8) and slot (4).  A block serves one class; freed
+// tables go back to their class's list and the blocks are released with the layer.
+constexpr uint64_t kTableMinCap = 64;
+constexpr uint64_t kTableBlockBytes = 1ull << 20;
+
+struct TablePool {
+    std::vector<void *> blocks;
+    std::vector<std::vector<uint8_t *>> free_tables;  // per class
+
+    static uint64_t table_bytes(uint64_t cap) { return (cap * 52 + 8 + 255) & ~255ull; }
+    static size_t class_of(uint64_t cap) { return (size_t)__builtin_ctzll(cap / kTableMinCap); }
+    static cdc::SpanTable at(uint8_t *base, uint64_t cap) {
+        cdc::SpanTable t{};
+        t.digest = base;
+        t.off = reinterpret_cast<uint64_t *>(base + cap * 32);
+        t.loc = t.off + cap + 1;
+        t.slot = reinterpret_cast<uint32_t *>(t.loc + cap);
+        return t;
+    }
+
+    // cap: 64 << c.  A table larger than the block size gets a block of its own.
+    hipError_t take(uint64_t cap, cdc::SpanTable *out) {
+        const size_t c = class_of(cap);
+        if (free_tables.size() <= c) free_tables.resize(c + 1);
+        if (free_tables[c].empty()) {
+            const uint64_t tb = table_bytes(cap), per = tb < kTableBlockBytes ? kTableBlockBytes / tb : 1;
+            void *p = nullptr;
+            const hipError_t e = hipMalloc(&p, per * tb);
+            if (e != hipSuccess) return e;
+            blocks.push_back(p);
+            for (uint64_t i = per; i-- > 0;) free_tables[c].push_back(static_cast<uint8_t *>(p) + i * tb);
+        }
+        *out = at(free_tables[c].back(), cap);
+        free_tables[c].pop_back();
+        return hipSuccess;
+    }
+    void give(const cdc::SpanTable &t, uint64_t cap) {
+        if (cap) free_tables[class_of(cap)].push_back(t.digest);
+    }
+    void release() {
+        for (void *p : blocks) (void)hipFree(p);
+        blocks.clear();
+        free_tables.clear();
+    }
+};
+
 }  // namespace
 
 struct cdc_files {
     cdc_store *store = nullptr;
     int device = 0;  // the store's, kept so that teardown needs nothing of the store
     uint64_t seg = 0;
+    TablePool pool;
+    // cdc_files_write_batch_device: per-request first[], destinations and statistics, one upload
+    uint64_t b_cap = 0;
+    uint8_t *h_batch = nullptr, *d_batch = nullptr;  // h_*: pinned host memory
     std::map<std::string, FileRec *> files;  // ordered: cdc_files_list is deterministic
     std::set<cdc_fh *> handles;
     // cdc_file_write_device: chunk list and digests of one call
@@ -95,51 +149,70 @@ int fail(int code, const std::string &msg) {
     return code;
 }
 
-void free_table(FileRec *f) {
-    (void)hipFree(f->t.off);
-    (void)hipFree(f->t.digest);
-    (void)hipFree(f->t.loc);
-    (void)hipFree(f->t.slot);
+// The table goes back to the layer's pool.  Every call synchronises its stream
+// before it returns, so a table handed out again is no longer read or written.
+void free_table(cdc_files *fs, FileRec *f) {
+    fs->pool.give(f->t, f->cap);
     f->t = cdc::SpanTable{};
     f->cap = 0;
 }
 
 void drop_files(cdc_files *fs) {
     for (auto &kv : fs->files) {
-        free_table(kv.second);
+        free_table(fs, kv.second);
         delete kv.second;
     }
     fs->files.clear();
 }
 
-// Capacity doubles: allocate, copy on the call's stream, free the old arrays.
-int reserve(FileRec *f, uint64_t need, hipStream_t s) {
+// Capacity doubles: a table of the next class from the pool, the spans copied on
+// the call's stream, the old table back to the pool.  copied == NULL: the copy is
+// waited for here.  Otherwise *copied is set when a copy was queued and the
+// caller waits once for all of them; until then only work on `s` may follow.
+int reserve(cdc_files *fs, FileRec *f, uint64_t need, hipStream_t s, bool *copied = nullptr) {
     if (need <= f->cap) return CDC_OK;
-    uint64_t cap = f->cap ? f->cap : 64;
+    uint64_t cap = f->cap ? f->cap : kTableMinCap;
     while (cap < need) cap *= 2;
     cdc::SpanTable t{};
-    hipError_t e = hipMalloc(&t.off, (cap + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc(&t.digest, cap * 32);
-    if (e == hipSuccess) e = hipMalloc(&t.loc, cap * 8);
-    if (e == hipSuccess) e = hipMalloc(&t.slot, cap * 4);
-    if (e == hipSuccess && f->n) {
+    hipError_t e = fs->pool.take(cap, &t);
+    if (e != hipSuccess) {
+        cdc::set_error(std::string("file layer: span table growth: ") + hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE;
+    }
+    if (f->n) {
         e = hipMemcpyAsync(t.off, f->t.off, (f->n + 1) * 8, hipMemcpyDeviceToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(t.digest, f->t.digest, f->n * 32, hipMemcpyDeviceToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(t.loc, f->t.loc, f->n * 8, hipMemcpyDeviceToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(t.slot, f->t.slot, f->n * 4, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e == hipSuccess && !copied) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(s);  // whatever was queued is done before the table is handed out again
+            fs->pool.give(t, cap);
+            cdc::set_error(std::string("file layer: span table growth: ") + hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE;
+        }
+        if (copied) *copied = true;
     }
-    if (e != hipSuccess) {
-        (void)hipFree(t.off);
-        (void)hipFree(t.digest);
-        (void)hipFree(t.loc);
-        (void)hipFree(t.slot);
-        cdc::set_error(std::string("file layer: span table growth: ") + hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE;
-    }
-    free_table(f);
+    free_table(fs, f);
     f->t = t;
     f->cap = cap;
+    return CDC_OK;
+}
+
+// What cdc_files_write_batch_device uploads in one copy, for n requests:
+// first[n + 1], the destinations and the preset statistics.
+uint64_t batch_bytes(uint64_t n) { return (n + 1) * 8 + n * (sizeof(cdc::AppendDst) + sizeof(cdc::AppendStat)); }
+
+int grow_batch(cdc_files *fs, uint64_t n) {
+    if (fs->b_cap >= n) return CDC_OK;
+    (void)hipHostFree(fs->h_batch);
+    (void)hipFree(fs->d_batch);
+    fs->h_batch = fs->d_batch = nullptr;
+    fs->b_cap = 0;
+    const uint64_t cap = n + n / 8 + 16;
+    FL_TRY(hipHostMalloc(&fs->h_batch, batch_bytes(cap)));
+    FL_TRY(hipMalloc(&fs->d_batch, batch_bytes(cap)));
+    fs->b_cap = cap;
     return CDC_OK;
 }
 
@@ -214,6 +287,9 @@ void release(cdc_files *fs) {
     (void)hipSetDevice(fs->device);
     drop_files(fs);
     for (cdc_fh *h : fs->handles) h->fs = nullptr;
+    fs->pool.release();
+    (void)hipHostFree(fs->h_batch);
+    (void)hipFree(fs->d_batch);
     (void)hipFree(fs->w_chunks);
     (void)hipFree(fs->w_dig);
     (void)hipFree(fs->a_val);
@@ -272,7 +348,7 @@ int64_t append(cdc_fh *fh, const uint8_t *d_data, uint64_t data_len, const cdc_c
     if (n == 0) return 0;
     FL_TRY(hipSetDevice(v.device));
     hipStream_t s = stream_of(fs, hip_stream);
-    if ((rc = reserve(f, f->n + n, s)) != CDC_OK) return rc;
+    if ((rc = reserve(fs, f, f->n + n, s)) != CDC_OK) return rc;
     if ((rc = grow_span_scratch(fs, n)) != CDC_OK) return rc;
     const int64_t put = cdc::store_put_slots(fs->store, d_data, data_len, d_chunks, d_digests, n, hip_stream);
     if (put < 0) return put;  // refused: the file is as it was
@@ -487,6 +563,11 @@ void cdc_files_destroy(cdc_files_t *fs) {
     if (fs) release(fs);
 }
 
+int64_t cdc_debug_files_table_blocks(const cdc_files_t *fs) {
+    if (!fs) return fail(CDC_EINVAL, "NULL file layer");
+    return (int64_t)fs->pool.blocks.size();
+}
+
 int cdc_files_clear(cdc_files_t *fs) {
     if (!fs) return fail(CDC_EINVAL, "NULL file layer");
     (void)hipSetDevice(cdc::store_view(fs->store).device);
@@ -519,7 +600,7 @@ int cdc_files_create_file(cdc_files_t *fs, const char *name, int create_new, cdc
     if (it != fs->files.end()) {
         if (!create_new) return fail(CDC_EEXIST, std::string("file layer: '") + name + "' already exists");
         (void)hipSetDevice(cdc::store_view(fs->store).device);
-        free_table(it->second);  // replaced by an empty file (file_layer.rs:95-96)
+        free_table(fs, it->second);  // replaced by an empty file (file_layer.rs:95-96)
         *it->second = FileRec{};
     } else {
         fs->files[name] = new FileRec();
@@ -608,6 +689,118 @@ int64_t cdc_file_write_device(cdc_fh_t *fh, cdc_handle_t *chunker, const uint8_t
 int64_t cdc_file_append_device(cdc_fh_t *fh, const uint8_t *d_data, size_t data_len, const cdc_chunk_t *d_chunks,
                                const uint8_t *d_digests, size_t n, void *hip_stream) {
     return append(fh, d_data, data_len, d_chunks, d_digests, n, hip_stream);
+}
+
+int64_t cdc_files_write_batch_device(cdc_files_t *fs, cdc_handle_t *chunker, size_t n, const cdc_fwrite_t *reqs,
+                                     uint64_t *spans, void *hip_stream) {
+    if (!fs) return fail(CDC_EINVAL, "NULL file layer");
+    if (!chunker) return fail(CDC_EINVAL, "cdc_files_write_batch_device: NULL chunker");
+    if (n == 0) return 0;
+    if (!reqs) return fail(CDC_EINVAL, "cdc_files_write_batch_device: NULL argument");
+    // Everything that can refuse, before the store or a table's contents are touched.
+    cdc::StoreView v = cdc::store_view(fs->store);
+    std::vector<FileRec *> recs(n);
+    std::set<FileRec *> seen;
+    std::vector<const uint8_t *> streams;
+    std::vector<uint64_t> lens;
+    uint64_t bytes = 0;
+    for (size_t i = 0; i < n; ++i) {
+        cdc_fh *fh = reqs[i].fh;
+        if (fh && fh->fs && fh->fs != fs)
+            return fail(CDC_EINVAL, "cdc_files_write_batch_device: a handle of another layer");
+        const int rc = lookup(fh, false, &recs[i]);
+        if (rc) return rc;
+        if (fh->readonly) return fail(CDC_EPERM, "file handle is read-only");
+        if (recs[i]->n && recs[i]->epoch != v.epoch)
+            return fail(CDC_ENOTFOUND, "file layer: the store was cleared since '" + fh->name + "' was written");
+        if (reqs[i].len && !reqs[i].d_data) return fail(CDC_EINVAL, "cdc_files_write_batch_device: NULL data");
+        if (!seen.insert(recs[i]).second)
+            return fail(CDC_EINVAL, "cdc_files_write_batch_device: '" + fh->name + "' is named twice");
+        if (reqs[i].len) {  // a request without bytes is no stream: it appends nothing
+            streams.push_back(reqs[i].d_data);
+            lens.push_back(reqs[i].len);
+            bytes += reqs[i].len;
+        }
+    }
+    const size_t ns = streams.size();
+    if (ns == 0) {
+        if (spans) std::memset(spans, 0, n * sizeof(uint64_t));
+        return 0;
+    }
+    FL_TRY(hipSetDevice(v.device));
+    hipStream_t s = stream_of(fs, hip_stream);
+    const uint64_t cap = cdc_batch_max_chunks(chunker, ns, lens.data());
+    if (fs->w_cap < cap) {
+        (void)hipFree(fs->w_chunks);
+        (void)hipFree(fs->w_dig);
+        fs->w_chunks = nullptr;
+        fs->w_dig = nullptr;
+        fs->w_cap = 0;
+        FL_TRY(hipMalloc(&fs->w_chunks, cap * sizeof(cdc_chunk_t)));
+        FL_TRY(hipMalloc(&fs->w_dig, cap * 32));
+        fs->w_cap = cap;
+    }
+    std::vector<uint64_t> sfirst(ns + 1, 0);
+    const auto t0 = std::chrono::steady_clock::now();
+    const int64_t m = cdc_chunk_batch_device(chunker, ns, streams.data(), lens.data(), fs->w_chunks, cap,
+                                             sfirst.data(), s);
+    if (m < 0) return m;
+    const auto t1 = std::chrono::steady_clock::now();
+    int rc = cdc_sha256_batch_device(chunker, ns, streams.data(), sfirst.data(), fs->w_chunks, fs->w_dig, s);
+    if (rc) return rc;
+    const auto t2 = std::chrono::steady_clock::now();
+
+    // Room for every file's new spans (the contents stay as they are), then the one put.
+    if ((rc = grow_batch(fs, n)) != CDC_OK) return rc;
+    if ((rc = grow_span_scratch(fs, (uint64_t)m)) != CDC_OK) return rc;
+    uint64_t *h_first = reinterpret_cast<uint64_t *>(fs->h_batch);
+    cdc::AppendDst *h_dst = reinterpret_cast<cdc::AppendDst *>(h_first + n + 1);
+    cdc::AppendStat *h_stat = reinterpret_cast<cdc::AppendStat *>(h_dst + n);
+    bool copied = false;
+    h_first[0] = 0;
+    for (size_t i = 0, j = 0; i < n; ++i) {
+        const uint64_t cnt = reqs[i].len ? sfirst[j + 1] - sfirst[j] : 0;
+        if (reqs[i].len) ++j;
+        h_first[i + 1] = h_first[i] + cnt;
+        if (cnt && (rc = reserve(fs, recs[i], recs[i]->n + cnt, s, &copied)) != CDC_OK) {
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
+    }
+    if (copied) FL_TRY(hipStreamSynchronize(s));
+    const int64_t put = cdc::store_put_batch_slots(fs->store, ns, streams.data(), lens.data(), sfirst.data(),
+                                                   fs->w_chunks, fs->w_dig, s);
+    if (put < 0) return put;  // refused: every file is as it was
+    v = cdc::store_view(fs->store);
+    for (size_t i = 0; i < n; ++i) {
+        h_dst[i] = cdc::AppendDst{recs[i]->t, recs[i]->n, recs[i]->size};
+        h_stat[i] = cdc::AppendStat{0, ~0ull, 0};
+    }
+    uint64_t *d_first = reinterpret_cast<uint64_t *>(fs->d_batch);
+    cdc::AppendDst *d_dst = reinterpret_cast<cdc::AppendDst *>(d_first + n + 1);
+    cdc::AppendStat *d_stat = reinterpret_cast<cdc::AppendStat *>(d_dst + n);
+    FL_TRY(hipMemcpyAsync(fs->d_batch, fs->h_batch, batch_bytes(n), hipMemcpyHostToDevice, s));
+    FL_TRY(cdc::launch_files_append_batch(d_dst, d_first, n, (uint64_t)m, v.slot_of, v.length, v.loc, fs->w_dig,
+                                          fs->a_val, fs->a_block, d_stat, s));
+    FL_TRY(hipMemcpyAsync(h_stat, d_stat, n * sizeof(cdc::AppendStat), hipMemcpyDeviceToHost, s));
+    FL_TRY(hipStreamSynchronize(s));
+    const double chunk_s = std::chrono::duration<double>(t1 - t0).count();
+    const double hash_s = std::chrono::duration<double>(t2 - t1).count();
+    for (size_t i = 0; i < n; ++i) {
+        const uint64_t cnt = h_first[i + 1] - h_first[i];
+        const double share = (double)reqs[i].len / (double)bytes;
+        reqs[i].fh->chunk_s += chunk_s * share;
+        reqs[i].fh->hash_s += hash_s * share;
+        if (spans) spans[i] = cnt;
+        if (!cnt) continue;
+        FileRec *f = recs[i];
+        f->n += cnt;
+        f->size += h_stat[i].bytes;
+        f->epoch = v.epoch;
+        if (h_stat[i].least != ~0ull && h_stat[i].least + 1 < f->min_len) f->min_len = h_stat[i].least + 1;
+        f->zeros += h_stat[i].zeros;
+    }
+    return m;
 }
 
 int64_t cdc_file_read_complete_device(cdc_fh_t *fh, uint8_t *d_out, size_t out_cap, cdc_chunk_t *d_spans,
@@ -725,11 +918,12 @@ int64_t cdc_files_get_to_dedup_ratio(cdc_files_t *fs, const char *name, double d
     FileRec made;  // the new file; its table is freed again unless the call succeeds
     made.epoch = src->epoch;
     struct Guard {
+        cdc_files *fs;
         FileRec *f;
         ~Guard() {
-            if (f) free_table(f);
+            if (f) free_table(fs, f);
         }
-    } guard{&made};
+    } guard{fs, &made};
     if (src->n >= 2) {
         // 1. The unique list over all but the last span (the reference's zip with skip(1)).
         const uint64_t m = src->n - 1;
@@ -767,7 +961,7 @@ int64_t cdc_files_get_to_dedup_ratio(cdc_files_t *fs, const char *name, double d
                 return fail(CDC_ENOMEM, "cdc_files_get_to_dedup_ratio: the new span table cannot be allocated");
             // 3. The new table: gather, scan, write.
             if (n) {
-                if ((rc = reserve(&made, n, s)) != CDC_OK) return rc;
+                if ((rc = reserve(fs, &made, n, s)) != CDC_OK) return rc;
                 if ((rc = grow_span_scratch(fs, n)) != CDC_OK) return rc;
                 FL_TRY(mem.alloc(&sidx, n));
                 FL_TRY(hipMemsetAsync(fs->d_stat, 0xFF, 8, s));
@@ -785,7 +979,7 @@ int64_t cdc_files_get_to_dedup_ratio(cdc_files_t *fs, const char *name, double d
     }
     // HashMap::insert (file_layer.rs:265): the name's old file, if any, is replaced.
     FileRec *&slot = fs->files[new_name];
-    if (slot) free_table(slot);
+    if (slot) free_table(fs, slot);
     else slot = new FileRec();
     *slot = made;
     guard.f = nullptr;

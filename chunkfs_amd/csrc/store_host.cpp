@@ -608,6 +608,12 @@ int64_t store_put_slots(cdc_store *st, const uint8_t *d_data, uint64_t data_len,
     return put(st, 1, streams, lens, first, d_chunks, d_digests, nullptr, hip_stream);
 }
 
+int64_t store_put_batch_slots(cdc_store *st, size_t n_streams, const uint8_t *const *d_streams, const uint64_t *lens,
+                              const uint64_t *first, const cdc_chunk_t *d_chunks, const uint8_t *d_digests,
+                              void *hip_stream) {
+    return put(st, n_streams, d_streams, lens, first, d_chunks, d_digests, nullptr, hip_stream);
+}
+
 }  // namespace cdc
 
 extern "C" {

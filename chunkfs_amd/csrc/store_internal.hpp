@@ -33,6 +33,12 @@ StoreView store_view(const cdc_store *st);
 int64_t store_put_slots(cdc_store *st, const uint8_t *d_data, uint64_t data_len, const cdc_chunk_t *d_chunks,
                         const uint8_t *d_digests, uint64_t n, void *hip_stream);
 
+// cdc_store_put_batch_device in the same way: first[] (HOST, n_streams + 1
+// entries, first[0] = 0, not decreasing) is the caller's to get right; on
+// success store_view().slot_of holds the first[n_streams] slots in chunk order.
+int64_t store_put_batch_slots(cdc_store *st, size_t n_streams, const uint8_t *const *d_streams, const uint64_t *lens,
+                              const uint64_t *first, const cdc_chunk_t *d_chunks, const uint8_t *d_digests,
+                              void *hip_stream);
 
 // The scrubbed state: true once the store holds target-kind containers, whose
 // bytes are found through the slot's current container (the base arena was

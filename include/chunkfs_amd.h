@@ -38,7 +38,8 @@ extern "C" {
  *    cdc_store_keys_device, cdc_scrub_measurements_t, cdc_scrub_stats_t,
  *    CDC_SCRUB_*; the bench fixture -- cdc_files_get_to_dedup_ratio,
  *    cdc_file_verify_device, cdc_store_size_distribution_device; the AE
- *    chunker -- CDC_ALGO_AE, cdc_create_ae. */
+ *    chunker -- CDC_ALGO_AE, cdc_create_ae; the batch write --
+ *    cdc_files_write_batch_device, cdc_fwrite_t. */
 #define CHUNKFS_AMD_ABI_VERSION 6
 
 /* Chunk{offset,length} -- reference src/lib.rs:43-47 (usize fields; u64 here). */
@@ -594,6 +595,13 @@ typedef struct cdc_pread {
     uint8_t *d_dst; /* DEVICE, len bytes, any alignment */
 } cdc_pread_t;
 
+/* One file of cdc_files_write_batch_device. */
+typedef struct cdc_fwrite {
+    cdc_fh_t *fh;
+    const uint8_t *d_data; /* DEVICE, 16-byte aligned when len > 0 */
+    uint64_t len;
+} cdc_fwrite_t;
+
 /* FileLayer::default over `store` (not owned: destroy the layer first).
  * seg_size is the segment of cdc_file_read_device, SEG_SIZE of
  * file_layer.rs:162; 0 = 1 MiB. */
@@ -640,6 +648,41 @@ int64_t cdc_file_write_device(cdc_fh_t *fh, cdc_handle_t *chunker, const uint8_t
  * legal.  A span's length is that of the chunk stored under its digest. */
 int64_t cdc_file_append_device(cdc_fh_t *fh, const uint8_t *d_data, size_t data_len, const cdc_chunk_t *d_chunks,
                                const uint8_t *d_digests, size_t n, void *hip_stream);
+
+/* n FileSystem::write_to_file calls (mod.rs:93-110) as one: every request is one
+ * chunk_data over its whole buffer, as cdc_file_write_device -- but all requests
+ * share one cdc_chunk_batch_device (each request a stream of its own: AE and
+ * every other chunker see it as its own buffer), one cdc_sha256_batch_device,
+ * one put and one segmented append, so the host waits for the device a fixed
+ * number of times however many files there are.  reqs: HOST array of n entries.
+ * Returns the total number of spans appended; spans (HOST[n], nullable)
+ * receives each request's count.
+ *
+ * The contract: after the call everything observable equals n calls of
+ * cdc_file_write_device in request order on the same starting state -- every
+ * file's cdc_file_stat size and span count, its digest sequence, the span
+ * offsets and the bytes read back, the distribution, and cdc_store_stats in
+ * every field, arena_used included.  First insert wins in request order, and the
+ * arena layout is the chunk-order layout of cdc_store_put_batch_device; in the
+ * scrubbed state a digest that exists as a target adds nothing, as in a put.
+ * Stream and epoch conventions are cdc_file_write_device's.  n == 0 returns 0;
+ * a request with len == 0 is legal, appends nothing and reports 0 spans.
+ *
+ * All or nothing -- a refused call changes no file and not the store:
+ *   CDC_EINVAL    a NULL argument, len > 0 with NULL data, a handle of another
+ *                 layer or one that outlived its layer, two requests naming the
+ *                 same file, or (from the put) a chunk outside its buffer;
+ *   CDC_EPERM     a read-only handle anywhere in the list;
+ *   CDC_ENOTFOUND an unknown file, or one whose spans predate a store clear;
+ *   CDC_ENOMEM    the put's: max_chunks or the arena too small "as if every
+ *                 chunk were new", over the whole batch.
+ * Span tables may have grown in capacity before a refusal; their contents have
+ * not changed.
+ *
+ * Each handle's chunk_seconds / hash_seconds grow by the batch's chunking /
+ * hashing wall time times len_i / sum of len, so they sum to the batch's time. */
+int64_t cdc_files_write_batch_device(cdc_files_t *fs, cdc_handle_t *chunker, size_t n, const cdc_fwrite_t *reqs,
+                                     uint64_t *spans, void *hip_stream);
 
 /* FileSystem::read_file_complete (mod.rs:149-152): every span in order, back to
  * back in d_out (DEVICE, any alignment); d_spans (nullable, DEVICE

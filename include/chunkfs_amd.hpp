@@ -393,6 +393,14 @@ class Files {
     void pread_batch_device(size_t n, const cdc_pread_t *reqs, uint64_t *got, void *hip_stream = nullptr) {
         check(cdc_files_pread_batch_device(fs_, n, reqs, got, hip_stream));
     }
+    // n write_to_file calls as one (cdc_files_write_batch_device): one chunk
+    // batch, one hash batch, one put, one append; the files and the store end
+    // up as the n single writes in request order would leave them.  spans
+    // (nullable, n entries) receives each request's count; returns their sum.
+    int64_t write_batch_device(Chunker &chunker, size_t n, const cdc_fwrite_t *reqs, uint64_t *spans = nullptr,
+                               void *hip_stream = nullptr) {
+        return check(cdc_files_write_batch_device(fs_, chunker.handle(), n, reqs, spans, hip_stream));
+    }
     // get_to_dedup_ratio (mod.rs:170-178, file_layer.rs:208-268): derives the file
     // "{name}.{ratio:.2}" and returns its name; span offsets in it are true byte
     // positions.  Throws CDC_EINVAL for a ratio < 1, NaN or infinite, and when the

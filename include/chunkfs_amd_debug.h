@@ -78,6 +78,12 @@ int cdc_debug_read_bw(cdc_handle_t *h, const uint8_t *d_buf, size_t len, int rep
  * handle has none yet.  Returns the JSON length or a negative CDC_E* code. */
 int64_t cdc_debug_host_placement(cdc_handle_t *h, char *buf, size_t cap);
 
+/* Device blocks the file layer's span-table pool holds.  Span tables are carved
+ * out of these blocks (a free list per capacity class, capacities doubling from
+ * 64 spans), so a new file costs no device allocation; the blocks are released
+ * by cdc_files_destroy.  CDC_EINVAL for a NULL layer. */
+int64_t cdc_debug_files_table_blocks(const cdc_files_t *fs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,6 +47,19 @@ Bench fixture, on the file of (d)-(f), in the same run:
       every call; its span table is allocated inside the call);
   (n) cdc_store_size_distribution_device at adjustment 1024.
 
+Many files (skipped with --no-batch-write), each leg on a fresh layer and store,
+FastCDC 4096/8192/16384, file i filled with splitmix64 seeded i:
+
+  (o) 1024 files x 64 KiB written by a loop of cdc_file_write_device and by
+      one cdc_files_write_batch_device;
+  (p) 16 files x 64 MiB, written the same two ways.
+
+(o) and (p) are wall time around the calls, with a device synchronisation on
+both sides (the loop is host-bound: events on one stream would not see the
+host's share); the layer is cleared and the files are created outside the
+timed window, and the loop and the batch alternate.  Median of 10 after a
+warm-up.
+
 Prints one JSON line; --out also writes it to a file.
 """
 import argparse
@@ -150,6 +163,74 @@ def scrub_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med, fread_ms):
     return res
 
 
+def batch_write_legs(a, c, L, P, ch):
+    """Legs (o)-(p): many files by a loop of single writes and by one batch write."""
+    import time
+
+    import numpy as np
+    import torch
+    from chunkfs_amd import _lib
+
+    res = {}
+    for leg, files, size in (("o_1024x64KiB", 1024, 64 << 10), ("p_16x64MiB", 16, 64 << 20)):
+        data = torch.empty(files * size, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        for i in range(files):
+            _lib.check(L.cdc_fill_splitmix64_device(P(data.data_ptr() + i * size), size, i, None))
+        cap = ch.batch_max_chunks([size] * files)
+        fsys = c.FileSystem(store=c.ChunkStore(cap, files * size + 16 * cap))
+        reqs = (_lib.cdc_fwrite_t * files)()
+        for i in range(files):
+            reqs[i].d_data, reqs[i].len = data.data_ptr() + i * size, size
+        counts = (ctypes.c_uint64 * files)()
+        state = {}
+
+        def fresh():
+            fsys.clear_database()
+            state["h"] = [fsys.create_file(f"f{i:04d}", ch) for i in range(files)]
+            for i, h in enumerate(state["h"]):
+                reqs[i].fh = h._fh.value
+
+        def loop():
+            total = 0
+            for i, h in enumerate(state["h"]):
+                got = L.cdc_file_write_device(h._fh, ch._h, P(data.data_ptr() + i * size), size, None)
+                assert got > 0, f"cdc_file_write_device: {got}"
+                total += got
+            return total
+
+        def batch():
+            got = L.cdc_files_write_batch_device(fsys._h, ch._h, files, reqs, counts, None)
+            assert got > 0, f"cdc_files_write_batch_device: {got}"
+            return got
+
+        def wall(fn):
+            fresh()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            spans = fn()
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) * 1e3
+            return ms, spans, fsys.store.stats()["arena_used"]
+
+        t_loop, t_batch = [], []
+        for it in range(a.warmup + a.iters):
+            (ml, sl, ul), (mb, sb, ub) = wall(loop), wall(batch)
+            if (sl, ul) != (sb, ub):
+                raise SystemExit(f"store_bench: the batch write and the loop differ ({sl}, {ul}) != ({sb}, {ub})")
+            if it >= a.warmup:
+                t_loop.append(ml)
+                t_batch.append(mb)
+        med = lambda v: float(np.median(v))  # noqa: E731
+        res[leg] = {"files": files, "file_bytes": size, "spans": sl,
+                    "loop_ms": med(t_loop), "loop_ms_min_max": [min(t_loop), max(t_loop)],
+                    "batch_ms": med(t_batch), "batch_ms_min_max": [min(t_batch), max(t_batch)],
+                    "loop_over_batch": med(t_loop) / med(t_batch),
+                    "table_blocks": L.cdc_debug_files_table_blocks(fsys._h)}
+        del fsys, data
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--bytes", type=int, default=1 << 30)
@@ -158,6 +239,7 @@ def main():
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--out", default=None, help="also write the JSON result to this file")
     ap.add_argument("--no-scrub", action="store_true", help="skip the scrub-stage legs (g)-(j)")
+    ap.add_argument("--no-batch-write", action="store_true", help="skip the many-files legs (o)-(p)")
     ap.add_argument("--scrub-iters", type=int, default=3)
     ap.add_argument("--scrub-groups", default="4096,64m;65536,256m;1048576,1024m",
                     help="RECHUNK groups to time: containers,bytes[k|m] separated by ';'")
@@ -353,6 +435,8 @@ def main():
     }
     if not a.no_scrub:
         res.update(scrub_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med, med(t_fread)))
+    if not a.no_batch_write:
+        res["batch_write"] = batch_write_legs(a, c, L, P, ch)
     line = json.dumps(res)
     print(line)
     if a.out:
