@@ -234,7 +234,8 @@ int cdc_fill_splitmix64_device(uint8_t *d_buf, size_t len, uint64_t seed, void *
     return CDC_OK;
 }
 
-int cdc_debug_pipeline(const cdc_handle_t *h) { return h ? h->engine->pipeline() : (int)bad_handle(); }
+// (one FastCDC pipeline, scan + resolve, since the others were removed)
+int cdc_debug_pipeline(const cdc_handle_t *h) { return h ? 3 : (int)bad_handle(); }
 
 uint32_t cdc_debug_record_cap(const cdc_handle_t *h) { return h ? h->engine->record_cap() : 0; }
 

@@ -1,11 +1,15 @@
 // host_common.hpp -- what the host classes behind the C ABI share (Engine,
-// WalkEngine, the host path): the error text, HIP_TRY, the pinned-memory
-// placement and the per-call stream tables.
+// FastEngine, WalkEngine, the host path): the error text, HIP_TRY, the
+// pinned-memory placement, the copy pool and the per-call stream tables.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+#include <condition_variable>
 #include <cstring>
+#include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/chunkfs_amd.h"
@@ -44,6 +48,46 @@ struct HostPlacement {
     static HostPlacement probe(int device);
     hipError_t host_malloc(void **ptr, size_t bytes, unsigned flags) const;
     static int node_of(const void *addr);  // NUMA node of the page at addr (-1: unknown)
+};
+
+// Pageable -> pinned copies of the host path split over a few threads (one
+// core copies ~20 GB/s, below what the H2D DMA takes).  One pool per process
+// (CopyPool::shared), helpers spin briefly after a job (the next 1 MiB segment
+// usually follows within microseconds), then sleep.  copy() returns when
+// every part is done (hostpath.cpp).
+class CopyPool {
+  public:
+    CopyPool(unsigned threads, unsigned spin_us, const std::vector<int> &cpus);
+    ~CopyPool();
+    static CopyPool &for_node(int node, const std::vector<int> &cpus);
+    void copy(void *dst, const void *src, size_t n);
+    // Streamed copy for the small kernel's feed: pieces of `piece` bytes,
+    // claimed by the caller and the awake helpers, each announced by
+    // ready[piece index] = seq once copied (the device reads it over PCIe
+    // while later pieces are still being copied).  Returns once every piece
+    // is announced.
+    void copy_feed(void *dst, const void *src, size_t n, size_t piece, volatile uint64_t *ready, uint64_t seq);
+    unsigned threads() const { return (unsigned)th_.size() + 1; }
+    unsigned pinned() const { return pinned_; }
+
+  private:
+    void run(unsigned id);
+    void work();  // claim and copy pieces until none is left
+    void job(void *dst, const void *src, size_t n, size_t piece, volatile uint64_t *ready, uint64_t seq);
+    std::vector<std::thread> th_;
+    std::mutex m_, job_m_;
+    std::condition_variable cv_;
+    unsigned spin_us_ = 200;
+    unsigned pinned_ = 0;  // helpers bound to the node's CPUs
+    std::atomic<uint64_t> gen_{0};
+    std::atomic<bool> stop_{false}, open_{false};
+    std::atomic<unsigned> active_{0};  // helpers inside the current job
+    std::atomic<size_t> next_{0}, done_{0};  // next piece to claim, pieces copied
+    uint8_t *dst_ = nullptr;
+    const uint8_t *src_ = nullptr;
+    size_t n_ = 0, piece_ = 0, np_ = 0;
+    volatile uint64_t *ready_ = nullptr;  // feed words (nullptr: a plain copy)
+    uint64_t seq_ = 0;
 };
 
 // Batches of more than kSmallBatch bytes are the ones the async entry

@@ -35,6 +35,7 @@
 #include <sstream>
 
 #include "engine.hpp"
+#include "fast_engine.hpp"
 
 #include <atomic>
 
@@ -382,22 +383,23 @@ int64_t Engine::chunk_host(const uint8_t *data, size_t len, cdc_chunk_t *out, si
     // copy overlaps the launch and the reads; no DMA, no second kernel on the
     // call's critical path (small.hip).  A call the kernel's budgets cannot
     // take falls through to the regular upload + pipeline.
-    if (algo_ == CDC_ALGO_FASTCDC && small_zc_ && !digests && small_ok(len) && len <= kRingSlot) {
-        rc = ensure_host_staging(1);
-        if (rc) return rc;
+    if (fast_ && fast_->small_zero_copy() && !digests && fast_->small_ok(len) && len <= kRingSlot) {
         const uint32_t k = ring_next_;
         ring_next_ = (ring_next_ + 1) % kRingSlots;
         HIP_TRY(hipEventSynchronize(ring_ev_[k]));
         uint8_t *slot = static_cast<uint8_t *>(h_ring_) + (size_t)k * kRingSlot;
         uint64_t first[2] = {0, 0};
-        if (small_feed_) {
-            rc = run_small(h_ring_dev_ + (size_t)k * kRingSlot, len, d_hout_, need, first, own_stream_, true, data,
-                           slot, k);
-            t1 = t0 + small_copy_s_;
+        if (fast_->small_feed()) {
+            const FastEngine::SmallFeed feed{data, slot, h_ready_ + (size_t)k * small::kFeedPieces,
+                                             h_ready_dev_ + (size_t)k * small::kFeedPieces, pool_};
+            rc = fast_->run_small(h_ring_dev_ + (size_t)k * kRingSlot, len, d_hout_, need, first, own_stream_,
+                                  placement(), true, &feed);
+            t1 = t0 + fast_->small_copy_s();
         } else {  // (A/B: the whole copy, then the launch)
             pool_->copy(slot, data, len);
             t1 = now_s();
-            rc = run_small(h_ring_dev_ + (size_t)k * kRingSlot, len, d_hout_, need, first, own_stream_, true);
+            rc = fast_->run_small(h_ring_dev_ + (size_t)k * kRingSlot, len, d_hout_, need, first, own_stream_,
+                                  placement(), true);
         }
         HIP_TRY(hipEventRecord(ring_ev_[k], own_stream_));  // the slot is free once the kernel retires
         if (rc < 0) return rc;
@@ -424,9 +426,9 @@ int64_t Engine::chunk_host(const uint8_t *data, size_t len, cdc_chunk_t *out, si
         const uint8_t *p = d_data_;
         const uint64_t l = len;
         uint64_t first[2] = {0, 0};
-        small_skip_ = small_tried;  // (the small kernel already declined these bytes)
-        count = chunk_batch_device(1, &p, &l, reinterpret_cast<cdc_chunk_t *>(d_hout_), need, first, own_stream_);
-        small_skip_ = false;
+        // (small_tried: the small kernel already declined these bytes)
+        count = batch_device(1, &p, &l, reinterpret_cast<cdc_chunk_t *>(d_hout_), need, first, own_stream_, false,
+                             small_tried);
         if (count < 0) return count;
         // The done word the collection spins on says the resolve's last block
         // is through; the list is read only once the stream itself has retired
@@ -669,7 +671,8 @@ int64_t Engine::host_placement_json(char *out, size_t cap) {
 
 int Engine::host_stats(double *v, size_t n) const {
     const double s[8] = {(double)host_.calls, host_.upload_s, host_.total_s, wr_.chunk_s, (double)wr_.segments,
-                         (double)small_calls_, (double)small_fallbacks_, (double)host_.guard_trips};
+                         fast_ ? (double)fast_->small_calls() : 0.0, fast_ ? (double)fast_->small_fallbacks() : 0.0,
+                         (double)host_.guard_trips};
     for (size_t i = 0; i < n && i < 8; ++i) v[i] = s[i];
     return CDC_OK;
 }

@@ -1,8 +1,8 @@
 """FastCDC size table and a plain-Python model of the engine's derived
 parameters (a helper of test_fast_sizes_model.py and test_gpu_fast_sizes.py).
 
-The model restates, from the size triple alone, what Engine::create
-(chunkfs_amd/csrc/engine.cpp) derives: the mask pair, the candidate-test form,
+The model restates, from the size triple alone, what FastEngine::create
+(chunkfs_amd/csrc/fast_engine.cpp) derives: the mask pair, the candidate-test form,
 the span size, the record cap, the chunk starts per span and the one-launch
 small kernel's eligibility.  The GPU tests compare the two values the engine
 exports (cdc_debug_record_cap, the span count of cdc_debug_copy) with it, so a
@@ -22,7 +22,7 @@ import oracle
 
 KIB, MIB = 1 << 10, 1 << 20
 
-# Engine constants restated (engine.cpp, host_common.hpp, small.hpp).
+# Engine constants restated (fast_engine.cpp, host_common.hpp, small.hpp).
 MIN_SPAN_LOG2, MAX_SPAN_LOG2 = 16, 17   # 64 KiB spans, 128 KiB while records stay sparse
 SMALL_BATCH = 8 * MIB                   # batches up to this use the small-batch span size
 SMALL_MAX_BYTES = 4 * MIB               # the one-launch kernel's longest stream
@@ -158,7 +158,7 @@ def params(mn, avg, mx):
 
 
 def small_eligible(p, n):
-    """Engine::small_ok: the one-launch kernel takes a single stream of n bytes."""
+    """FastEngine::small_ok: the one-launch kernel takes a single stream of n bytes."""
     return p.small_on and 0 < n <= SMALL_MAX_BYTES and (n >> p.pmin) <= SMALL_REC_BUDGET
 
 
@@ -171,7 +171,7 @@ def write_window_bytes():
 
 
 def batch_span_log2(p, lens):
-    """Span size of one batch (Engine::fast_submit)."""
+    """Span size of one batch (FastEngine::enqueue)."""
     return p.small_span_log2 if sum(lens) <= SMALL_BATCH else p.span_log2
 
 

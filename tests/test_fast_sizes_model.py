@@ -33,7 +33,7 @@ def test_model_refuses_undefined_orderings():
 
 
 def test_model_known_rows():
-    """Rows worked out by hand from engine.cpp and the mask table."""
+    """Rows worked out by hand from fast_engine.cpp and the mask table."""
     p = fs.params(4096, 8192, 16384)
     assert (p.bits, p.aligned, p.trunc, p.pop_c, p.span_log2, p.small_span_log2, p.cap, p.smax, p.small_on) == \
         (13, True, 47, 12, 17, 14, 256, 34, True)

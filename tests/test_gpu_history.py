@@ -8,7 +8,9 @@ bytes (no tolerances).  tests/test_history_model.py shows, on the CPU, that in
 every sequence an answer computed from the state of the call 1, 3 or 4 back
 differs from the right one; a mismatch here names that call (harness.diagnose).
 
-Engine state each sequence targets (chunkfs_amd/csrc/engine.hpp):
+Engine state each sequence targets (chunkfs_amd/csrc/engine.hpp; small_ws_,
+the staging blocks hb_, the device slots fs_, the workspace and d_gear_ are
+FastEngine's, fast_engine.hpp):
 
     S1  h_out_ (the host-mapped chunk list), the pinned ring, d_data_; on the
         default handle also small_ws_ and the feed words
