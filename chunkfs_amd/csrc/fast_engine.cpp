@@ -435,6 +435,7 @@ int64_t FastEngine::enqueue(size_t n, const uint8_t *const *d_streams, const uin
     }
     rec.live = true;
     seq_ = seq + 1;
+    small_last_len_ = 0;
     any_ = true;
     stream_ = s;
     any_two_stream_ = two_stream;
@@ -630,12 +631,16 @@ int FastEngine::run_small(const uint8_t *data, uint64_t len, cdc_chunk_t *d_out,
         }
         std::fprintf(stderr, "\n");
     }
+    small_last_len_ = 0;
     if (h_stats[small::kWordFallback]) {
         ++small_fallbacks_;
         return kSmallFallback;
     }
     first[0] = 0;
     first[1] = h_first[1];
+    small_last_len_ = len;
+    small_last_staged_ = host_input;
+    small_last_stream_ = s;
     return CDC_OK;
 }
 
@@ -675,6 +680,28 @@ int FastEngine::timing_back(uint32_t back, cdc_timing_t &out) {
 }
 
 int64_t FastEngine::debug_copy(int what, void *out, size_t max_bytes) {
+    if (what >= 2 && what <= 7) {  // the small kernel's scratch, as the last call left it
+        const bool whole = what >= 5;  // 5..7: the arrays of 2..4 at their full size
+        const int arr = whole ? what - 3 : what;
+        if (small_last_len_ == 0 || (arr == 4 && !small_last_staged_)) {
+            set_error(small_last_len_ ? "debug_copy: the last one-launch call read device input (no copy)"
+                                      : "debug_copy: the last FastCDC call was not a one-launch call");
+            return CDC_EINVAL;
+        }
+        const uint64_t blocks =
+            whole ? small::kMaxBlocks : (small_last_len_ + small::kBlockBytes - 1) / small::kBlockBytes;
+        const void *src = arr == 2 ? (const void *)small_ws_.bcnt
+                          : arr == 3 ? (const void *)small_ws_.brec
+                                     : (const void *)small_ws_.copy;
+        size_t bytes = arr == 2 ? blocks * 4
+                       : arr == 3 ? blocks * small::kBlockRecCap * 8
+                                  : (size_t)(whole ? small::kMaxBytes : small_last_len_);
+        if (bytes > max_bytes) bytes = max_bytes;
+        HIP_TRY(hipSetDevice(device_));
+        HIP_TRY(hipStreamSynchronize(small_last_stream_));
+        if (bytes) HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+        return (int64_t)bytes;
+    }
     if (seq_ == 0) {
         set_error("debug_copy: no FastCDC batch yet");
         return CDC_EINVAL;

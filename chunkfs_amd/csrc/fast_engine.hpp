@@ -64,7 +64,11 @@ class FastEngine {
     int timing_back(uint32_t back, cdc_timing_t &out);
     // Debug (include/chunkfs_amd_debug.h): an intermediate array of the last
     // pipeline batch.  what: 0 = per-span candidate counts (u32), 1 =
-    // candidate records (u32, record_cap() per span).  Returns bytes copied.
+    // candidate records (u32, record_cap() per span).  2..4: the scratch of
+    // the last call when the one-launch kernel took it (small.hip): per-block
+    // record counts, per-block record regions, the device copy of a host
+    // input; 5..7: the same arrays whole, with what earlier calls left beyond
+    // the last one's blocks.  Returns bytes copied.
     int64_t debug_copy(int what, void *out, size_t max_bytes);
     uint32_t record_cap() const { return cap_; }
 
@@ -201,6 +205,12 @@ class FastEngine {
     uint64_t small_calls_ = 0, small_fallbacks_ = 0;
     uint64_t small_seq_ = 0;       // launch sequence number (feed words, block publication tags)
     double small_copy_s_ = 0;
+    // The last FastCDC call, when the small kernel took it (debug_copy): its
+    // length (0: a pipeline batch, a fallback or none), whether its input was
+    // host memory (device copy written) and its stream.
+    uint64_t small_last_len_ = 0;
+    bool small_last_staged_ = false;
+    hipStream_t small_last_stream_ = nullptr;
 };
 
 }  // namespace cdc

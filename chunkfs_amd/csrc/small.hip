@@ -392,6 +392,12 @@ __global__ __launch_bounds__(kThreads, 1) void small_kernel(const uint8_t *__res
         // bytes P-64 .. P-1 (the first lane's 48 warm-up bytes); zeros at the
         // stream start, where no record can be used (positions < a0 + 47)
         if (lane < 4) B[lane] = P ? ld16(data + P - 64 + lane * 16) : make_uint4(0, 0, 0, 0);
+    } else if (fed && P < n + 64) {
+        // No byte of the stream lies in this piece, but its last ones lie in
+        // the 64 before it: a truncated region that ends with the stream and
+        // whose 52 word-aligned bytes reach past the piece edge is evaluated
+        // from this wave's buffer (below), so those 64 bytes must be in it.
+        if (lane < 4) B[lane] = ld16_guarded(data, P - 64 + lane * 16, n);
     }
     __syncthreads();  // (also the GEAR table)
     if (diag && tid == 0) ws.bstamp[blockIdx.x * 8 + 1] = __builtin_amdgcn_s_memrealtime();

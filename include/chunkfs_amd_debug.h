@@ -21,8 +21,21 @@ uint32_t cdc_debug_record_cap(const cdc_handle_t *h);
  * max_bytes): 0 = per-span candidate counts (u32; > cap means overflowed),
  * 1 = candidate records (u32, cap per span: offset in span (bits 0-23) |
  * truncated-region result of a chunk starting there (bits 24-29; 63 none, 62
- * not precomputed) | bit30 mask_l hit | bit31 mask_s hit).  Returns the bytes copied or a negative CDC_E*
- * code (CDC_EINVAL for any other `what`). */
+ * not precomputed) | bit30 mask_l hit | bit31 mask_s hit).
+ * When the handle's last FastCDC call (cdc_chunk_data, or a single-stream
+ * cdc_chunk_batch_device) was taken by the one-launch kernel (small.hip) and
+ * did not fall back, its scan stage can be read as well (CDC_EINVAL after any
+ * other call): 2 = per-block record counts (u32, one per 32 KiB block of the
+ * call; > 256 means the block overflowed), 3 = per-block record regions (u64,
+ * 256 per block: bits 0-29 stream offset | bit30 mask_l hit | bit31 mask_s hit
+ * | truncated-region result of a chunk starting there << 32 | that of its
+ * max-cut successor << 40; 63 none, 62 left to the last block), 4 = the first
+ * `len` bytes of the device copy of the input (a cdc_chunk_data call only:
+ * CDC_EINVAL after a device-input call, which writes no copy).  5, 6, 7 = the
+ * arrays of 2, 3, 4 at their full size (128 blocks, 4 MiB), i.e. with whatever
+ * earlier calls left beyond the last call's blocks.
+ * Returns the bytes copied or a negative CDC_E* code (CDC_EINVAL for any other
+ * `what`). */
 int64_t cdc_debug_copy(cdc_handle_t *h, int what, void *out, size_t max_bytes);
 /* Host-path statistics into v[0..n): cdc_chunk_data calls, their upload
  * seconds (CPU copy into the pinned ring + queueing the H2D), their total
