@@ -647,6 +647,27 @@ class ChunkStore:
     def clear(self):
         check(lib().cdc_store_clear(self._h))
 
+    def retain_device(self, d_digests, n, stream=None):
+        """cdc_store_retain_device: keep exactly the containers whose digest is
+        among the n given (device pointer, 32 bytes each; duplicates allowed, n =
+        0 keeps none), drop the rest and compact the arena in place.  Returns the
+        number kept.  CdcError(CDC_ENOTFOUND) for a digest that is not stored,
+        CdcError(CDC_ENOTSUP) on a scrubbed store; a refused call changes nothing.
+        Every file layer on this store goes stale (include/chunkfs_amd.h,
+        "Removal and collection")."""
+        return check(lib().cdc_store_retain_device(self._h, _ptr(d_digests), n, _ptr(stream)))
+
+    def retain(self, digests):
+        """retain_device for a host array of digests ((n, 32) uint8)."""
+        import torch
+        dig = np.ascontiguousarray(np.asarray(digests, dtype=np.uint8)).reshape(-1, 32)
+        if len(dig) == 0:
+            return self.retain_device(None, 0)
+        dev = f"cuda:{self.device}"
+        d_dig = torch.from_numpy(dig).to(dev)
+        torch.cuda.synchronize(dev)
+        return self.retain_device(d_dig.data_ptr(), len(dig))
+
     def stats(self):
         s = _lib.cdc_store_stats_t()
         check(lib().cdc_store_stats(self._h, ctypes.byref(s)))
@@ -855,6 +876,22 @@ class FileSystem:
         buf = ctypes.create_string_buffer(need)
         assert check(lib().cdc_files_list(self._h, buf, need)) == need
         return [b.decode() for b in buf.raw[:need].split(b"\0")[:-1]]
+
+    def remove_file(self, name):
+        """cdc_files_remove: drop the file (host only; collect() reclaims the
+        space).  CdcError(CDC_ENOTFOUND) for an unknown name.  Handles to the
+        file raise CdcError(CDC_ENOTFOUND) from here on."""
+        check(lib().cdc_files_remove(self._h, name.encode()))
+
+    def collect(self, stream=None):
+        """cdc_files_collect: keep exactly the containers some file of this
+        layer references, compact the arena in place and rewrite every file's
+        table.  Returns cdc_collect_stats_t as a dict: containers_before /
+        _after, arena_used_before / _after, bytes_moved, groups_direct,
+        groups_bounced, seconds."""
+        s = _lib.cdc_collect_stats_t()
+        check(lib().cdc_files_collect(self._h, ctypes.byref(s), _ptr(stream)))
+        return {f: getattr(s, f) for f, _ in _lib.cdc_collect_stats_t._fields_}
 
     def stat(self, handle):
         s = _lib.cdc_file_stat_t()

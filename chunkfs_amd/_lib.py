@@ -41,12 +41,14 @@ EXPORTS = [
     "cdc_files_pread_batch_device", "cdc_file_hashes_device", "cdc_file_distribution_device",
     "cdc_files_write_batch_device",
     "cdc_files_get_to_dedup_ratio", "cdc_file_verify_device", "cdc_store_size_distribution_device",
+    "cdc_files_remove", "cdc_files_collect", "cdc_store_retain_device",
     "cdc_fill_splitmix64_device", "cdc_version", "cdc_abi_version",
 ]
 # include/chunkfs_amd_debug.h (diagnostics, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["cdc_debug_pipeline", "cdc_debug_record_cap", "cdc_debug_copy", "cdc_debug_host_stats",
                  "cdc_debug_read_bw", "cdc_debug_host_placement",
-                 "cdc_debug_timing_back", "cdc_debug_walk_params", "cdc_debug_files_table_blocks"]
+                 "cdc_debug_timing_back", "cdc_debug_walk_params", "cdc_debug_files_table_blocks",
+                 "cdc_debug_collect_split"]
 
 
 class CdcError(RuntimeError):
@@ -95,6 +97,13 @@ class cdc_pread_t(ctypes.Structure):
 
 class cdc_fwrite_t(ctypes.Structure):
     _fields_ = [("fh", ctypes.c_void_p), ("d_data", ctypes.c_void_p), ("len", ctypes.c_uint64)]
+
+
+class cdc_collect_stats_t(ctypes.Structure):
+    _fields_ = [("containers_before", ctypes.c_uint64), ("containers_after", ctypes.c_uint64),
+                ("arena_used_before", ctypes.c_uint64), ("arena_used_after", ctypes.c_uint64),
+                ("bytes_moved", ctypes.c_uint64), ("groups_direct", ctypes.c_uint64),
+                ("groups_bounced", ctypes.c_uint64), ("seconds", ctypes.c_double)]
 
 
 class cdc_timing_t(ctypes.Structure):
@@ -276,6 +285,12 @@ def lib():
     L.cdc_file_verify_device.restype = ctypes.c_int64
     L.cdc_store_size_distribution_device.argtypes = [P, ctypes.c_uint64, P, P, sz, P]
     L.cdc_store_size_distribution_device.restype = ctypes.c_int64
+    L.cdc_files_remove.argtypes = [P, ctypes.c_char_p]
+    L.cdc_files_remove.restype = ctypes.c_int
+    L.cdc_files_collect.argtypes = [P, ctypes.POINTER(cdc_collect_stats_t), P]
+    L.cdc_files_collect.restype = ctypes.c_int
+    L.cdc_store_retain_device.argtypes = [P, P, sz, P]
+    L.cdc_store_retain_device.restype = ctypes.c_int64
     L.cdc_fill_splitmix64_device.argtypes = [P, sz, ctypes.c_uint64, P]
     L.cdc_fill_splitmix64_device.restype = ctypes.c_int
     L.cdc_debug_pipeline.argtypes = [P]
@@ -290,6 +305,8 @@ def lib():
     L.cdc_debug_copy.restype = ctypes.c_int64
     L.cdc_debug_files_table_blocks.argtypes = [P]
     L.cdc_debug_files_table_blocks.restype = ctypes.c_int64
+    L.cdc_debug_collect_split.argtypes = [ctypes.POINTER(ctypes.c_double), sz]
+    L.cdc_debug_collect_split.restype = ctypes.c_int
     L.cdc_version.argtypes = []
     L.cdc_version.restype = ctypes.c_char_p
     L.cdc_abi_version.argtypes = []

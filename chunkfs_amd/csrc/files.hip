@@ -11,9 +11,9 @@
 // Layout: one span table per file, structure of arrays in HBM: the n + 1 byte
 // offsets (off[i + 1] - off[i] is span i's length; every search runs over
 // them), the 32-byte digests, and per span the table slot and arena offset the
-// store resolved when the span was written.  A put never moves stored bytes
-// and the store has no removal, so a read goes from span to bytes with no
-// digest lookup.
+// store resolved when the span was written.  A put never moves stored bytes,
+// and a collect (the one call that does) rewrites both in every table, so a
+// read goes from span to bytes with no digest lookup.
 //
 // Every read form is the same four steps with no host wait between them: one
 // thread per request resolves its span range by binary search in the offsets;
@@ -533,7 +533,76 @@ __global__ __launch_bounds__(kFlThreads) void ratio_write_kernel(SpanTable src, 
     to[1] = from[1];
 }
 
+// ---- collect (cdc_files_collect) --------------------------------------------------
+// The m spans of all the layer's files in one launch, segmented as the batch
+// append is: span i belongs to file f = file_of_span(first, nfiles, i).
+// refs[slot] += 1 per span.  A wave first combines: for up to kRefRounds
+// leaders, the lanes that name the leader's slot retire with one atomic of their
+// count (a file that repeats one chunk would otherwise serialise on one
+// address); what is left after that -- a wave of mostly distinct slots -- adds
+// for itself.
+constexpr int kRefRounds = 4;
+
+__global__ __launch_bounds__(kFlThreads) void collect_refs_kernel(const CollectSeg *__restrict__ seg,
+                                                                  const uint64_t *__restrict__ first, uint64_t nfiles,
+                                                                  uint64_t m, uint64_t slots,
+                                                                  unsigned long long *refs) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool todo = false;
+    uint32_t s = kNoSlot;
+    if (i < m) {
+        const uint64_t f = file_of_span(first, nfiles, i);
+        s = seg[f].slot[i - first[f]];
+        todo = s < slots;  // 0xFFFFFFFF: a span without a slot
+    }
+    const uint32_t lane = threadIdx.x & 63;
+    unsigned long long left = __ballot(todo);
+    for (int round = 0; round < kRefRounds && left; ++round) {  // wave-uniform
+        const uint32_t leader = (uint32_t)__builtin_ctzll(left);
+        const uint32_t lead_slot = __shfl(s, (int)leader);
+        const bool mine = todo && s == lead_slot;
+        const unsigned long long same = __ballot(mine);
+        if (lane == leader) atomicAdd(&refs[lead_slot], (unsigned long long)__popcll(same));
+        if (mine) todo = false;
+        left &= ~same;
+    }
+    if (todo) atomicAdd(&refs[s], 1ull);
+}
+
+// After the store's collect: every span's slot through map (old slot -> new
+// slot) and its arena offset from the new table.
+__global__ __launch_bounds__(kFlThreads) void collect_remap_kernel(const CollectSeg *__restrict__ seg,
+                                                                   const uint64_t *__restrict__ first, uint64_t nfiles,
+                                                                   uint64_t m, uint64_t slots,
+                                                                   const uint32_t *__restrict__ map,
+                                                                   const uint64_t *__restrict__ new_loc) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint64_t f = file_of_span(first, nfiles, i), j = i - first[f];
+    const CollectSeg sg = seg[f];
+    const uint32_t s = sg.slot[j];
+    if (s >= slots) return;
+    const uint32_t ns = map[s];  // referenced, so it survived
+    if (ns == kNoSlot) return;
+    sg.slot[j] = ns;
+    sg.loc[j] = new_loc[ns];
+}
+
 }  // namespace
+
+hipError_t launch_files_refs(const CollectSeg *d_seg, const uint64_t *d_first, uint64_t nfiles, uint64_t m,
+                             uint64_t slots, unsigned long long *refs, hipStream_t s) {
+    if (!m) return hipSuccess;
+    collect_refs_kernel<<<grid_of(m), kFlThreads, 0, s>>>(d_seg, d_first, nfiles, m, slots, refs);
+    return hipGetLastError();
+}
+
+hipError_t launch_files_remap(const CollectSeg *d_seg, const uint64_t *d_first, uint64_t nfiles, uint64_t m,
+                              uint64_t slots, const uint32_t *map, const uint64_t *new_loc, hipStream_t s) {
+    if (!m) return hipSuccess;
+    collect_remap_kernel<<<grid_of(m), kFlThreads, 0, s>>>(d_seg, d_first, nfiles, m, slots, map, new_loc);
+    return hipGetLastError();
+}
 
 hipError_t launch_files_ratio_unique(const SpanTable &t, uint64_t m, uint32_t *cnt, uint64_t *firstpos, uint64_t *val,
                                      uint64_t *block_sums, uint64_t *uidx, uint64_t *ulen, uint64_t *ublock,

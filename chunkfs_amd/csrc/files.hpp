@@ -144,6 +144,22 @@ hipError_t launch_files_distribution(const SpanTable &t, uint64_t m, uint32_t *c
                                      uint64_t *d_lengths, uint64_t cap, unsigned long long *h_distinct,
                                      hipStream_t s);
 
+// ---- collect (cdc_files_collect) ----------------------------------------------------
+// One file of the layer: the slot and arena-offset arrays of its span table.
+struct CollectSeg {
+    uint32_t *slot;
+    uint64_t *loc;
+};
+// The reference pass: all m = first[nfiles] spans of the layer's files in one
+// launch, file f owning spans [first[f], first[f + 1]) (d_seg: nfiles entries,
+// d_first: nfiles + 1, both DEVICE).  refs[slot] += 1 per span (refs: `slots`
+// u64, zeroed by the caller), combined within the wave before the atomics.
+hipError_t launch_files_refs(const CollectSeg *d_seg, const uint64_t *d_first, uint64_t nfiles, uint64_t m,
+                             uint64_t slots, unsigned long long *refs, hipStream_t s);
+// After store_retain: slot[i] = map[slot[i]], loc[i] = new_loc[slot[i]] for every span.
+hipError_t launch_files_remap(const CollectSeg *d_seg, const uint64_t *d_first, uint64_t nfiles, uint64_t m,
+                              uint64_t slots, const uint32_t *map, const uint64_t *new_loc, hipStream_t s);
+
 // ---- get_to_dedup_ratio (file_layer.rs:208-268) -----------------------------------
 // Step 1: the unique list over spans [0, m), m = n - 1, from the distribution's
 // first-occurrence flags and scan: uidx[j] = span index of the j-th distinct

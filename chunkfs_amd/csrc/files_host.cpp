@@ -575,6 +575,62 @@ int cdc_files_clear(cdc_files_t *fs) {
     return cdc_store_clear(fs->store);
 }
 
+int cdc_files_remove(cdc_files_t *fs, const char *name) {
+    if (!fs || !name) return fail(CDC_EINVAL, "cdc_files_remove: NULL argument");
+    auto it = fs->files.find(name);
+    if (it == fs->files.end()) return fail(CDC_ENOTFOUND, std::string("file layer: no file named '") + name + "'");
+    free_table(fs, it->second);
+    delete it->second;
+    fs->files.erase(it);  // handles hold the name: lookup() answers them with CDC_ENOTFOUND from here on
+    return CDC_OK;
+}
+
+int cdc_files_collect(cdc_files_t *fs, cdc_collect_stats_t *out, void *hip_stream) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!fs) return fail(CDC_EINVAL, "NULL file layer");
+    cdc::StoreView v = cdc::store_view(fs->store);
+    FL_TRY(hipSetDevice(v.device));
+    hipStream_t s = stream_of(fs, hip_stream);
+    // The roots: every file whose spans were resolved under the store's present
+    // epoch.  A file from before a clear names slots of another table.
+    std::vector<FileRec *> roots;
+    std::vector<cdc::CollectSeg> segs;
+    std::vector<uint64_t> first{0};
+    for (auto &kv : fs->files) {
+        FileRec *f = kv.second;
+        if (!f->n || f->epoch != v.epoch) continue;
+        roots.push_back(f);
+        segs.push_back(cdc::CollectSeg{f->t.slot, f->t.loc});
+        first.push_back(first.back() + f->n);
+    }
+    const uint64_t nf = roots.size(), m = first.back();
+    cdc::DeviceScratch mem;
+    cdc::CollectSeg *d_seg = nullptr;
+    uint64_t *d_first = nullptr;
+    unsigned long long *refs = nullptr;
+    uint32_t *map = nullptr;
+    FL_TRY(mem.alloc(&d_seg, nf));
+    FL_TRY(mem.alloc(&d_first, nf + 1));
+    FL_TRY(mem.alloc(&refs, v.slots));
+    FL_TRY(mem.alloc(&map, v.slots));
+    FL_TRY(hipMemsetAsync(refs, 0, v.slots * 8, s));
+    if (nf) FL_TRY(hipMemcpyAsync(d_seg, segs.data(), nf * sizeof(cdc::CollectSeg), hipMemcpyHostToDevice, s));
+    FL_TRY(hipMemcpyAsync(d_first, first.data(), (nf + 1) * 8, hipMemcpyHostToDevice, s));
+    FL_TRY(cdc::launch_files_refs(d_seg, d_first, nf, m, v.slots, refs, s));
+    cdc_collect_stats_t r{};
+    const int rc = cdc::store_retain(fs->store, refs, map, &r, s);  // waits for the stream
+    if (rc) return rc;  // refused: no table was touched
+    const auto t1 = std::chrono::steady_clock::now();
+    v = cdc::store_view(fs->store);
+    FL_TRY(cdc::launch_files_remap(d_seg, d_first, nf, m, v.slots, map, v.loc, s));
+    FL_TRY(hipStreamSynchronize(s));
+    for (FileRec *f : roots) f->epoch = v.epoch;
+    cdc::collect_split()[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (out) *out = r;
+    return CDC_OK;
+}
+
 int cdc_files_exists(const cdc_files_t *fs, const char *name) {
     if (!fs || !name) return fail(CDC_EINVAL, "cdc_files_exists: NULL argument");
     return fs->files.count(name) ? 1 : 0;

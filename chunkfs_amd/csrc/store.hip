@@ -37,6 +37,16 @@
 // runs the copy's piece list through compare_kernel -- the same tiles and loads,
 // a comparison in place of the store -- and the size distribution is a
 // max-reduce, a wave-aggregated histogram and a compaction over the slots.
+//
+// Retain / collect (not in the reference; DESIGN.md "Removal and collection"):
+// from per-slot reference counts the survivors are listed, ordered by arena
+// offset (rocPRIM's radix sort, bookkeeping only) and given new offsets by a
+// scan of their padded lengths; one thread plans move groups over those scans;
+// the bytes slide down in place through the copy kernel, a group either straight
+// to its new place or through a bounce buffer; the survivors are inserted into
+// a second, zeroed table with the unchanged index insert.
+#include <rocprim/device/device_radix_sort.hpp>
+
 #include "store.hpp"
 
 namespace cdc {
@@ -653,6 +663,232 @@ __global__ __launch_bounds__(kStThreads) void keys_kernel(IndexTable t, ScrubVie
     }
 }
 
+// ---- retain / collect --------------------------------------------------------------
+// refs[slot] += 1 per digest found (lookup_kernel's probe); res[0] += digests absent.
+__global__ __launch_bounds__(kStThreads) void retain_refs_kernel(IndexTable t, const uint8_t *__restrict__ digests,
+                                                                 uint64_t n, unsigned long long *refs,
+                                                                 unsigned long long *res) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t missing = 0;
+    if (i < n) {
+        const uint8_t *d = digests + 32 * i;
+        const uint2 w = *reinterpret_cast<const uint2 *>(d);
+        const uint64_t key = (((uint64_t)w.y << 32) | w.x) | 1ull;  // index.hip key_of
+        const uint64_t mask = t.slots - 1;
+        uint64_t s = (key >> 1) & mask;
+        missing = 1;
+        for (uint64_t probe = 0; probe < t.slots; ++probe, s = (s + 1) & mask) {
+            const uint64_t cur = t.tag[s];
+            if (cur == 0) break;
+            if (cur == key && same_digest(t.digest + 32 * s, d)) {
+                atomicAdd(&refs[s], 1ull);
+                missing = 0;
+                break;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 1; k < 64; k <<= 1) missing += __shfl_xor(missing, k);
+    if ((threadIdx.x & 63) == 0 && missing) atomicAdd(&res[0], (unsigned long long)missing);
+}
+
+// val[s] = 1 for the containers that stay (occupied, refs > 0).  acc[0] += sum of
+// refs, acc[1] += sum of refs * length, acc[2] += the survivors' bytes, acc[3] =
+// their longest padded length: one atomic per wave each.
+__global__ __launch_bounds__(kStThreads) void retain_flag_kernel(IndexTable t,
+                                                                 const unsigned long long *__restrict__ refs,
+                                                                 uint64_t *val, unsigned long long *acc) {
+    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t r = 0, rb = 0, ub = 0, mx = 0;
+    if (s < t.slots) {
+        r = occupied(t, s) ? refs[s] : 0;
+        val[s] = r ? 1 : 0;
+        if (r) {
+            const uint64_t len = t.length[s];
+            rb = r * len;
+            ub = len;
+            mx = (len + (kStoreAlign - 1)) & ~(kStoreAlign - 1);
+        }
+    }
+#pragma unroll
+    for (int k = 1; k < 64; k <<= 1) {
+        r += __shfl_xor(r, k);
+        rb += __shfl_xor(rb, k);
+        ub += __shfl_xor(ub, k);
+        const uint64_t o = __shfl_xor(mx, k);
+        mx = o > mx ? o : mx;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (r) atomicAdd(&acc[0], (unsigned long long)r);
+        if (rb) atomicAdd(&acc[1], (unsigned long long)rb);
+        if (ub) atomicAdd(&acc[2], (unsigned long long)ub);
+        if (mx) atomicMax(&acc[3], (unsigned long long)mx);
+    }
+}
+
+// The survivors at their ranks (val = the scanned flags): the sort key is the
+// arena offset, a multiple of 16, with bit 0 set for a container that holds
+// bytes.  A length-0 container shares its offset with the container stored next
+// after it and must stay in front of it, or the gaps would not be monotonic.
+__global__ __launch_bounds__(kStThreads) void retain_list_kernel(IndexTable t, const uint64_t *__restrict__ loc,
+                                                                 const unsigned long long *__restrict__ refs,
+                                                                 const uint64_t *__restrict__ val, uint64_t *key,
+                                                                 uint32_t *slot) {
+    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= t.slots || !occupied(t, s) || !refs[s]) return;
+    const uint64_t j = val[s];
+    key[j] = loc[s] | (t.length[s] ? 1ull : 0ull);
+    slot[j] = (uint32_t)s;
+}
+
+// In arena order: the padded length (scanned into the new offsets afterwards),
+// the digest and the {0, length} record the index insert takes.
+__global__ __launch_bounds__(kStThreads) void retain_gather_kernel(IndexTable t, const uint32_t *__restrict__ slot,
+                                                                   uint64_t m, uint64_t *pad, uint8_t *digests,
+                                                                   cdc_chunk_pod *chunks) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t s = slot[i];
+    const uint64_t len = t.length[s];
+    pad[i] = (len + (kStoreAlign - 1)) & ~(kStoreAlign - 1);
+    chunks[i] = cdc_chunk_pod{0, len};
+    const uint4 *src = reinterpret_cast<const uint4 *>(t.digest + 32ull * s);
+    uint4 *dst = reinterpret_cast<uint4 *>(digests + 32 * i);
+    dst[0] = src[0];
+    dst[1] = src[1];
+}
+
+// Largest b in [a, m] with newloc[b] - newloc[a] <= limit (newloc has m + 1 entries).
+__device__ __forceinline__ uint64_t retain_reach(const uint64_t *__restrict__ newloc, uint64_t a, uint64_t m,
+                                                 uint64_t limit) {
+    uint64_t lo = a, hi = m;
+    const uint64_t base = newloc[a];
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi + 1) >> 1;
+        if (newloc[mid] - base <= limit) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// One thread plans the move groups (tests/gc_model.py plan_groups is the same
+// rule in Python).  gap[i] = old offset - new offset never decreases along the
+// survivors; the leading run with gap 0 stays where it is.  From the first moved
+// survivor a on: the direct group [a, bd) is the longest whose bytes fit into
+// gap[a], the bounced group [a, bb) the longest whose bytes fit into W.  The
+// direct one is taken when it moves at least half of what the bounced one would
+// (a bounced byte is copied twice) or reaches the end.  W = max(max_pad,
+// min(w_req, bytes to move)) rounded up to 16: at least every padded length, so
+// bb > a and the loop advances.  out: [0] groups, [1] direct, [2] bounced, [3]
+// bytes moved, [4] groups that did not fit `cap`, [5] W, [6] new offset of the
+// first moved byte, [7] newloc[m].
+__global__ void retain_plan_kernel(const uint64_t *__restrict__ key, const uint64_t *__restrict__ newloc, uint64_t m,
+                                   uint64_t w_req, uint64_t max_pad, RetainGroup *groups, uint64_t cap,
+                                   unsigned long long *out) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    uint64_t lo = 0, hi = m;  // first survivor with gap > 0
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if ((key[mid] & ~(kStoreAlign - 1)) > newloc[mid]) hi = mid;
+        else lo = mid + 1;
+    }
+    uint64_t ng = 0, nd = 0, nb = 0, over = 0;
+    const uint64_t first = lo, moved = first < m ? newloc[m] - newloc[first] : 0;
+    uint64_t W = w_req < moved ? w_req : moved;
+    W = (W + (kStoreAlign - 1)) & ~(kStoreAlign - 1);
+    W = W < max_pad ? max_pad : W;
+    for (uint64_t a = first; a < m;) {
+        const uint64_t gap = (key[a] & ~(kStoreAlign - 1)) - newloc[a];
+        const uint64_t bd = retain_reach(newloc, a, m, gap), bb = retain_reach(newloc, a, m, W);
+        const uint64_t direct_bytes = newloc[bd] - newloc[a], bounced_bytes = newloc[bb] - newloc[a];
+        const bool direct = bd == m || 2 * direct_bytes >= bounced_bytes;
+        const uint64_t b = direct ? bd : bb;
+        if (b <= a) {  // cannot happen while W >= the longest padded length: stop instead of spinning
+            over = ~0ull;
+            break;
+        }
+        if (ng < cap) groups[ng] = RetainGroup{a, b, direct ? direct_bytes : bounced_bytes, direct ? 1ull : 0ull};
+        else ++over;
+        ++ng;
+        if (direct) ++nd;
+        else ++nb;
+        a = b;
+    }
+    out[0] = ng;
+    out[1] = nd;
+    out[2] = nb;
+    out[3] = moved;
+    out[4] = over;
+    out[5] = W;
+    out[6] = first < m ? newloc[first] : newloc[m];
+    out[7] = newloc[m];
+}
+
+// The group of survivor i (groups are consecutive ranges from groups[0].a on);
+// ng when it lies in the leading run that does not move.
+__device__ __forceinline__ uint64_t retain_group_of(const RetainGroup *__restrict__ groups, uint64_t ng, uint64_t i) {
+    if (ng == 0 || i < groups[0].a) return ng;
+    uint64_t a = 0, b = ng;
+    while (b - a > 1) {
+        const uint64_t mid = (a + b) >> 1;
+        if (groups[mid].a <= i) a = mid;
+        else b = mid;
+    }
+    return a;
+}
+
+// One piece per survivor, padded length (both ends are 16-byte multiples inside
+// the arena): to its new offset for a direct group, into the bounce buffer at
+// its distance from the group's first byte for a bounced one.
+__global__ __launch_bounds__(kStThreads) void retain_pieces_kernel(const uint64_t *__restrict__ key,
+                                                                   const uint64_t *__restrict__ newloc, uint64_t m,
+                                                                   const RetainGroup *__restrict__ groups, uint64_t ng,
+                                                                   uint64_t arena, uint64_t bounce, StorePiece *pieces,
+                                                                   uint64_t *tiles) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint64_t g = retain_group_of(groups, ng, i);
+    StorePiece p{0, 0, 0};
+    if (g < ng) {
+        p.src = arena + (key[i] & ~(kStoreAlign - 1));
+        p.len = newloc[i + 1] - newloc[i];
+        p.dst = groups[g].direct ? arena + newloc[i] : bounce + (newloc[i] - newloc[groups[g].a]);
+    }
+    pieces[i] = p;
+    tiles[i] = (p.len + (kStoreTile - 1)) / kStoreTile;
+}
+
+// tstart = the scan of the tile counts over all survivors (m + 1 entries); the
+// copy wants each group's scan to start at 0.  Threads [m, m + ng): the group's
+// tile count, which the copy reads on the device.
+__global__ __launch_bounds__(kStThreads) void retain_rel_kernel(const uint64_t *__restrict__ tstart, uint64_t m,
+                                                                const RetainGroup *__restrict__ groups, uint64_t ng,
+                                                                uint64_t *trel, uint64_t *gtiles) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m + ng) return;
+    if (i >= m) {
+        const RetainGroup g = groups[i - m];
+        gtiles[i - m] = tstart[g.b] - tstart[g.a];
+        return;
+    }
+    const uint64_t g = retain_group_of(groups, ng, i);
+    trel[i] = g < ng ? tstart[i] - tstart[groups[g].a] : 0;
+}
+
+// After the insert into the new table: old slot -> new slot (map, preset to
+// 0xFFFFFFFF) and the new table's loc entry.
+__global__ __launch_bounds__(kStThreads) void retain_scatter_kernel(const uint32_t *__restrict__ old_slot,
+                                                                    const uint32_t *__restrict__ new_slot,
+                                                                    const uint64_t *__restrict__ newloc, uint64_t m,
+                                                                    uint64_t *new_loc, uint32_t *map) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t ns = new_slot[i];
+    if (ns == kNoSlot) return;  // the host refuses the call on the insert's counters
+    map[old_slot[i]] = ns;
+    new_loc[ns] = newloc[i];
+}
+
 constexpr uint64_t kMaxCopyBlocks = 1u << 20;  // waves past this stride over the tiles
 
 inline unsigned grid_of(uint64_t n) { return (unsigned)((n + kStThreads - 1) / kStThreads); }
@@ -829,6 +1065,68 @@ hipError_t launch_store_key_counts(const IndexTable &t, const ScrubView &v, uint
 hipError_t launch_store_keys(const IndexTable &t, const ScrubView &v, const uint64_t *val, uint8_t *d_keys,
                              hipStream_t s) {
     keys_kernel<<<grid_of(t.slots), kStThreads, 0, s>>>(t, v, val, d_keys);
+    return hipGetLastError();
+}
+
+hipError_t launch_retain_refs(const IndexTable &t, const uint8_t *d_digests, uint64_t n, unsigned long long *refs,
+                              unsigned long long *d_res, hipStream_t s) {
+    if (!n) return hipSuccess;
+    retain_refs_kernel<<<grid_of(n), kStThreads, 0, s>>>(t, d_digests, n, refs, d_res);
+    return hipGetLastError();
+}
+
+hipError_t launch_retain_flag(const IndexTable &t, const unsigned long long *refs, uint64_t *val,
+                              uint64_t *block_sums, unsigned long long *d_acc, unsigned long long *d_total,
+                              hipStream_t s) {
+    retain_flag_kernel<<<grid_of(t.slots), kStThreads, 0, s>>>(t, refs, val, d_acc);
+    scan_exclusive(val, t.slots, block_sums, d_total, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_retain_list(const IndexTable &t, const uint64_t *loc, const unsigned long long *refs,
+                              const uint64_t *val, uint64_t *key, uint32_t *slot, hipStream_t s) {
+    retain_list_kernel<<<grid_of(t.slots), kStThreads, 0, s>>>(t, loc, refs, val, key, slot);
+    return hipGetLastError();
+}
+
+hipError_t launch_retain_sort(void *temp, size_t *temp_bytes, const uint64_t *key_in, uint64_t *key_out,
+                              const uint32_t *slot_in, uint32_t *slot_out, uint64_t m, unsigned end_bit,
+                              hipStream_t s) {
+    return rocprim::radix_sort_pairs(temp, *temp_bytes, key_in, key_out, slot_in, slot_out, (size_t)m, 0u, end_bit, s);
+}
+
+hipError_t launch_retain_layout(const IndexTable &t, const uint32_t *slot, uint64_t m, uint64_t *newloc,
+                                uint64_t *block_sums, uint8_t *d_digests, void *d_chunks, hipStream_t s) {
+    if (!m) return hipSuccess;
+    retain_gather_kernel<<<grid_of(m), kStThreads, 0, s>>>(t, slot, m, newloc, d_digests,
+                                                           reinterpret_cast<cdc_chunk_pod *>(d_chunks));
+    scan_exclusive(newloc, m, block_sums, reinterpret_cast<unsigned long long *>(newloc + m), s);
+    return hipGetLastError();
+}
+
+hipError_t launch_retain_plan(const uint64_t *key, const uint64_t *newloc, uint64_t m, uint64_t w_req,
+                              uint64_t max_pad, RetainGroup *groups, uint64_t cap, unsigned long long *d_out,
+                              hipStream_t s) {
+    retain_plan_kernel<<<1, 64, 0, s>>>(key, newloc, m, w_req, max_pad, groups, cap, d_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_retain_pieces(const uint64_t *key, const uint64_t *newloc, uint64_t m, const RetainGroup *groups,
+                                uint64_t ng, const uint8_t *arena, const uint8_t *bounce, StorePiece *pieces,
+                                uint64_t *tstart, uint64_t *block_sums, uint64_t *trel, uint64_t *gtiles,
+                                hipStream_t s) {
+    if (!m || !ng) return hipSuccess;
+    retain_pieces_kernel<<<grid_of(m), kStThreads, 0, s>>>(key, newloc, m, groups, ng, (uint64_t)(uintptr_t)arena,
+                                                           (uint64_t)(uintptr_t)bounce, pieces, tstart);
+    scan_exclusive(tstart, m, block_sums, reinterpret_cast<unsigned long long *>(tstart + m), s);
+    retain_rel_kernel<<<grid_of(m + ng), kStThreads, 0, s>>>(tstart, m, groups, ng, trel, gtiles);
+    return hipGetLastError();
+}
+
+hipError_t launch_retain_scatter(const uint32_t *old_slot, const uint32_t *new_slot, const uint64_t *newloc,
+                                 uint64_t m, uint64_t *new_loc, uint32_t *map, hipStream_t s) {
+    if (!m) return hipSuccess;
+    retain_scatter_kernel<<<grid_of(m), kStThreads, 0, s>>>(old_slot, new_slot, newloc, m, new_loc, map);
     return hipGetLastError();
 }
 

@@ -174,4 +174,65 @@ hipError_t launch_store_key_counts(const IndexTable &t, const ScrubView &v, uint
 hipError_t launch_store_keys(const IndexTable &t, const ScrubView &v, const uint64_t *val, uint8_t *d_keys,
                              hipStream_t s);
 
+// ---- retain / collect ------------------------------------------------------------
+// Keep the containers with refs[slot] > 0, drop the rest, slide the survivors
+// down the arena in place (store_host.cpp store_retain; DESIGN.md "Removal and
+// collection").  Survivors are numbered 0 .. m-1 in arena order.
+
+// One move group: survivors [a, b), `bytes` padded bytes; direct = 1: copied
+// arena -> arena in one launch, 0: gathered into the bounce buffer and written
+// back with one device copy.
+struct RetainGroup {
+    uint64_t a, b, bytes, direct;
+};
+
+// refs[slot] += 1 for each of the n digests found (refs: slots u64, zeroed by
+// the caller); d_res[0] += digests absent.
+hipError_t launch_retain_refs(const IndexTable &t, const uint8_t *d_digests, uint64_t n, unsigned long long *refs,
+                              unsigned long long *d_res, hipStream_t s);
+
+// val[s] = 1 for the occupied slots with refs > 0, scanned in place (*d_total =
+// m).  d_acc (zeroed): [0] sum of refs, [1] sum of refs * length, [2] bytes of
+// the survivors, [3] their longest padded length.
+hipError_t launch_retain_flag(const IndexTable &t, const unsigned long long *refs, uint64_t *val,
+                              uint64_t *block_sums, unsigned long long *d_acc, unsigned long long *d_total,
+                              hipStream_t s);
+
+// The survivors in slot order: key[j] = arena offset | (length > 0), slot[j].
+hipError_t launch_retain_list(const IndexTable &t, const uint64_t *loc, const unsigned long long *refs,
+                              const uint64_t *val, uint64_t *key, uint32_t *slot, hipStream_t s);
+
+// rocPRIM's stable radix sort of the pairs over key bits [0, end_bit).  temp ==
+// NULL: *temp_bytes receives the scratch size and nothing runs.
+hipError_t launch_retain_sort(void *temp, size_t *temp_bytes, const uint64_t *key_in, uint64_t *key_out,
+                              const uint32_t *slot_in, uint32_t *slot_out, uint64_t m, unsigned end_bit,
+                              hipStream_t s);
+
+// In sorted order: newloc[0 .. m] = exclusive scan of round_up(length, 16)
+// (newloc[m] = the arena bytes in use afterwards), the digests and {0, length}
+// records the index insert takes.  block_sums: store_scan_blocks(m) + 1.
+hipError_t launch_retain_layout(const IndexTable &t, const uint32_t *slot, uint64_t m, uint64_t *newloc,
+                                uint64_t *block_sums, uint8_t *d_digests, void *d_chunks, hipStream_t s);
+
+// The move groups, planned by one thread with binary searches over newloc.  The
+// bounce buffer is W = max(max_pad, min(w_req, bytes to move)) bytes, max_pad
+// being the longest padded length.  d_out: [0] groups, [1] direct, [2] bounced,
+// [3] bytes moved, [4] != 0: the plan did not fit cap, [5] W, [6] the new offset
+// of the first moved byte, [7] newloc[m].
+hipError_t launch_retain_plan(const uint64_t *key, const uint64_t *newloc, uint64_t m, uint64_t w_req,
+                              uint64_t max_pad, RetainGroup *groups, uint64_t cap, unsigned long long *d_out,
+                              hipStream_t s);
+
+// The piece list of all groups and, per group, a tile scan from 0: group g is
+// moved by launch_store_copy(pieces + a, trel + a, b - a, ..., gtiles + g).
+// tstart: m + 1; trel: m; gtiles: ng; block_sums: store_scan_blocks(m) + 1.
+hipError_t launch_retain_pieces(const uint64_t *key, const uint64_t *newloc, uint64_t m, const RetainGroup *groups,
+                                uint64_t ng, const uint8_t *arena, const uint8_t *bounce, StorePiece *pieces,
+                                uint64_t *tstart, uint64_t *block_sums, uint64_t *trel, uint64_t *gtiles,
+                                hipStream_t s);
+
+// map[old slot] = new slot (map preset to 0xFF bytes), new_loc[new slot] = newloc.
+hipError_t launch_retain_scatter(const uint32_t *old_slot, const uint32_t *new_slot, const uint64_t *newloc,
+                                 uint64_t m, uint64_t *new_loc, uint32_t *map, hipStream_t s);
+
 }  // namespace cdc

@@ -5,6 +5,7 @@
 // stage ("Scrub stage"): the target map as a second store, the Scrub hook
 // (src/system/scrub.rs), DataContainer kinds with resolved key runs
 // (storage.rs:12-21), new_with_scrubber / scrub / iterator (storage.rs:165-235).
+// Retain / collect ("Removal and collection") is this project's own.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "../../include/chunkfs_amd.h"
+#include "../../include/chunkfs_amd_debug.h"
 #include "engine.hpp"
 #include "index.hpp"
 #include "store.hpp"
@@ -586,9 +588,224 @@ int64_t get_expanded(cdc_store *st, const uint8_t *d_digests, size_t n, uint8_t 
     return (int64_t)res[1];
 }
 
+// ---- retain / collect ---------------------------------------------------------------
+// Bytes of the bounce buffer before it is clipped to the bytes to move and raised
+// to the longest container: CHUNKFS_AMD_GC_BOUNCE=bytes.
+uint64_t retain_bounce_request() {
+    if (const char *v = std::getenv("CHUNKFS_AMD_GC_BOUNCE")) {
+        char *end = nullptr;
+        const unsigned long long w = std::strtoull(v, &end, 10);
+        if (end != v) return w;
+    }
+    return 256ull << 20;
+}
+
+// An allocation that fails is a refusal (CDC_ENOMEM), not a device error.
+#define ST_ALLOC(expr)                                                                        \
+    do {                                                                                      \
+        hipError_t e_ = (expr);                                                               \
+        if (e_ != hipSuccess) {                                                               \
+            (void)hipGetLastError();                                                          \
+            cdc::set_error(std::string("chunk store collect: ") + #expr + ": " + hipGetErrorString(e_)); \
+            return e_ == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE;                      \
+        }                                                                                     \
+    } while (0)
+
+// The second set of table arrays the survivors are inserted into; freed unless adopted.
+struct NewTable {
+    cdc::IndexTable t{};
+    uint64_t *loc = nullptr;
+    ~NewTable() {
+        (void)hipFree(t.tag);
+        (void)hipFree(t.digest);
+        (void)hipFree(t.owner);
+        (void)hipFree(t.length);
+        (void)hipFree(loc);
+    }
+};
+
+int retain(cdc_store *st, const unsigned long long *d_refs, uint32_t *d_map, cdc_collect_stats_t *out,
+           hipStream_t s) {
+    const auto t0 = std::chrono::steady_clock::now();
+    auto last = t0;
+    double split[6] = {0, 0, 0, 0, 0, 0};  // cdc_debug_collect_split
+    auto lap = [&](int phase) {
+        const auto now = std::chrono::steady_clock::now();
+        split[phase] += std::chrono::duration<double, std::milli>(now - last).count();
+        last = now;
+    };
+    if (st->target_containers) {
+        cdc::set_error("chunk store collect: the store holds target-kind containers (scrubbed); not supported");
+        return CDC_ENOTSUP;
+    }
+    ST_TRY(hipSetDevice(st->device));
+    const uint64_t slots = st->t.slots;
+    cdc::DeviceScratch mem;
+
+    // 1. Which containers stay, how many, and the totals the stats are set from.
+    uint64_t *val = nullptr, *block = nullptr;
+    unsigned long long *acc = nullptr;  // [0..3] the flag pass, [4] m, [8..12] the insert, [16..23] the plan
+    ST_ALLOC(mem.alloc(&val, slots));
+    ST_ALLOC(mem.alloc(&block, cdc::store_scan_blocks(slots) + 1));
+    ST_ALLOC(mem.alloc(&acc, 24));
+    ST_TRY(hipMemsetAsync(acc, 0, 24 * 8, s));
+    ST_TRY(cdc::launch_retain_flag(st->t, d_refs, val, block, acc, acc + 4, s));
+    uint64_t h[5];  // sum of refs, sum of refs * length, survivors' bytes, longest padded length, m
+    ST_TRY(hipMemcpyAsync(h, acc, sizeof h, hipMemcpyDeviceToHost, s));
+    ST_TRY(hipStreamSynchronize(s));
+    const uint64_t m = h[4];
+    lap(0);
+    // Owners are renumbered 0 .. m-1 and the next put's base is chunks_written =
+    // the sum of refs: first insert wins across the collect only while base > every owner.
+    if (h[0] < m) {
+        cdc::set_error("chunk store collect: fewer references than surviving containers");
+        return CDC_EDEVICE;
+    }
+
+    // 2. Every allocation the call needs (the bounce buffer follows the plan,
+    // still before anything is written).
+    uint64_t *key_in = nullptr, *key = nullptr, *newloc = nullptr, *nblock = nullptr, *tstart = nullptr,
+             *trel = nullptr, *gtiles = nullptr;
+    uint32_t *slot_in = nullptr, *slot = nullptr, *new_slot = nullptr, *pending = nullptr, *map = d_map;
+    uint8_t *dig = nullptr, *sort_tmp = nullptr, *bounce = nullptr;
+    cdc_chunk_t *recs = nullptr;
+    cdc::RetainGroup *groups = nullptr;
+    cdc::StorePiece *pieces = nullptr;
+    size_t sort_bytes = 0;
+    unsigned end_bit = 1;
+    while (end_bit < 64 && (st->arena_capacity >> end_bit)) ++end_bit;
+    ST_ALLOC(mem.alloc(&key_in, m));
+    ST_ALLOC(mem.alloc(&key, m));
+    ST_ALLOC(mem.alloc(&slot_in, m));
+    ST_ALLOC(mem.alloc(&slot, m));
+    ST_ALLOC(mem.alloc(&newloc, m + 1));
+    ST_ALLOC(mem.alloc(&nblock, cdc::store_scan_blocks(m) + 1));
+    ST_ALLOC(mem.alloc(&dig, m * 32));
+    ST_ALLOC(mem.alloc(&recs, m));
+    ST_ALLOC(mem.alloc(&new_slot, m));
+    ST_ALLOC(mem.alloc(&pending, cdc::kIndexPendingCap));
+    ST_ALLOC(mem.alloc(&groups, m));
+    ST_ALLOC(mem.alloc(&pieces, m));
+    ST_ALLOC(mem.alloc(&tstart, m + 1));
+    ST_ALLOC(mem.alloc(&trel, m));
+    ST_ALLOC(mem.alloc(&gtiles, m));
+    if (!map) ST_ALLOC(mem.alloc(&map, slots));  // the scatter writes one either way
+    if (m) {
+        ST_ALLOC(cdc::launch_retain_sort(nullptr, &sort_bytes, key_in, key, slot_in, slot, m, end_bit, s));
+        ST_ALLOC(mem.alloc(&sort_tmp, sort_bytes));
+    }
+    NewTable nt;
+    nt.t.slots = slots;
+    ST_ALLOC(hipMalloc(&nt.t.tag, slots * 8));
+    ST_ALLOC(hipMalloc(&nt.t.digest, slots * 32));
+    ST_ALLOC(hipMalloc(&nt.t.owner, slots * 8));
+    ST_ALLOC(hipMalloc(&nt.t.length, slots * 8));
+    ST_ALLOC(hipMalloc(&nt.loc, slots * 8));
+    lap(1);
+
+    // 3. The survivors in arena order, their new offsets, the move groups.
+    // groups, direct, bounced, bytes moved, overflow, W, new offset of the first moved byte, arena bytes afterwards
+    uint64_t plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<cdc::RetainGroup> h_groups;
+    if (m) {
+        ST_TRY(cdc::launch_retain_list(st->t, st->loc, d_refs, val, key_in, slot_in, s));
+        ST_TRY(cdc::launch_retain_sort(sort_tmp, &sort_bytes, key_in, key, slot_in, slot, m, end_bit, s));
+        ST_TRY(cdc::launch_retain_layout(st->t, slot, m, newloc, nblock, dig, recs, s));
+        ST_TRY(cdc::launch_retain_plan(key, newloc, m, retain_bounce_request(), h[3], groups, m, acc + 16, s));
+        ST_TRY(hipMemcpyAsync(plan, acc + 16, sizeof plan, hipMemcpyDeviceToHost, s));
+        ST_TRY(hipStreamSynchronize(s));
+        if (plan[4]) {
+            cdc::set_error("chunk store collect: the move plan did not close");
+            return CDC_EDEVICE;
+        }
+        h_groups.resize(plan[0]);
+        if (plan[0]) {
+            ST_TRY(hipMemcpyAsync(h_groups.data(), groups, plan[0] * sizeof(cdc::RetainGroup), hipMemcpyDeviceToHost, s));
+            ST_TRY(hipStreamSynchronize(s));
+        }
+        lap(2);
+        if (plan[2]) ST_ALLOC(mem.alloc(&bounce, plan[5]));
+        lap(1);
+    }
+
+    // 4. The new table, beside the live one: a failure here is still a refusal.
+    ST_TRY(hipMemsetAsync(nt.t.tag, 0, slots * 8, s));
+    ST_TRY(hipMemsetAsync(nt.t.owner, 0xFF, slots * 8, s));
+    ST_TRY(hipMemsetAsync(map, 0xFF, slots * 4, s));
+    uint64_t ins[5] = {0, 0, 0, 0, 0};  // the insert's counters, on scratch: the totals come from the contract
+    if (m) {
+        ST_TRY(cdc::launch_index_insert(nt.t, dig, recs, m, 0, new_slot, pending, nullptr, acc + 8, s));
+        ST_TRY(cdc::launch_retain_scatter(slot, new_slot, newloc, m, nt.loc, map, s));
+        ST_TRY(hipMemcpyAsync(ins, acc + 8, sizeof ins, hipMemcpyDeviceToHost, s));
+        ST_TRY(hipStreamSynchronize(s));
+        // A subset of what the table held cannot fill it; a pile of 64-bit key
+        // collisions gathered over many puts could pass the one-batch cap.
+        if (ins[0] != m || ins[3] || ins[4] > cdc::kIndexPendingCap) {
+            cdc::set_error("chunk store collect: the survivors could not be inserted into the new table (" +
+                           std::to_string(ins[0]) + " of " + std::to_string(m) + " placed, " +
+                           std::to_string(ins[4]) + " 64-bit key collisions)");
+            return CDC_ENOMEM;
+        }
+    }
+    lap(3);
+
+    // 5. The move: from here on the arena changes.  Groups run in stream order.
+    if (!h_groups.empty()) {
+        ST_TRY(cdc::launch_retain_pieces(key, newloc, m, groups, h_groups.size(), st->arena, bounce, pieces, tstart,
+                                         nblock, trel, gtiles, s));
+        uint64_t at = plan[6];  // new offset of the group's first byte
+        for (size_t g = 0; g < h_groups.size(); ++g) {
+            const cdc::RetainGroup &gr = h_groups[g];
+            const uint64_t n = gr.b - gr.a;
+            ST_TRY(cdc::launch_store_copy(pieces + gr.a, trel + gr.a, n, gr.bytes / cdc::kStoreTile + n, gtiles + g, s));
+            if (!gr.direct && gr.bytes)
+                ST_TRY(hipMemcpyAsync(st->arena + at, bounce, gr.bytes, hipMemcpyDeviceToDevice, s));
+            at += gr.bytes;
+        }
+        ST_TRY(hipStreamSynchronize(s));
+    }
+    lap(4);
+
+    // 6. Adopt the new table.
+    const uint64_t new_used = plan[7];
+    std::swap(st->t.tag, nt.t.tag);
+    std::swap(st->t.digest, nt.t.digest);
+    std::swap(st->t.owner, nt.t.owner);
+    std::swap(st->t.length, nt.t.length);
+    std::swap(st->loc, nt.loc);
+    cdc_collect_stats_t r{};
+    r.containers_before = st->st.unique_chunks;
+    r.containers_after = m;
+    r.arena_used_before = st->arena_used;
+    r.arena_used_after = new_used;
+    r.bytes_moved = plan[3];
+    r.groups_direct = plan[1];
+    r.groups_bounced = plan[2];
+    st->st.chunks_written = h[0];
+    st->st.bytes_written = h[1];
+    st->st.unique_chunks = m;
+    st->st.unique_bytes = h[2];
+    st->arena_used = new_used;
+    ++st->epoch;
+    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    *out = r;
+    std::memcpy(cdc::collect_split(), split, sizeof split);
+    return CDC_OK;
+}
+
 }  // namespace
 
 namespace cdc {
+
+double *collect_split() {
+    static thread_local double split[6];
+    return split;
+}
+
+int store_retain(cdc_store *st, const unsigned long long *d_refs, uint32_t *d_map, cdc_collect_stats_t *out,
+                 hipStream_t s) {
+    return retain(st, d_refs, d_map, out, s);
+}
 
 bool store_scrub_view(const cdc_store *st, ScrubView *view, bool *stale) {
     if (!st->target || !st->target_containers) return false;
@@ -741,6 +958,49 @@ int64_t cdc_store_contains_device(cdc_store_t *st, const uint8_t *d_digests, siz
     ST_TRY(hipMemcpyAsync(&missing, res_d, 8, hipMemcpyDeviceToHost, s));
     ST_TRY(hipStreamSynchronize(s));
     return (int64_t)(n - missing);
+}
+
+int64_t cdc_store_retain_device(cdc_store_t *st, const uint8_t *d_digests, size_t n, void *hip_stream) {
+    if (!st) {
+        cdc::set_error("NULL store");
+        return CDC_EINVAL;
+    }
+    if (n && !d_digests) {
+        cdc::set_error("cdc_store_retain_device: NULL argument");
+        return CDC_EINVAL;
+    }
+    if (st->target_containers) {
+        cdc::set_error("chunk store collect: the store holds target-kind containers (scrubbed); not supported");
+        return CDC_ENOTSUP;
+    }
+    ST_TRY(hipSetDevice(st->device));
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : st->stream;
+    cdc::DeviceScratch mem;
+    unsigned long long *refs = nullptr, *res = nullptr;
+    ST_ALLOC(mem.alloc(&refs, st->t.slots));
+    ST_ALLOC(mem.alloc(&res, 1));
+    ST_TRY(hipMemsetAsync(refs, 0, st->t.slots * 8, s));
+    ST_TRY(hipMemsetAsync(res, 0, 8, s));
+    ST_TRY(cdc::launch_retain_refs(st->t, d_digests, n, refs, res, s));
+    uint64_t missing = 0;
+    ST_TRY(hipMemcpyAsync(&missing, res, 8, hipMemcpyDeviceToHost, s));
+    ST_TRY(hipStreamSynchronize(s));
+    if (missing) {
+        cdc::set_error("chunk store retain: " + std::to_string(missing) + " digest(s) not found");
+        return CDC_ENOTFOUND;
+    }
+    cdc_collect_stats_t r{};
+    const int rc = retain(st, refs, nullptr, &r, s);
+    return rc ? rc : (int64_t)r.containers_after;
+}
+
+int cdc_debug_collect_split(double *ms, size_t n) {
+    if (n && !ms) {
+        cdc::set_error("cdc_debug_collect_split: NULL argument");
+        return CDC_EINVAL;
+    }
+    if (n) std::memcpy(ms, cdc::collect_split(), (n < 6 ? n : 6) * sizeof(double));
+    return 6;
 }
 
 int cdc_store_set_target(cdc_store_t *base, cdc_store_t *target) { return set_target(base, target); }

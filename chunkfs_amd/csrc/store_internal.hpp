@@ -47,6 +47,22 @@ int64_t store_put_batch_slots(cdc_store *st, size_t n_streams, const uint8_t *co
 // must return CDC_ENOTFOUND.
 bool store_scrub_view(const cdc_store *st, ScrubView *view, bool *stale);
 
+// Retain by per-slot reference counts, the one primitive behind
+// cdc_files_collect and cdc_store_retain_device (the contract: chunkfs_amd.h
+// "Removal and collection").  d_refs: DEVICE u64[slots]; a container stays iff
+// its slot is occupied and refs > 0.  d_map (DEVICE u32[slots], nullable)
+// receives old slot -> new slot, 0xFFFFFFFF for a dropped or empty slot; the new
+// offsets are store_view().loc afterwards.  *out is always filled on success.
+// Every refusal and every allocation comes before the first write to the table
+// or the arena; a CDC_EDEVICE after that leaves the store fit only for clear or
+// destroy.
+int store_retain(cdc_store *st, const unsigned long long *d_refs, uint32_t *d_map, cdc_collect_stats_t *out,
+                 hipStream_t s);
+
+// cdc_debug_collect_split's six figures of this thread: store_retain fills
+// [0..4] and zeroes [5], the file layer sets [5].
+double *collect_split();
+
 // Device memory of one call, freed when the call returns.
 struct DeviceScratch {
     std::vector<void *> ptrs;

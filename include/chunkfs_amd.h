@@ -39,7 +39,9 @@ extern "C" {
  *    CDC_SCRUB_*; the bench fixture -- cdc_files_get_to_dedup_ratio,
  *    cdc_file_verify_device, cdc_store_size_distribution_device; the AE
  *    chunker -- CDC_ALGO_AE, cdc_create_ae; the batch write --
- *    cdc_files_write_batch_device, cdc_fwrite_t. */
+ *    cdc_files_write_batch_device, cdc_fwrite_t; removal and collection --
+ *    cdc_files_remove, cdc_files_collect, cdc_store_retain_device,
+ *    cdc_collect_stats_t. */
 #define CHUNKFS_AMD_ABI_VERSION 6
 
 /* Chunk{offset,length} -- reference src/lib.rs:43-47 (usize fields; u64 here). */
@@ -781,6 +783,86 @@ int64_t cdc_file_verify_device(cdc_fh_t *fh, const uint8_t *d_data, size_t len, 
  * adjustment + 1 counters) cannot be allocated. */
 int64_t cdc_store_size_distribution_device(cdc_store_t *st, uint64_t adjustment, uint64_t *d_sizes,
                                            uint32_t *d_counts, size_t cap, void *hip_stream);
+
+/* ---- Removal and collection ---------------------------------------------------------
+ * Not in the reference, whose store only grows: delete a file and get its space
+ * in the arena back.  cdc_files_remove forgets a file on the host;
+ * cdc_files_collect (and cdc_store_retain_device for users of the bare store)
+ * then keeps exactly the containers that are still referenced, slides them down
+ * the arena in place and rebuilds the table.
+ *
+ * After a collect with reference counts refs (for a layer: how many spans of its
+ * files name the container; for cdc_store_retain_device: how often its digest is
+ * given):
+ *   a container stays if and only if refs > 0; its digest, length and bytes are
+ *     unchanged, so get, contains and every file read return what they did.  A
+ *     dropped digest is absent (contains 0, get CDC_ENOTFOUND) and a later put of
+ *     the same bytes reports it new and stores it again;
+ *   the survivors keep their relative arena order: the arena afterwards is their
+ *     padded lengths back to back from 0 and arena_used is that sum.  The layout
+ *     depends on the calls alone.  Where a length-0 container lies is unspecified;
+ *   the stats are those of a store that had only ever been handed the surviving
+ *     references: unique_chunks / unique_bytes are the survivors', chunks_written
+ *     = sum of refs, bytes_written = sum of refs * length.  For a layer whose
+ *     files were all written through it: what they would be had only the
+ *     remaining files been written;
+ *   the store's epoch is bumped (every cached slot and offset is stale).  The
+ *     collecting layer rewrites the slot and offset of every span of its files
+ *     and stamps them with the new epoch; a file that was stale already (written
+ *     before a cdc_store_clear) is no root and stays stale.  A SECOND LAYER ON THE
+ *     SAME STORE IS NOT CONSULTED: its containers are dropped unless the
+ *     collecting layer names them too, and all its files return CDC_ENOTFOUND
+ *     afterwards -- never wrong bytes.  Handles of cdc_store_retain_device's
+ *     callers: every layer on the store goes stale.
+ * A collect with nothing to drop moves no byte; it still rebuilds the table,
+ * bumps the epoch and restamps the files (the stats may change: a removed file
+ * whose chunks all live on in other files lowers chunks_written).
+ *
+ * A refused call changes nothing -- stats, epoch, every read, the arena bytes
+ * below arena_used.  All refusals and every allocation come before the first
+ * write to the table, the arena or a span table:
+ *   CDC_EINVAL    a NULL layer, store or name, n > 0 with NULL digests;
+ *   CDC_ENOTFOUND cdc_store_retain_device: a digest that is not stored;
+ *   CDC_ENOMEM    a scratch allocation failed (the bounce buffer, the second set
+ *                 of table arrays: 56 bytes per slot, about 150 bytes per
+ *                 survivor);
+ *   CDC_ENOTSUP   the store holds target-kind containers (it was scrubbed):
+ *                 collecting key runs is not implemented.
+ * Collecting a store that is another store's TARGET is allowed; the epoch bump
+ * is what the base already treats as "target cleared".
+ * A CDC_EDEVICE (a HIP error) once the move has begun leaves the store fit only
+ * for cdc_store_clear or cdc_store_destroy.
+ *
+ * The move is in place: a group of survivors goes straight to its new offsets
+ * when the whole group fits into the gap below it, and through a bounce buffer
+ * otherwise.  The buffer is min(256 MiB, bytes to move), never below the longest
+ * surviving container; CHUNKFS_AMD_GC_BOUNCE=bytes overrides the 256 MiB. */
+typedef struct cdc_collect_stats {
+    uint64_t containers_before;
+    uint64_t containers_after;
+    uint64_t arena_used_before;
+    uint64_t arena_used_after;
+    uint64_t bytes_moved;    /* padded bytes of the survivors that changed place */
+    uint64_t groups_direct;  /* move groups copied arena -> arena */
+    uint64_t groups_bounced; /* move groups that went through the bounce buffer */
+    double seconds;          /* wall time of the call */
+} cdc_collect_stats_t;
+
+/* Drops the file `name` and returns its span table to the layer's pool.  Host
+ * only: no device work, the store is not touched (cdc_files_collect reclaims
+ * the space).  CDC_ENOTFOUND for an unknown name.  Handles to the file stay
+ * allocated and every later call through them returns CDC_ENOTFOUND until a
+ * file of that name is created again -- a new, empty file. */
+int cdc_files_remove(cdc_files_t *fs, const char *name);
+
+/* Keeps exactly the containers that some file of this layer references (see
+ * above).  out is nullable. */
+int cdc_files_collect(cdc_files_t *fs, cdc_collect_stats_t *out, void *hip_stream);
+
+/* The same for users of the bare store: keeps exactly the containers whose
+ * digest is among d_digests[0..n) (DEVICE, 32 bytes each; duplicates allowed,
+ * each one counts as a reference; n = 0 keeps none).  Returns the number kept. */
+int64_t cdc_store_retain_device(cdc_store_t *st, const uint8_t *d_digests, size_t n, void *hip_stream);
 
 /* ---- Synthetic data -----------------------------------------
  * Fill a DEVICE buffer with the splitmix64 stream: little-endian u64 words,

@@ -249,6 +249,14 @@ class Store {
         return check(cdc_store_contains_device(st_, d_digests, n, d_found, hip_stream));
     }
     void clear() { check(cdc_store_clear(st_)); }
+    // Keeps exactly the containers whose digest is among the n given (duplicates
+    // allowed, n = 0 keeps none), drops the rest and compacts the arena in place;
+    // returns the number kept.  Throws CDC_ENOTFOUND for a digest that is not
+    // stored, CDC_ENOTSUP on a scrubbed store.  Every file layer on the store
+    // goes stale (chunkfs_amd.h "Removal and collection").
+    int64_t retain_device(const uint8_t *d_digests, size_t n, void *hip_stream = nullptr) {
+        return check(cdc_store_retain_device(st_, d_digests, n, hip_stream));
+    }
     cdc_store_stats_t stats() const {
         cdc_store_stats_t s{};
         check(cdc_store_stats(st_, &s));
@@ -409,6 +417,17 @@ class Files {
         std::vector<char> buf(name.size() + 400);
         check(cdc_files_get_to_dedup_ratio(fs_, name.c_str(), dedup_ratio, buf.data(), buf.size(), hip_stream));
         return std::string(buf.data());
+    }
+    // Drops the file (host only); throws CDC_ENOTFOUND for an unknown name.  Calls
+    // through handles to it throw CDC_ENOTFOUND from here on.
+    void remove(const std::string &name) { check(cdc_files_remove(fs_, name.c_str())); }
+    // Keeps exactly the containers some file of this layer references, compacts
+    // the arena in place and rewrites every file's table (chunkfs_amd.h "Removal
+    // and collection").  A second layer on the same store goes stale.
+    cdc_collect_stats_t collect(void *hip_stream = nullptr) {
+        cdc_collect_stats_t s{};
+        check(cdc_files_collect(fs_, &s, hip_stream));
+        return s;
     }
     // clear_database (mod.rs:275-278): no files, an empty store, handles invalid.
     void clear() { check(cdc_files_clear(fs_)); }

@@ -97,6 +97,15 @@ int64_t cdc_debug_host_placement(cdc_handle_t *h, char *buf, size_t cap);
  * by cdc_files_destroy.  CDC_EINVAL for a NULL layer. */
 int64_t cdc_debug_files_table_blocks(const cdc_files_t *fs);
 
+/* Where the last successful cdc_files_collect / cdc_store_retain_device of this
+ * thread spent its time: wall milliseconds between the call's host waits (every
+ * pass ends in one, so each figure covers the device work queued before it):
+ * [0] references and survivor flags, [1] scratch and second-table allocation,
+ * [2] survivor list, sort, new offsets and move plan, [3] index rebuild, [4] the
+ * move, [5] table rewrite (0 for cdc_store_retain_device).  Copies min(n, 6)
+ * entries and returns 6; CDC_EINVAL for n > 0 with NULL ms. */
+int cdc_debug_collect_split(double *ms, size_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,18 @@ host's share); the layer is cleared and the files are created outside the
 timed window, and the loop and the batch alternate.  Median of 10 after a
 warm-up.
 
+Remove and collect (skipped with --no-collect), on a layer of its own written
+afresh before every timed collect:
+
+  (q) files A (the stream above) and B (a second stream of the same size),
+      remove A, cdc_files_collect: nearly every surviving byte moves, by as
+      much as A was long;
+  (r) 1024 files of 1/1024 of the stream each, every second one removed,
+      cdc_files_collect: many small gaps.
+
+(q) and (r) report the call's own wall time (every pass and host wait in it),
+the bytes moved, the move groups, and the ratio to (c) scaled to the bytes moved.
+
 Prints one JSON line; --out also writes it to a file.
 """
 import argparse
@@ -231,6 +243,71 @@ def batch_write_legs(a, c, L, P, ch):
     return res
 
 
+def collect_legs(a, c, L, P, ch, buf, n, memcpy_ms):
+    """Legs (q)-(r): remove and collect.  Every timed collect runs on a layer
+    written afresh; the time is the call's own wall time (cdc_collect_stats_t
+    .seconds: every pass, the host waits included), set against the device's own
+    copy of as many bytes as the collect moved (leg (c), scaled by the bytes).
+    split_ms is cdc_debug_collect_split of the last run: wall time between the
+    call's host waits, pass by pass."""
+    import time
+
+    import numpy as np
+    import torch
+    from chunkfs_amd import _lib
+
+    res = {}
+    other = torch.empty(n, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    _lib.check(L.cdc_fill_splitmix64_device(P(other.data_ptr()), n, a.seed + 1, None))
+    cap = ch.batch_max_chunks([n, n])
+    fsys = c.FileSystem(store=c.ChunkStore(cap, 2 * n + 16 * cap))
+
+    def leg(name, fill, remove):
+        runs = []
+        for it in range(1 + a.collect_iters):
+            fsys.clear_database()
+            fill()
+            for nm in remove():
+                fsys.remove_file(nm)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = fsys.collect()
+            r["call_ms"] = (time.perf_counter() - t0) * 1e3  # with the scratch and the old table freed
+            split = (ctypes.c_double * 6)()
+            assert L.cdc_debug_collect_split(split, 6) == 6
+            r["split_ms"] = dict(zip(("references", "allocation", "sort_plan", "rebuild", "move", "rewrite"), split))
+            if it:
+                runs.append(r)
+        ms = [r["seconds"] * 1e3 for r in runs]
+        calls = [r["call_ms"] for r in runs]
+        r = runs[-1]
+        own = memcpy_ms * r["bytes_moved"] / n  # the device's own copy of the same byte count
+        res[name] = {k: r[k] for k in r if k not in ("seconds", "call_ms")}
+        res[name].update(collect_ms=float(np.median(ms)), collect_ms_min_max=[min(ms), max(ms)],
+                         call_ms=float(np.median(calls)), call_ms_min_max=[min(calls), max(calls)],
+                         memcpy_same_bytes_ms=own, collect_over_memcpy=float(np.median(ms)) / own if own else None,
+                         moved_GiBps=r["bytes_moved"] / (1 << 30) / (float(np.median(ms)) * 1e-3))
+
+    def two_files():
+        for nm, t in (("A", buf), ("B", other)):
+            h = fsys.create_file(nm, ch)
+            assert L.cdc_file_write_device(h._fh, ch._h, P(t.data_ptr()), n, None) > 0
+
+    files, size = 1024, n // 1024
+    reqs = (_lib.cdc_fwrite_t * files)()
+
+    def many_files():
+        hs = [fsys.create_file(f"f{i:04d}", ch) for i in range(files)]
+        for i, h in enumerate(hs):
+            reqs[i].fh, reqs[i].d_data, reqs[i].len = h._fh.value, buf.data_ptr() + i * size, size
+        assert L.cdc_files_write_batch_device(fsys._h, ch._h, files, reqs, None, None) > 0
+
+    leg("q_remove_first_of_two", two_files, lambda: ["A"])
+    leg("r_remove_every_second_of_1024", many_files, lambda: [f"f{i:04d}" for i in range(0, files, 2)])
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--bytes", type=int, default=1 << 30)
@@ -240,6 +317,8 @@ def main():
     ap.add_argument("--out", default=None, help="also write the JSON result to this file")
     ap.add_argument("--no-scrub", action="store_true", help="skip the scrub-stage legs (g)-(j)")
     ap.add_argument("--no-batch-write", action="store_true", help="skip the many-files legs (o)-(p)")
+    ap.add_argument("--no-collect", action="store_true", help="skip the remove-and-collect legs (q)-(r)")
+    ap.add_argument("--collect-iters", type=int, default=3)
     ap.add_argument("--scrub-iters", type=int, default=3)
     ap.add_argument("--scrub-groups", default="4096,64m;65536,256m;1048576,1024m",
                     help="RECHUNK groups to time: containers,bytes[k|m] separated by ';'")
@@ -437,6 +516,8 @@ def main():
         res.update(scrub_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med, med(t_fread)))
     if not a.no_batch_write:
         res["batch_write"] = batch_write_legs(a, c, L, P, ch)
+    if not a.no_collect:
+        res["collect"] = collect_legs(a, c, L, P, ch, buf, n, med(t_memcpy))
     line = json.dumps(res)
     print(line)
     if a.out:
