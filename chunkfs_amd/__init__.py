@@ -571,6 +571,27 @@ class ScrubMeasurements:
                 f"data_left: {self.data_left} }}")
 
 
+class SpliceStats:
+    """cdc_splice_stats_t of one FileSystem.splice: the first span replaced, how
+    many spans went and came, where the new cuts met the old ones again (in the
+    new file's coordinates), the sizes, the bytes the put stored for first-seen
+    chunks, the bytes handed to the chunker and the chunking rounds."""
+
+    FIELDS = ("first_span", "spans_removed", "spans_inserted", "resync_offset", "size_before", "size_after",
+              "bytes_new", "window_bytes", "rounds")
+    __slots__ = FIELDS
+
+    def __init__(self, **kw):
+        for f in self.FIELDS:
+            setattr(self, f, int(kw.get(f, 0)))
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f in self.FIELDS}
+
+    def __repr__(self):
+        return "SpliceStats { " + ", ".join(f"{f}: {getattr(self, f)}" for f in self.FIELDS) + " }"
+
+
 class CopyScrubber:
     """CopyScrubber (scrub.rs:85-114): every chunk moves to the target map under
     its own hash; the container keeps that one key."""
@@ -998,6 +1019,63 @@ class FileSystem:
         """cdc_file_append_device: spans chunked and hashed by the caller (device pointers)."""
         return check(lib().cdc_file_append_device(handle._fh, _ptr(d_data), data_len, _ptr(d_chunks),
                                                   _ptr(d_digests), n, _ptr(stream)))
+
+    # -- edits in place ---------------------------------------------------------------
+    def splice(self, handle, offset, remove_len, data, stream=None):
+        """cdc_file_splice_device: replace the bytes [offset, offset + remove_len)
+        of the file with `data` (host bytes, a numpy array or a CUDA uint8
+        tensor, as for write_to_file; None or empty inserts nothing), through the
+        handle's chunker.  Only the spans from the one that holds offset - 8 to
+        the first new cut that falls on an old one are chunked, hashed and stored
+        again; the result is span for span the file a single write of the new
+        content would have made.  Returns SpliceStats.  A refused call (CdcError)
+        changes nothing; the replaced spans' containers stay in the store until
+        collect()."""
+        import torch
+        if handle.chunker is None:  # the library refuses too; this keeps the upload away
+            self.stat(handle)  # CDC_ENOTFOUND first, as write_to_file
+            raise CdcError(_lib.CDC_EPERM, "file handle is read-only")
+        dev = f"cuda:{self.device}"
+        if data is None:
+            t = torch.empty(0, dtype=torch.uint8, device=dev)
+        elif isinstance(data, torch.Tensor):
+            t = data.contiguous().view(torch.uint8).reshape(-1)
+            if not t.is_cuda:
+                t = t.to(dev)
+        else:
+            t = torch.from_numpy(_as_buffer(data)[2].copy()).to(dev)
+        if stream is None:
+            torch.cuda.synchronize(dev)  # the call runs on the store's stream, not torch's
+        s = _lib.cdc_splice_stats_t()
+        got = check(lib().cdc_file_splice_device(handle._fh, handle.chunker._h, int(offset), int(remove_len),
+                                                 _ptr(t.data_ptr()) if t.numel() else None, t.numel(),
+                                                 ctypes.byref(s), _ptr(stream)))
+        if not remove_len and not t.numel():  # nothing to do: the library fills no stats
+            size = self.stat(handle)["size"]
+            return SpliceStats(size_before=size, size_after=size, resync_offset=int(offset))
+        assert got == s.spans_inserted
+        return SpliceStats(**{f: getattr(s, f) for f in SpliceStats.FIELDS})
+
+    def pwrite(self, handle, offset, data, stream=None):
+        """Overwrite from `offset` on: up to the end of the file in place, the rest
+        of `data` extends it (pwrite(2)); offset above the size is refused."""
+        size = self.stat(handle)["size"]
+        n = data.numel() if hasattr(data, "numel") else _as_buffer(data)[2].size
+        return self.splice(handle, offset, max(0, min(int(n), size - int(offset))), data, stream)
+
+    def insert(self, handle, offset, data, stream=None):
+        return self.splice(handle, offset, 0, data, stream)
+
+    def delete_range(self, handle, offset, length, stream=None):
+        return self.splice(handle, offset, length, None, stream)
+
+    def truncate(self, handle, size, stream=None):
+        """Cut the file down to `size` bytes; a size above the file's is refused
+        (CDC_EINVAL), as a splice past the end is."""
+        have = self.stat(handle)["size"]
+        if int(size) > have:
+            raise CdcError(_lib.CDC_EINVAL, f"truncate: {size} is above the file's {have} bytes")
+        return self.splice(handle, size, have - int(size), None, stream)
 
     # -- reads ----------------------------------------------------------------------
     def read_complete_device(self, handle, d_out, out_cap, d_spans=None, stream=None):

@@ -42,13 +42,14 @@ EXPORTS = [
     "cdc_files_write_batch_device",
     "cdc_files_get_to_dedup_ratio", "cdc_file_verify_device", "cdc_store_size_distribution_device",
     "cdc_files_remove", "cdc_files_collect", "cdc_store_retain_device",
+    "cdc_file_splice_device",
     "cdc_fill_splitmix64_device", "cdc_version", "cdc_abi_version",
 ]
 # include/chunkfs_amd_debug.h (diagnostics, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["cdc_debug_pipeline", "cdc_debug_record_cap", "cdc_debug_copy", "cdc_debug_host_stats",
                  "cdc_debug_read_bw", "cdc_debug_host_placement",
                  "cdc_debug_timing_back", "cdc_debug_walk_params", "cdc_debug_files_table_blocks",
-                 "cdc_debug_collect_split"]
+                 "cdc_debug_collect_split", "cdc_debug_splice_split", "cdc_debug_file_slots"]
 
 
 class CdcError(RuntimeError):
@@ -104,6 +105,14 @@ class cdc_collect_stats_t(ctypes.Structure):
                 ("arena_used_before", ctypes.c_uint64), ("arena_used_after", ctypes.c_uint64),
                 ("bytes_moved", ctypes.c_uint64), ("groups_direct", ctypes.c_uint64),
                 ("groups_bounced", ctypes.c_uint64), ("seconds", ctypes.c_double)]
+
+
+class cdc_splice_stats_t(ctypes.Structure):
+    _fields_ = [("first_span", ctypes.c_uint64), ("spans_removed", ctypes.c_uint64),
+                ("spans_inserted", ctypes.c_uint64), ("resync_offset", ctypes.c_uint64),
+                ("size_before", ctypes.c_uint64), ("size_after", ctypes.c_uint64),
+                ("bytes_new", ctypes.c_uint64), ("window_bytes", ctypes.c_uint64),
+                ("rounds", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
 
 
 class cdc_timing_t(ctypes.Structure):
@@ -291,6 +300,13 @@ def lib():
     L.cdc_files_collect.restype = ctypes.c_int
     L.cdc_store_retain_device.argtypes = [P, P, sz, P]
     L.cdc_store_retain_device.restype = ctypes.c_int64
+    L.cdc_file_splice_device.argtypes = [P, P, ctypes.c_uint64, ctypes.c_uint64, P, sz,
+                                         ctypes.POINTER(cdc_splice_stats_t), P]
+    L.cdc_file_splice_device.restype = ctypes.c_int64
+    L.cdc_debug_splice_split.argtypes = [ctypes.POINTER(ctypes.c_double), sz]
+    L.cdc_debug_splice_split.restype = ctypes.c_int
+    L.cdc_debug_file_slots.argtypes = [P, P, P, sz]
+    L.cdc_debug_file_slots.restype = ctypes.c_int64
     L.cdc_fill_splitmix64_device.argtypes = [P, sz, ctypes.c_uint64, P]
     L.cdc_fill_splitmix64_device.restype = ctypes.c_int
     L.cdc_debug_pipeline.argtypes = [P]

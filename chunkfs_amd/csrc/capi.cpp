@@ -20,6 +20,7 @@ int64_t bad_handle() {
 
 namespace cdc {
 int handle_device(const cdc_handle *h) { return h->engine->device(); }
+uint64_t handle_max_chunk(const cdc_handle *h) { return h->engine->max_chunk(); }
 }  // namespace cdc
 
 extern "C" {

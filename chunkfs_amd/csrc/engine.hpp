@@ -81,6 +81,8 @@ class Engine {
     // (cut_gear starts testing at index 2*(min/2)).
     size_t min_chunk() const { return algo_ == CDC_ALGO_FASTCDC ? (min_ / 2) * 2 : min_; }
     size_t max_chunks(size_t len) const { return len / min_chunk() + 1; }
+    // The longest chunk the rule cuts (FSChunker: the chunk size).
+    size_t max_chunk() const { return algo_ == CDC_ALGO_FIXED ? min_ : max_; }
     size_t batch_max_chunks(size_t n, const uint64_t *lens) const;
     int set_gear(const uint64_t *gear);
     int set_rabin_poly(uint64_t poly);

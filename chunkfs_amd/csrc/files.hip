@@ -36,6 +36,8 @@
 // as its last step.
 #include "files.hpp"
 
+#include "splice_plan.hpp"
+
 namespace cdc {
 namespace {
 
@@ -533,6 +535,105 @@ __global__ __launch_bounds__(kFlThreads) void ratio_write_kernel(SpanTable src, 
     to[1] = from[1];
 }
 
+// ---- splice (cdc_file_splice_device) -----------------------------------------------
+// One thread: the start span and its offset.
+__global__ void splice_start_kernel(const uint64_t *__restrict__ off, uint64_t n, uint64_t offset,
+                                    unsigned long long *out) {
+    if (blockIdx.x || threadIdx.x) return;
+    const uint64_t i0 = splice_start_span(off, n, offset);
+    out[0] = i0;
+    out[1] = off[i0];
+}
+
+// Whether chunk k of the window resyncs: it is trusted, its cut lies at or past
+// the inserted bytes and, moved back by delta, on an old boundary (*j, the first
+// of equal offsets).
+__device__ __forceinline__ bool splice_meets(const cdc_chunk_pod c, const SpliceRound &r,
+                                             const uint64_t *__restrict__ off, uint64_t n, uint64_t *e, uint64_t *j) {
+    const uint64_t start = r.w0 + c.offset;
+    *e = start + c.length;
+    if (!splice_trusted(start, r.max_chunk, r.end_w, r.size_after)) return false;
+    if (*e < r.offset + r.insert_len) return false;
+    return splice_old_boundary(off, n, *e, r.remove_len, r.insert_len, j);
+}
+
+// One thread per new chunk; the smallest k that meets, reduced within the wave,
+// then one atomicMin per wave.
+__global__ __launch_bounds__(kFlThreads) void splice_resync_kernel(const cdc_chunk_pod *__restrict__ chunks,
+                                                                   uint64_t m, SpliceRound r,
+                                                                   const uint64_t *__restrict__ off, uint64_t n,
+                                                                   unsigned long long *best) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t cand = ~0ull;
+    if (k < m) {
+        uint64_t e, j;
+        if (splice_meets(chunks[k], r, off, n, &e, &j)) cand = k;
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = __shfl_xor(cand, d);
+        cand = o < cand ? o : cand;
+    }
+    if ((threadIdx.x & 63) == 0 && cand != ~0ull) atomicMin(best, (unsigned long long)cand);
+}
+
+// One thread: {k, j, e_k} of the winner for the host.
+__global__ void splice_pick_kernel(const cdc_chunk_pod *__restrict__ chunks, SpliceRound r,
+                                   const uint64_t *__restrict__ off, uint64_t n,
+                                   const unsigned long long *__restrict__ best, unsigned long long *out) {
+    if (blockIdx.x || threadIdx.x) return;
+    const uint64_t k = *best;
+    uint64_t e = 0, j = 0;
+    if (k != ~0ull) (void)splice_meets(chunks[k], r, off, n, &e, &j);
+    out[0] = k;
+    out[1] = j;
+    out[2] = e;
+}
+
+// val = exclusive scan of the m accepted lengths.  Entry t of the new table:
+// t < i0 the old entry; t < i0 + m accepted chunk t - i0, as append_kernel writes
+// it; after that old entry j + (t - i0 - m) with its offset moved.  Entry n_new
+// closes the table.  patch: dst is the old table, only [i0, i0 + m) is written
+// (the offsets around it stay what they are).
+__global__ __launch_bounds__(kFlThreads) void splice_build_kernel(SpanTable old, SpanTable dst, uint64_t i0,
+                                                                  uint64_t j, uint64_t n, uint64_t size_old,
+                                                                  uint64_t w0, uint64_t rem, uint64_t ins,
+                                                                  uint64_t n_new, bool patch,
+                                                                  const uint32_t *__restrict__ slot_of,
+                                                                  const uint64_t *__restrict__ tbl_loc,
+                                                                  const uint8_t *__restrict__ digests, uint64_t m,
+                                                                  const uint64_t *__restrict__ val) {
+    uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (patch) {
+        if (t >= m) return;
+        t += i0;
+    } else if (t > n_new) {
+        return;
+    }
+    if (t >= i0 && t < i0 + m) {
+        const uint64_t c = t - i0;
+        const uint32_t s = slot_of[c];
+        dst.off[t] = w0 + val[c];
+        dst.slot[t] = s;
+        dst.loc[t] = s == kNoSlot ? 0 : tbl_loc[s];
+        const uint4 *src = reinterpret_cast<const uint4 *>(digests + 32 * c);
+        uint4 *to = reinterpret_cast<uint4 *>(dst.digest + 32 * t);
+        to[0] = src[0];
+        to[1] = src[1];
+        return;
+    }
+    const uint64_t si = t < i0 ? t : j + (t - i0 - m);
+    const uint64_t o = si == n ? size_old : old.off[si];  // a file without spans has no table
+    dst.off[t] = t < i0 ? o : o - rem + ins;
+    if (t == n_new) return;
+    dst.slot[t] = old.slot[si];
+    dst.loc[t] = old.loc[si];
+    const uint4 *src = reinterpret_cast<const uint4 *>(old.digest + 32 * si);
+    uint4 *to = reinterpret_cast<uint4 *>(dst.digest + 32 * t);
+    to[0] = src[0];
+    to[1] = src[1];
+}
+
 // ---- collect (cdc_files_collect) --------------------------------------------------
 // The m spans of all the layer's files in one launch, segmented as the batch
 // append is: span i belongs to file f = file_of_span(first, nfiles, i).
@@ -589,6 +690,36 @@ __global__ __launch_bounds__(kFlThreads) void collect_remap_kernel(const Collect
 }
 
 }  // namespace
+
+hipError_t launch_splice_start(const uint64_t *off, uint64_t n, uint64_t offset, unsigned long long *h_out,
+                               hipStream_t s) {
+    splice_start_kernel<<<1, 64, 0, s>>>(off, n, offset, h_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_splice_resync(const cdc_chunk_pod *chunks, uint64_t m, const SpliceRound &r, const uint64_t *off,
+                                uint64_t n, unsigned long long *d_best, unsigned long long *h_out, hipStream_t s) {
+    const hipError_t e = hipMemsetAsync(d_best, 0xFF, 8, s);
+    if (e != hipSuccess) return e;
+    splice_resync_kernel<<<grid_of(m), kFlThreads, 0, s>>>(chunks, m, r, off, n, d_best);
+    splice_pick_kernel<<<1, 64, 0, s>>>(chunks, r, off, n, d_best, h_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_splice_build(const SpanTable &old, uint64_t n, uint64_t size_old, const SpanTable &dst,
+                               uint64_t i0, uint64_t j, uint64_t w0, uint64_t rem, uint64_t ins, const uint32_t *slot_of,
+                               const uint64_t *tbl_length, const uint64_t *tbl_loc, const uint8_t *d_digests,
+                               uint64_t m, uint64_t *val, uint64_t *block_sums, unsigned long long *d_stat,
+                               unsigned long long *h_total, hipStream_t s) {
+    span_len_kernel<<<grid_of(m), kFlThreads, 0, s>>>(slot_of, tbl_length, m, val, d_stat);
+    const hipError_t e = launch_store_scan(val, m, block_sums, h_total, s);
+    if (e != hipSuccess) return e;
+    const uint64_t n_new = i0 + m + (n - j);
+    const bool patch = dst.off == old.off;
+    splice_build_kernel<<<grid_of(patch ? m : n_new + 1), kFlThreads, 0, s>>>(
+        old, dst, i0, j, n, size_old, w0, rem, ins, n_new, patch, slot_of, tbl_loc, d_digests, m, val);
+    return hipGetLastError();
+}
 
 hipError_t launch_files_refs(const CollectSeg *d_seg, const uint64_t *d_first, uint64_t nfiles, uint64_t m,
                              uint64_t slots, unsigned long long *refs, hipStream_t s) {

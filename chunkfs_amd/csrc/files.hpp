@@ -160,6 +160,37 @@ hipError_t launch_files_refs(const CollectSeg *d_seg, const uint64_t *d_first, u
 hipError_t launch_files_remap(const CollectSeg *d_seg, const uint64_t *d_first, uint64_t nfiles, uint64_t m,
                               uint64_t slots, const uint32_t *map, const uint64_t *new_loc, hipStream_t s);
 
+// ---- splice (cdc_file_splice_device; the arithmetic: splice_plan.hpp) -------------
+// Step 1: h_out (pinned) = {i0, off[i0]} of a table holding n > 0 spans.
+hipError_t launch_splice_start(const uint64_t *off, uint64_t n, uint64_t offset, unsigned long long *h_out,
+                               hipStream_t s);
+
+// What one round's resync needs besides the table: the window [w0, end_w) of the
+// new file that was chunked, and the edit.
+struct SpliceRound {
+    uint64_t w0, end_w;
+    uint64_t size_after;
+    uint64_t offset, remove_len, insert_len;
+    uint64_t max_chunk;
+};
+// Step 3 over the m > 0 chunks of a window (offsets relative to w0): the smallest
+// trusted k whose cut e_k >= offset + insert_len lies on an old boundary.  d_best:
+// one device word.  h_out (pinned) = {k, j, e_k}, k = ~0 when no chunk qualifies.
+hipError_t launch_splice_resync(const cdc_chunk_pod *chunks, uint64_t m, const SpliceRound &r, const uint64_t *off,
+                                uint64_t n, unsigned long long *d_best, unsigned long long *h_out, hipStream_t s);
+
+// Step 4 after the put of the m accepted chunks (slot_of .. d_stat, h_total as
+// launch_files_append): dst = old spans [0, i0), the m chunks from offset w0 on,
+// old spans [j, n) with off + (ins - rem); dst.off[n_new] closes the table, n_new
+// = i0 + m + n - j.  dst must not overlap old -- unless m == j - i0 and ins ==
+// rem, when dst may BE old: then only the entries [i0, i0 + m) are written.
+// size_old = old.off[n]: a file without spans has no table to read it from.
+hipError_t launch_splice_build(const SpanTable &old, uint64_t n, uint64_t size_old, const SpanTable &dst,
+                               uint64_t i0, uint64_t j, uint64_t w0, uint64_t rem, uint64_t ins, const uint32_t *slot_of,
+                               const uint64_t *tbl_length, const uint64_t *tbl_loc, const uint8_t *d_digests,
+                               uint64_t m, uint64_t *val, uint64_t *block_sums, unsigned long long *d_stat,
+                               unsigned long long *h_total, hipStream_t s);
+
 // ---- get_to_dedup_ratio (file_layer.rs:208-268) -----------------------------------
 // Step 1: the unique list over spans [0, m), m = n - 1, from the distribution's
 // first-occurrence flags and scan: uidx[j] = span index of the j-th distinct

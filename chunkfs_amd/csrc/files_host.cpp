@@ -16,6 +16,7 @@
 #include "../../include/chunkfs_amd_debug.h"
 #include "engine.hpp"
 #include "files.hpp"
+#include "splice_plan.hpp"
 #include "store.hpp"
 #include "store_internal.hpp"
 
@@ -123,6 +124,11 @@ struct cdc_files {
     uint64_t *d_pcnt = nullptr, *d_xblock = nullptr;
     unsigned long long *h_xtot = nullptr;  // pinned: [0] pieces, [1] target-kind spans touched
     unsigned long long *d_touch = nullptr;
+    // cdc_file_splice_device: the window of the new file that is chunked, and the searches' results
+    uint64_t s_cap = 0;
+    uint8_t *s_win = nullptr;
+    unsigned long long *h_sp = nullptr;  // pinned: start {i0, off[i0]}; resync {k, j, e_k}
+    unsigned long long *d_sp = nullptr;  // the smallest chunk that resyncs
 };
 
 struct cdc_fh {
@@ -314,6 +320,9 @@ void release(cdc_files *fs) {
     (void)hipFree(fs->d_xblock);
     (void)hipHostFree(fs->h_xtot);
     (void)hipFree(fs->d_touch);
+    (void)hipFree(fs->s_win);
+    (void)hipHostFree(fs->h_sp);
+    (void)hipFree(fs->d_sp);
     delete fs;
 }
 
@@ -534,6 +543,207 @@ int64_t read_one(cdc_fh *fh, uint32_t kind, uint64_t a, uint64_t b, uint8_t *d_o
     return (int64_t)fh->fs->h_res[0].bytes;
 }
 
+// ---- splice ---------------------------------------------------------------------
+double *splice_split() {
+    static thread_local double split[5];
+    return split;
+}
+
+// The window buffer for `window` bytes, and the result words.
+int grow_splice(cdc_files *fs, uint64_t window) {
+    if (!fs->h_sp) {
+        FL_TRY(hipHostMalloc(&fs->h_sp, 4 * sizeof(unsigned long long)));
+        FL_TRY(hipMalloc(&fs->d_sp, sizeof(unsigned long long)));
+    }
+    if (fs->s_cap >= window) return CDC_OK;
+    (void)hipFree(fs->s_win);
+    fs->s_win = nullptr;
+    fs->s_cap = 0;
+    const uint64_t cap = (window + window / 8 + 4095) & ~4095ull;
+    FL_TRY(hipMalloc(&fs->s_win, cap));
+    fs->s_cap = cap;
+    return CDC_OK;
+}
+
+int grow_write(cdc_files *fs, uint64_t cap) {
+    if (fs->w_cap >= cap) return CDC_OK;
+    (void)hipFree(fs->w_chunks);
+    (void)hipFree(fs->w_dig);
+    fs->w_chunks = nullptr;
+    fs->w_dig = nullptr;
+    fs->w_cap = 0;
+    FL_TRY(hipMalloc(&fs->w_chunks, cap * sizeof(cdc_chunk_t)));
+    FL_TRY(hipMalloc(&fs->w_dig, cap * 32));
+    fs->w_cap = cap;
+    return CDC_OK;
+}
+
+int64_t splice(cdc_fh *fh, cdc_handle_t *chunker, uint64_t offset, uint64_t remove_len, const uint8_t *d_data,
+               uint64_t insert_len, cdc_splice_stats_t *out, void *hip_stream) {
+    // Everything that can refuse, before any device work.
+    if (!fh) return fail(CDC_EINVAL, "cdc_file_splice_device: NULL file handle");
+    if (!chunker) return fail(CDC_EINVAL, "cdc_file_splice_device: NULL chunker");
+    if (insert_len && !d_data) return fail(CDC_EINVAL, "cdc_file_splice_device: NULL data");
+    FileRec *f = nullptr;
+    int rc = lookup(fh, false, &f);
+    if (rc) return rc;
+    if (fh->readonly) return fail(CDC_EPERM, "file handle is read-only");
+    cdc_files *fs = fh->fs;
+    cdc::StoreView v = cdc::store_view(fs->store);
+    if (f->n && f->epoch != v.epoch)
+        return fail(CDC_ENOTFOUND, "file layer: the store was cleared since '" + fh->name + "' was written");
+    const uint64_t n = f->n, size = f->size;
+    if (offset > size)
+        return fail(CDC_EINVAL, "cdc_file_splice_device: offset " + std::to_string(offset) + " is past the file's " +
+                                    std::to_string(size) + " bytes");
+    if (!cdc::splice_range_ok(size, offset, remove_len))
+        return fail(CDC_EINVAL, "cdc_file_splice_device: offset + remove_len is past the file's " +
+                                    std::to_string(size) + " bytes");
+    uint64_t size_after = 0;
+    if (!cdc::splice_size_after(size, remove_len, insert_len, &size_after))
+        return fail(CDC_EINVAL, "cdc_file_splice_device: insert_len makes the file larger than 2^64 bytes");
+    if (cdc::handle_device(chunker) != v.device)
+        return fail(CDC_EINVAL, "cdc_file_splice_device: the chunker is on another device than the store");
+    {
+        cdc::ScrubView sv;
+        bool stale = false;
+        if (cdc::store_scrub_view(fs->store, &sv, &stale))
+            return fail(CDC_ENOTSUP, "cdc_file_splice_device: the store holds target-kind containers (scrubbed); "
+                                     "not supported");
+    }
+    if (!remove_len && !insert_len) return 0;
+
+    FL_TRY(hipSetDevice(v.device));
+    hipStream_t s = stream_of(fs, hip_stream);
+    double split[5] = {0, 0, 0, 0, 0};
+    auto last = std::chrono::steady_clock::now();
+    auto lap = [&](int phase) {
+        const auto now = std::chrono::steady_clock::now();
+        split[phase] += std::chrono::duration<double, std::milli>(now - last).count();
+        last = now;
+    };
+    if ((rc = grow_splice(fs, 0)) != CDC_OK) return rc;
+
+    // 1. The start span.
+    uint64_t i0 = 0, w0 = 0;
+    if (n) {
+        FL_TRY(cdc::launch_splice_start(f->t.off, n, offset, fs->h_sp, s));
+        FL_TRY(hipStreamSynchronize(s));
+        i0 = fs->h_sp[0];
+        w0 = fs->h_sp[1];
+    }
+
+    // 2, 3. Windows of the new file from off[i0] on, until a trusted cut meets an old one.
+    const uint64_t maxc = cdc::handle_max_chunk(chunker), lo = offset + insert_len;
+    uint64_t j = n, e = size_after, m = 0, wlen = 0, window_bytes = 0;
+    uint32_t rounds = 1;
+    const uint8_t *streams[1] = {nullptr};
+    for (uint32_t round = 1; size_after > w0; ++round) {
+        const uint64_t end_w = cdc::splice_window_end(size_after, offset, insert_len, maxc, round);
+        wlen = end_w - w0;
+        if ((rc = grow_splice(fs, wlen)) != CDC_OK) return rc;
+        streams[0] = fs->s_win;
+        std::vector<HostReq> reqs;
+        if (offset > w0) reqs.push_back(HostReq{f, cdc::kReadRange, w0, offset - w0, fs->s_win, offset - w0, nullptr});
+        if (end_w > lo)
+            reqs.push_back(HostReq{f, cdc::kReadRange, offset + remove_len, end_w - lo, fs->s_win + (lo - w0),
+                                   end_w - lo, nullptr});
+        if (!reqs.empty() && (rc = run_reads(fs, reqs, hip_stream)) != CDC_OK) return rc;
+        if (insert_len)
+            FL_TRY(hipMemcpyAsync(fs->s_win + (offset - w0), d_data, insert_len, hipMemcpyDeviceToDevice, s));
+        lap(0);
+        const uint64_t lens[1] = {wlen};
+        const uint64_t cap = cdc_batch_max_chunks(chunker, 1, lens);
+        if ((rc = grow_write(fs, cap)) != CDC_OK) return rc;
+        uint64_t first[2] = {0, 0};
+        const int64_t cnt = cdc_chunk_batch_device(chunker, 1, streams, lens, fs->w_chunks, cap, first, s);
+        if (cnt < 0) return cnt;
+        window_bytes += wlen;
+        rounds = round;
+        lap(1);
+        const cdc::SpliceRound r{w0, end_w, size_after, offset, remove_len, insert_len, maxc};
+        FL_TRY(cdc::launch_splice_resync(reinterpret_cast<const cdc::cdc_chunk_pod *>(fs->w_chunks), (uint64_t)cnt, r,
+                                         f->t.off, n, fs->d_sp, fs->h_sp, s));
+        FL_TRY(hipStreamSynchronize(s));
+        lap(2);
+        if (fs->h_sp[0] != ~0ull) {
+            m = fs->h_sp[0] + 1;
+            j = fs->h_sp[1];
+            e = fs->h_sp[2];
+            break;
+        }
+        if (end_w == size_after)  // the last cut of a window that ends with the file is the file's end
+            return fail(CDC_EDEVICE, "cdc_file_splice_device: the chunks do not end where the file does");
+    }
+
+    // 4. Hash and put the accepted chunks, then the table.
+    const uint64_t n_new = i0 + m + (n - j);
+    uint64_t bytes_new = 0;
+    if (m) {
+        const uint64_t hfirst[2] = {0, m};
+        if ((rc = cdc_sha256_batch_device(chunker, 1, streams, hfirst, fs->w_chunks, fs->w_dig, s)) != CDC_OK) return rc;
+        const bool patch = m == j - i0 && insert_len == remove_len;
+        cdc::SpanTable nt = f->t;
+        uint64_t cap = f->cap;
+        if (!patch) {
+            if (!cap) cap = kTableMinCap;
+            while (cap < n_new) cap *= 2;
+            const hipError_t he = fs->pool.take(cap, &nt);
+            if (he != hipSuccess) {
+                cdc::set_error(std::string("file layer: span table for the splice: ") + hipGetErrorString(he));
+                return he == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE;
+            }
+        }
+        struct Guard {  // the fresh table goes back unless the call succeeds
+            cdc_files *fs;
+            cdc::SpanTable t;
+            uint64_t cap;
+            ~Guard() {
+                if (cap) fs->pool.give(t, cap);
+            }
+        } guard{fs, nt, patch ? 0 : cap};
+        if ((rc = grow_span_scratch(fs, m)) != CDC_OK) return rc;
+        cdc_store_stats_t before{}, after{};
+        (void)cdc_store_stats(fs->store, &before);
+        const int64_t put = cdc::store_put_slots(fs->store, fs->s_win, wlen, fs->w_chunks, fs->w_dig, m, hip_stream);
+        if (put < 0) return put;  // refused: the file and its table are as they were
+        (void)cdc_store_stats(fs->store, &after);
+        bytes_new = after.index.unique_bytes - before.index.unique_bytes;
+        v = cdc::store_view(fs->store);
+        lap(3);
+        hipError_t he = hipMemsetAsync(fs->d_stat, 0xFF, 8, s);
+        if (he == hipSuccess) he = hipMemsetAsync(fs->d_stat + 1, 0, 8, s);
+        if (he == hipSuccess)
+            he = cdc::launch_splice_build(f->t, n, size, nt, i0, j, w0, remove_len, insert_len, v.slot_of, v.length,
+                                          v.loc, fs->w_dig, m, fs->a_val, fs->a_block, fs->d_stat, fs->h_tot, s);
+        if (he == hipSuccess) he = hipMemcpyAsync(fs->h_tot + 2, fs->d_stat, 16, hipMemcpyDeviceToHost, s);
+        const hipError_t hs = hipStreamSynchronize(s);  // also on failure: nothing queued still writes the fresh table
+        if (he == hipSuccess) he = hs;
+        if (he != hipSuccess) {
+            cdc::set_error(std::string("cdc_file_splice_device: table build: ") + hipGetErrorString(he));
+            return CDC_EDEVICE;
+        }
+        if (!patch) {
+            free_table(fs, f);
+            f->t = nt;
+            f->cap = cap;
+            guard.cap = 0;
+        }
+        if (fs->h_tot[2] != ~0ull && fs->h_tot[2] + 1 < f->min_len) f->min_len = fs->h_tot[2] + 1;
+        f->zeros += fs->h_tot[3];
+        lap(4);
+    } else {
+        free_table(fs, f);  // nothing is left after off[i0] = 0: the file is empty
+    }
+    f->n = n_new;
+    f->size = size_after;
+    f->epoch = v.epoch;
+    std::memcpy(splice_split(), split, sizeof split);
+    if (out)
+        *out = cdc_splice_stats_t{i0, j - i0, m, e, size, size_after, bytes_new, window_bytes, rounds, 0};
+    return (int64_t)m;
+}
+
 }  // namespace
 
 extern "C" {
@@ -745,6 +955,28 @@ int64_t cdc_file_write_device(cdc_fh_t *fh, cdc_handle_t *chunker, const uint8_t
 int64_t cdc_file_append_device(cdc_fh_t *fh, const uint8_t *d_data, size_t data_len, const cdc_chunk_t *d_chunks,
                                const uint8_t *d_digests, size_t n, void *hip_stream) {
     return append(fh, d_data, data_len, d_chunks, d_digests, n, hip_stream);
+}
+
+int64_t cdc_file_splice_device(cdc_fh_t *fh, cdc_handle_t *chunker, uint64_t offset, uint64_t remove_len,
+                               const uint8_t *d_data, size_t insert_len, cdc_splice_stats_t *out, void *hip_stream) {
+    return splice(fh, chunker, offset, remove_len, d_data, insert_len, out, hip_stream);
+}
+
+int64_t cdc_debug_file_slots(cdc_fh_t *fh, uint32_t *slots, uint64_t *locs, size_t cap) {
+    FileRec *f = nullptr;
+    const int rc = lookup(fh, false, &f);
+    if (rc) return rc;
+    if (f->n > cap || f->n == 0) return (int64_t)f->n;
+    FL_TRY(hipSetDevice(cdc::store_view(fh->fs->store).device));
+    if (slots) FL_TRY(hipMemcpy(slots, f->t.slot, f->n * 4, hipMemcpyDeviceToHost));
+    if (locs) FL_TRY(hipMemcpy(locs, f->t.loc, f->n * 8, hipMemcpyDeviceToHost));
+    return (int64_t)f->n;
+}
+
+int cdc_debug_splice_split(double *ms, size_t n) {
+    if (n && !ms) return fail(CDC_EINVAL, "cdc_debug_splice_split: NULL argument");
+    if (n) std::memcpy(ms, splice_split(), (n < 5 ? n : 5) * sizeof(double));
+    return 5;
 }
 
 int64_t cdc_files_write_batch_device(cdc_files_t *fs, cdc_handle_t *chunker, size_t n, const cdc_fwrite_t *reqs,

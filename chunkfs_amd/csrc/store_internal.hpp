@@ -81,5 +81,7 @@ struct DeviceScratch {
 
 // The device a chunker handle is bound to (capi.cpp).
 int handle_device(const cdc_handle *h);
+// The longest chunk its rule cuts (capi.cpp): the splice's trust window.
+uint64_t handle_max_chunk(const cdc_handle *h);
 
 }  // namespace cdc

@@ -41,7 +41,8 @@ extern "C" {
  *    chunker -- CDC_ALGO_AE, cdc_create_ae; the batch write --
  *    cdc_files_write_batch_device, cdc_fwrite_t; removal and collection --
  *    cdc_files_remove, cdc_files_collect, cdc_store_retain_device,
- *    cdc_collect_stats_t. */
+ *    cdc_collect_stats_t; the edit in place -- cdc_file_splice_device,
+ *    cdc_splice_stats_t. */
 #define CHUNKFS_AMD_ABI_VERSION 6
 
 /* Chunk{offset,length} -- reference src/lib.rs:43-47 (usize fields; u64 here). */
@@ -863,6 +864,71 @@ int cdc_files_collect(cdc_files_t *fs, cdc_collect_stats_t *out, void *hip_strea
  * digest is among d_digests[0..n) (DEVICE, 32 bytes each; duplicates allowed,
  * each one counts as a reference; n = 0 keeps none).  Returns the number kept. */
 int64_t cdc_store_retain_device(cdc_store_t *st, const uint8_t *d_digests, size_t n, void *hip_stream);
+
+/* ---- Editing a file in place --------------------------------------------------------
+ * Not in the reference, whose files only grow: replace the bytes [offset, offset +
+ * remove_len) of a file with insert_len bytes from DEVICE memory (any alignment),
+ * re-chunking only until the new cuts fall back onto the old ones.  One call covers
+ * overwrite (remove_len == insert_len), insert (remove_len == 0), delete
+ * (insert_len == 0), truncate (remove_len == size - offset, insert_len == 0) and
+ * the append that re-chunks the old tail (offset == size).
+ *
+ * The rule.  Old spans have offsets off[0..n]; delta = insert_len - remove_len; C'
+ * is the old content with the range replaced.
+ *   1. i0 is the last span with off[i0] + 8 <= offset, or 0 if there is none (among
+ *      equal offsets the last).  The 8 bytes cover AE, whose cut after byte i reads
+ *      the bytes i .. i+3; every other rule reads nothing at or past its cut.
+ *   2. T = chunk_data(C'[off[i0] ..]) with `chunker`, the whole tail as one buffer:
+ *      cuts e_1 < e_2 < ... in the new file's coordinates.
+ *   3. Resync: the smallest e_k >= offset + insert_len for which e_k - delta is an
+ *      old boundary off[j]; the smallest such j.  The end of the file always is one.
+ *   4. The new table: old spans [0, i0), the chunks of T up to e_k, old spans
+ *      [j, n) with every offset moved by delta -- digests, slots and arena
+ *      locations as they were.  An edit that leaves nothing after off[i0]
+ *      (truncate to 0) inserts no span.
+ * The engine does not chunk the whole tail: it chunks windows C'[off[i0], end_w)
+ * and trusts a chunk of a window only if start + max + 8 <= end_w or the window
+ * ends at the end of the file (max: the chunker's largest chunk, the chunk size
+ * for FSChunker).  Round r = 1, 2, ... ends at min(size_after, offset + insert_len
+ * + 4^r * max + 8); every round starts again from off[i0].  So a file written in
+ * one call with chunker X and spliced with X has, span for span, the offsets and
+ * digests of a file holding C' written in one call with X.
+ *
+ * The chunks up to e_k are hashed and put into the store; chunks of rounds that
+ * did not resync are neither hashed nor stored.  The containers of the replaced
+ * spans stay in the store until cdc_files_collect.  Other handles keep their
+ * cursors as numbers.  The host waits for the device a fixed number of times per
+ * round (the span search, the window read, the chunking, the resync) plus the
+ * hash's, the put's and the final one -- never a number that grows with the file --
+ * and an edit that resyncs in round 1 costs the window plus one pass over the
+ * table (52 bytes per span; nothing but the replaced entries when the span count
+ * and the size stay the same).
+ *
+ * Refusals, all before any device work, each leaving the file exactly as it was:
+ *   CDC_EINVAL    a NULL handle, a NULL chunker, NULL data with insert_len > 0,
+ *                 offset > size or offset + remove_len > size (no holes, no clipping);
+ *   CDC_EPERM     a read-only handle;
+ *   CDC_ENOTFOUND a removed file, or one whose spans predate a store clear;
+ *   CDC_ENOTSUP   the store holds target-kind containers (it was scrubbed).
+ * remove_len == 0 && insert_len == 0 returns 0 and touches nothing.  A put refused
+ * with CDC_ENOMEM leaves the file and its table as they were: the put comes before
+ * any write to the table.  Stream and epoch conventions are cdc_file_write_device's. */
+typedef struct {
+    uint64_t first_span;      /* i0: first span replaced */
+    uint64_t spans_removed;   /* j - i0 */
+    uint64_t spans_inserted;
+    uint64_t resync_offset;   /* e_k, in the new file's coordinates (== new size if the cuts met only at the end) */
+    uint64_t size_before, size_after;
+    uint64_t bytes_new;       /* bytes the put stored for first-seen chunks */
+    uint64_t window_bytes;    /* bytes handed to the chunker, all rounds together */
+    uint32_t rounds;          /* chunking rounds (1 = the first window sufficed) */
+    uint32_t pad;
+} cdc_splice_stats_t;
+
+/* Returns spans_inserted, or a negative CDC_E* code.  out is nullable. */
+int64_t cdc_file_splice_device(cdc_fh_t *fh, cdc_handle_t *chunker, uint64_t offset, uint64_t remove_len,
+                               const uint8_t *d_data, size_t insert_len, cdc_splice_stats_t *out,
+                               void *hip_stream);
 
 /* ---- Synthetic data -----------------------------------------
  * Fill a DEVICE buffer with the splitmix64 stream: little-endian u64 words,

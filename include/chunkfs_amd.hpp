@@ -326,6 +326,34 @@ class File {
                           const uint8_t *d_digests, size_t n, void *hip_stream = nullptr) {
         return check(cdc_file_append_device(fh_, d_data, data_len, d_chunks, d_digests, n, hip_stream));
     }
+    // cdc_file_splice_device: the bytes [offset, offset + remove_len) replaced by
+    // insert_len bytes from HBM, re-chunked only until the cuts realign.
+    cdc_splice_stats_t splice(Chunker &chunker, uint64_t offset, uint64_t remove_len, const uint8_t *d_data,
+                              size_t insert_len, void *hip_stream = nullptr) {
+        cdc_splice_stats_t s{};
+        s.size_before = s.size_after = stat().size;  // what a call with nothing to do leaves unset
+        s.resync_offset = offset;
+        check(cdc_file_splice_device(fh_, chunker.handle(), offset, remove_len, d_data, insert_len, &s, hip_stream));
+        return s;
+    }
+    // Overwrite up to the end of the file and extend past it, as pwrite(2).
+    cdc_splice_stats_t pwrite(Chunker &chunker, uint64_t offset, const uint8_t *d_data, size_t len,
+                              void *hip_stream = nullptr) {
+        const uint64_t size = stat().size, left = offset < size ? size - offset : 0;
+        return splice(chunker, offset, len < left ? len : left, d_data, len, hip_stream);
+    }
+    cdc_splice_stats_t insert(Chunker &chunker, uint64_t offset, const uint8_t *d_data, size_t len,
+                              void *hip_stream = nullptr) {
+        return splice(chunker, offset, 0, d_data, len, hip_stream);
+    }
+    cdc_splice_stats_t delete_range(Chunker &chunker, uint64_t offset, uint64_t len, void *hip_stream = nullptr) {
+        return splice(chunker, offset, len, nullptr, 0, hip_stream);
+    }
+    // A size above the file's is refused (CDC_EINVAL: offset past the end).
+    cdc_splice_stats_t truncate(Chunker &chunker, uint64_t size, void *hip_stream = nullptr) {
+        const uint64_t have = stat().size;
+        return splice(chunker, size, size < have ? have - size : 0, nullptr, 0, hip_stream);
+    }
     // read_file_complete (mod.rs:149-152): the size; > out_cap means nothing was written.
     int64_t read_complete_device(uint8_t *d_out, size_t out_cap, cdc_chunk_t *d_spans = nullptr,
                                  void *hip_stream = nullptr) {

@@ -106,6 +106,19 @@ int64_t cdc_debug_files_table_blocks(const cdc_files_t *fs);
  * entries and returns 6; CDC_EINVAL for n > 0 with NULL ms. */
 int cdc_debug_collect_split(double *ms, size_t n);
 
+/* The same for the last successful cdc_file_splice_device of this thread, all
+ * rounds together: [0] the span search and the window read (the range planner and
+ * the copy of the inserted bytes), [1] chunking, [2] resync, [3] SHA-256 and the
+ * put, [4] the table build.  Copies min(n, 5) entries and returns 5; CDC_EINVAL
+ * for n > 0 with NULL ms. */
+int cdc_debug_splice_split(double *ms, size_t n);
+
+/* What a file's span table holds besides the offsets and digests the reads
+ * return: per span the store's table slot and the arena offset resolved when the
+ * span was written (HOST arrays of cap entries, either nullable).  Returns the
+ * span count; a return > cap means nothing was written. */
+int64_t cdc_debug_file_slots(cdc_fh_t *fh, uint32_t *slots, uint64_t *locs, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,18 @@ afresh before every timed collect:
 (q) and (r) report the call's own wall time (every pass and host wait in it),
 the bytes moved, the move groups, and the ratio to (c) scaled to the bytes moved.
 
+Editing in place (skipped with --no-splice), on a layer of its own holding the
+1 GiB file of (d):
+
+  (s) cdc_file_splice_device overwriting 4 KiB in the middle of the file;
+  (t) the same inserting 4 KiB there;
+  (u) the same deleting 4 KiB there.
+
+Each reports ms, rounds, window_bytes, spans_removed / spans_inserted and the
+split of the last call into planner, chunk, resync, hash + put and table build.
+Compare with (d): writing the whole file again is the only other way to make
+the same edit.
+
 Prints one JSON line; --out also writes it to a file.
 """
 import argparse
@@ -308,6 +320,57 @@ def collect_legs(a, c, L, P, ch, buf, n, memcpy_ms):
     return res
 
 
+def splice_legs(a, c, L, P, ch, buf, n, k, sp, timed, med):
+    """Legs (s)-(u): a 4 KiB overwrite, insert and delete in the middle of the file
+    of (d), on a layer of its own.  Every iteration edits the file the one before
+    left (an insert grows it by 4 KiB, a delete shrinks it) with 4 KiB it has not
+    seen.  ms: HIP events around the call on its stream; wall_ms: the host's
+    clock around it; split_ms: cdc_debug_splice_split of the last call."""
+    import time
+
+    import numpy as np
+    import torch
+    from chunkfs_amd import _lib
+
+    edit = 4096
+    fresh = torch.empty(edit * 64, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    _lib.check(L.cdc_fill_splitmix64_device(P(fresh.data_ptr()), fresh.numel(), a.seed + 7, None))
+    fsys = c.FileSystem(store=c.ChunkStore(k + (1 << 14), n + 16 * k + (256 << 20)))
+    w = fsys.create_file("bench", ch)
+    assert L.cdc_file_write_device(w._fh, ch._h, P(buf.data_ptr()), n, None) == k
+    st = _lib.cdc_splice_stats_t()
+    turn = {"i": 0}
+    res = {}
+
+    def leg(name, rem, ins):
+        wall = []
+
+        def call():
+            src = fresh.data_ptr() + (turn["i"] % 64) * edit
+            turn["i"] += 1
+            t0 = time.perf_counter()
+            got = L.cdc_file_splice_device(w._fh, ch._h, n // 2 + 1234, rem, P(src) if ins else None, ins,
+                                           ctypes.byref(st), P(sp))
+            wall.append((time.perf_counter() - t0) * 1e3)
+            assert got >= 0, f"cdc_file_splice_device: {got}"
+
+        ms = timed(call)
+        wall = wall[a.warmup:]
+        split = (ctypes.c_double * 5)()
+        assert L.cdc_debug_splice_split(split, 5) == 5
+        res[name] = {"ms": med(ms), "ms_min_max": [min(ms), max(ms)], "wall_ms": float(np.median(wall)),
+                     "wall_ms_min_max": [min(wall), max(wall)], "rounds": st.rounds, "window_bytes": st.window_bytes,
+                     "spans_removed": st.spans_removed, "spans_inserted": st.spans_inserted,
+                     "bytes_new": st.bytes_new, "spans": fsys.stat(w)["spans"],
+                     "split_ms": dict(zip(("planner", "chunk", "resync", "hash_put", "table_build"), split))}
+
+    leg("s_overwrite_4k", edit, edit)
+    leg("t_insert_4k", 0, edit)
+    leg("u_delete_4k", edit, 0)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--bytes", type=int, default=1 << 30)
@@ -318,6 +381,7 @@ def main():
     ap.add_argument("--no-scrub", action="store_true", help="skip the scrub-stage legs (g)-(j)")
     ap.add_argument("--no-batch-write", action="store_true", help="skip the many-files legs (o)-(p)")
     ap.add_argument("--no-collect", action="store_true", help="skip the remove-and-collect legs (q)-(r)")
+    ap.add_argument("--no-splice", action="store_true", help="skip the edit-in-place legs (s)-(u)")
     ap.add_argument("--collect-iters", type=int, default=3)
     ap.add_argument("--scrub-iters", type=int, default=3)
     ap.add_argument("--scrub-groups", default="4096,64m;65536,256m;1048576,1024m",
@@ -518,6 +582,8 @@ def main():
         res["batch_write"] = batch_write_legs(a, c, L, P, ch)
     if not a.no_collect:
         res["collect"] = collect_legs(a, c, L, P, ch, buf, n, med(t_memcpy))
+    if not a.no_splice:
+        res["splice"] = splice_legs(a, c, L, P, ch, buf, n, k, sp, timed, med)
     line = json.dumps(res)
     print(line)
     if a.out:
