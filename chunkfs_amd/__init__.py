@@ -592,6 +592,28 @@ class SpliceStats:
         return "SpliceStats { " + ", ".join(f"{f}: {getattr(self, f)}" for f in self.FIELDS) + " }"
 
 
+class DiffStats:
+    """cdc_diff_stats_t of one FileSystem.diff, and the answer itself: .ranges
+    is the (n, 2) uint64 array of (offset, length); n_ranges their number;
+    bytes_differing the sum of the lengths; bytes_compared the bytes of each
+    file whose data was read; bytes_shared the bytes proved equal from the
+    tables alone; pieces the intervals the two tables cut [0, common) into."""
+
+    FIELDS = ("n_ranges", "bytes_differing", "bytes_compared", "bytes_shared", "pieces", "size_a", "size_b", "seconds")
+    __slots__ = FIELDS + ("ranges",)
+
+    def __init__(self, **kw):
+        for f in self.FIELDS:
+            setattr(self, f, float(kw.get(f, 0)) if f == "seconds" else int(kw.get(f, 0)))
+        self.ranges = np.zeros((0, 2), dtype=np.uint64)
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f in self.FIELDS}
+
+    def __repr__(self):
+        return "DiffStats { " + ", ".join(f"{f}: {getattr(self, f)}" for f in self.FIELDS) + " }"
+
+
 class CopyScrubber:
     """CopyScrubber (scrub.rs:85-114): every chunk moves to the target map under
     its own hash; the container keeps that one key."""
@@ -1076,6 +1098,46 @@ class FileSystem:
         if int(size) > have:
             raise CdcError(_lib.CDC_EINVAL, f"truncate: {size} is above the file's {have} bytes")
         return self.splice(handle, size, have - int(size), None, stream)
+
+    # -- snapshots and diffs ----------------------------------------------------------
+    def clone_file(self, src, dst, stream=None):
+        """cdc_files_clone: the new file `dst` with a deep copy of `src`'s span
+        table -- no put, no arena byte moved, store stats unchanged; an edit of
+        either file never shows through the other.  Returns the span count.
+        CdcError: CDC_ENOTFOUND for an unknown or stale src, CDC_EEXIST when
+        dst exists (dst == src included)."""
+        return check(lib().cdc_files_clone(self._h, src.encode(), dst.encode(), _ptr(stream)))
+
+    def diff_device(self, a, b, flags, d_ranges, cap, stats=None, stream=None):
+        """cdc_files_diff_device, raw: d_ranges is a device pointer to cap
+        cdc_chunk_t, stats a _lib.cdc_diff_stats_t or None.  Returns the number of
+        ranges; nothing is written when it exceeds cap."""
+        return check(lib().cdc_files_diff_device(a._fh, b._fh, int(flags), _ptr(d_ranges), int(cap),
+                                                 ctypes.byref(stats) if stats is not None else None, _ptr(stream)))
+
+    def diff(self, a, b, tables_only=False, stream=None):
+        """Where the files behind two handles differ: DiffStats, whose .ranges is
+        the (n, 2) uint64 array of maximal runs (offset, length) -- ascending,
+        never touching -- over [0, max(size_a, size_b)); bytes past the shorter
+        file count as differing.  Pieces whose spans name one store slot at one
+        offset are equal by construction and not read.  tables_only: no data is
+        read at all and every piece that is not shared counts as differing (a
+        superset: the changed-chunks list of a backup)."""
+        import torch
+        dev = f"cuda:{self.device}"
+        flags = _lib.CDC_DIFF_TABLES_ONLY if tables_only else 0
+        s = _lib.cdc_diff_stats_t()
+        cap = 1024
+        while True:
+            out = torch.empty((cap, 2), dtype=torch.int64, device=dev)
+            torch.cuda.synchronize(dev)
+            n = self.diff_device(a, b, flags, out.data_ptr(), cap, s, stream)
+            if n <= cap:
+                break
+            cap = n  # the exact count: the files cannot change in between
+        r = DiffStats(n_ranges=s.ranges, **{f: getattr(s, f) for f in DiffStats.FIELDS[1:]})
+        r.ranges = out[:n].cpu().numpy().view(np.uint64).reshape(n, 2)
+        return r
 
     # -- reads ----------------------------------------------------------------------
     def read_complete_device(self, handle, d_out, out_cap, d_spans=None, stream=None):

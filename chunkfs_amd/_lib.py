@@ -43,6 +43,7 @@ EXPORTS = [
     "cdc_files_get_to_dedup_ratio", "cdc_file_verify_device", "cdc_store_size_distribution_device",
     "cdc_files_remove", "cdc_files_collect", "cdc_store_retain_device",
     "cdc_file_splice_device",
+    "cdc_files_clone", "cdc_files_diff_device",
     "cdc_fill_splitmix64_device", "cdc_version", "cdc_abi_version",
 ]
 # include/chunkfs_amd_debug.h (diagnostics, not part of the drop-in boundary)
@@ -113,6 +114,16 @@ class cdc_splice_stats_t(ctypes.Structure):
                 ("size_before", ctypes.c_uint64), ("size_after", ctypes.c_uint64),
                 ("bytes_new", ctypes.c_uint64), ("window_bytes", ctypes.c_uint64),
                 ("rounds", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+class cdc_diff_stats_t(ctypes.Structure):
+    _fields_ = [("ranges", ctypes.c_uint64), ("bytes_differing", ctypes.c_uint64),
+                ("bytes_compared", ctypes.c_uint64), ("bytes_shared", ctypes.c_uint64),
+                ("pieces", ctypes.c_uint64), ("size_a", ctypes.c_uint64), ("size_b", ctypes.c_uint64),
+                ("seconds", ctypes.c_double)]
+
+
+CDC_DIFF_TABLES_ONLY = 1
 
 
 class cdc_timing_t(ctypes.Structure):
@@ -303,6 +314,10 @@ def lib():
     L.cdc_file_splice_device.argtypes = [P, P, ctypes.c_uint64, ctypes.c_uint64, P, sz,
                                          ctypes.POINTER(cdc_splice_stats_t), P]
     L.cdc_file_splice_device.restype = ctypes.c_int64
+    L.cdc_files_clone.argtypes = [P, ctypes.c_char_p, ctypes.c_char_p, P]
+    L.cdc_files_clone.restype = ctypes.c_int64
+    L.cdc_files_diff_device.argtypes = [P, P, ctypes.c_uint32, P, sz, ctypes.POINTER(cdc_diff_stats_t), P]
+    L.cdc_files_diff_device.restype = ctypes.c_int64
     L.cdc_debug_splice_split.argtypes = [ctypes.POINTER(ctypes.c_double), sz]
     L.cdc_debug_splice_split.restype = ctypes.c_int
     L.cdc_debug_file_slots.argtypes = [P, P, P, sz]

@@ -34,8 +34,18 @@
 // sums, and a gather writes the new table with true offsets.  verify
 // (src/bench/mod.rs:241-275) is the read chain with the store's compare kernel
 // as its last step.
+//
+// diff (cdc_files_diff_device; not in the reference, DESIGN.md "Snapshots and
+// diffs") compares two files of the layer.  The boundaries of both tables are
+// ranked into pieces, each inside one span of either file; a piece whose spans
+// name one slot at one offset is one arena address and is skipped; the others
+// become a piece list for the store's diff_mask_kernel, one bit per byte; a
+// wave per tile turns the mask into run starts and ends, a scan ranks them and
+// the emit maps (tile, bit) back to file offsets.  The arithmetic is
+// diff_plan.hpp's.
 #include "files.hpp"
 
+#include "diff_plan.hpp"
 #include "splice_plan.hpp"
 
 namespace cdc {
@@ -689,6 +699,257 @@ __global__ __launch_bounds__(kFlThreads) void collect_remap_kernel(const Collect
     sg.loc[j] = new_loc[ns];
 }
 
+// ---- diff ---------------------------------------------------------------------------
+static_assert(kDiffTile == kStoreTile && kDiffAlign == kStoreAlign, "diff_plan.hpp cuts the store's tiles");
+constexpr int kFlWaves = kFlThreads / 64;
+constexpr unsigned kDiffMaxBlocks = 1u << 18;  // waves (threads of the fix-up) past this stride
+
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+#pragma unroll
+    for (int k = 1; k < 64; k <<= 1) v += __shfl_xor(v, k);
+    return v;
+}
+// Exclusive prefix sum over the wave.
+__device__ __forceinline__ uint32_t wave_excl(uint32_t v, uint32_t lane) {
+    uint32_t inc = v;
+#pragma unroll
+    for (int k = 1; k < 64; k <<= 1) {
+        const uint32_t o = __shfl_up(inc, k);
+        if (lane >= (uint32_t)k) inc += o;
+    }
+    return inc - v;
+}
+
+// Stage 1a: one thread per span boundary of either table.
+__global__ __launch_bounds__(kFlThreads) void diff_flag_kernel(DiffSide a, DiffSide b, uint64_t common, uint64_t nc,
+                                                               uint64_t *cand) {
+    const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nc) return;
+    uint64_t x;
+    cand[c] = diff_opens(a.off, a.n, b.off, b.n, common, c, &x) ? 1 : 0;
+}
+
+// Stage 1b, after the scan: the merge by ranking.
+__global__ __launch_bounds__(kFlThreads) void diff_piece_kernel(DiffSide a, DiffSide b, uint64_t common, uint64_t nc,
+                                                                const uint64_t *__restrict__ cand, uint64_t *pstart,
+                                                                uint32_t *pia, uint32_t *pib) {
+    const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nc) return;
+    uint64_t x;
+    if (!diff_opens(a.off, a.n, b.off, b.n, common, c, &x)) return;
+    uint32_t ia, ib;
+    const uint64_t p = diff_rank(a.off, a.n, b.off, b.n, cand, c, x, &ia, &ib);
+    pstart[p] = x;
+    pia[p] = ia;
+    pib[p] = ib;
+}
+
+__device__ __forceinline__ bool piece_shared(const DiffSide &a, const DiffSide &b, const uint32_t *__restrict__ pia,
+                                             const uint32_t *__restrict__ pib, uint64_t p) {
+    const uint32_t ia = pia[p], ib = pib[p];
+    return diff_shared(a.slot[ia], a.off[ia], b.slot[ib], b.off[ib]);
+}
+
+// Stage 2a: the sharing rule.  pflag = the piece is compared (exact), or it
+// begins a run of pieces that are not shared (tables only); acc[0] += the bytes
+// of the pieces that are not shared.  Threads past the piece count write 0, so
+// the scan runs over max_pieces.
+__global__ __launch_bounds__(kFlThreads) void diff_share_kernel(DiffSide a, DiffSide b, uint64_t common,
+                                                                const uint64_t *__restrict__ n_pieces,
+                                                                const uint64_t *__restrict__ pstart,
+                                                                const uint32_t *__restrict__ pia,
+                                                                const uint32_t *__restrict__ pib, uint64_t max_pieces,
+                                                                bool tables_only, uint64_t *pflag,
+                                                                unsigned long long *acc) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t P = *n_pieces;
+    uint64_t bytes = 0, flag = 0;
+    if (p < P && !piece_shared(a, b, pia, pib, p)) {
+        bytes = (p + 1 < P ? pstart[p + 1] : common) - pstart[p];
+        flag = !tables_only || p == 0 || piece_shared(a, b, pia, pib, p - 1);
+    }
+    if (p < max_pieces) pflag[p] = flag;
+    bytes = wave_sum(bytes);
+    if ((threadIdx.x & 63) == 0 && bytes) atomicAdd(&acc[0], (unsigned long long)bytes);
+}
+
+// Stage 2b (exact): the compared pieces, compacted.  Entries from the compared
+// count on are written empty, so the tile scan runs over max_pieces.
+__global__ __launch_bounds__(kFlThreads) void diff_compact_kernel(DiffSide a, DiffSide b, uint64_t common,
+                                                                  uint64_t arena, DiffScratch w) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= w.max_pieces) return;
+    const uint64_t P = *w.n_pieces;
+    const uint64_t C = *w.n_cmp;
+    if (p >= C) {
+        w.cp[p] = StorePiece{0, 0, 0};
+        w.tstart[p] = 0;
+    }
+    if (p >= P || piece_shared(a, b, w.pia, w.pib, p)) return;
+    const uint64_t c = w.pflag[p], x = w.pstart[p], end = p + 1 < P ? w.pstart[p + 1] : common;
+    const uint32_t ia = w.pia[p], ib = w.pib[p];
+    const StorePiece pc{arena + a.loc[ia] + (x - a.off[ia]), arena + b.loc[ib] + (x - b.off[ib]), end - x};
+    w.cp[c] = pc;
+    w.tstart[c] = diff_tiles(pc.dst, pc.len);
+    w.cx[c] = x;
+    w.cflag[c] = (p > 0 && !piece_shared(a, b, w.pia, w.pib, p - 1) ? 1u : 0u) |
+                 (end == common && a.size != b.size ? 2u : 0u);
+}
+
+__device__ __forceinline__ uint64_t mask_bit(const uint64_t *__restrict__ mask, uint64_t tile, uint32_t b) {
+    return (mask[tile * kDiffTileWords + b / 64] >> (b % 64)) & 1;
+}
+// Does the last byte of compared piece c differ?
+__device__ __forceinline__ uint64_t last_bit_of(const DiffScratch &w, uint64_t c) {
+    uint64_t k;
+    uint32_t b;
+    diff_last_bit((uint32_t)(w.cp[c].dst & (kDiffAlign - 1)), w.cp[c].len, &k, &b);
+    return mask_bit(w.mask, w.tstart[c] + k, b);
+}
+
+// Tile T of the tile scan as the run passes see it; *x = its piece's first byte
+// in the file.  The same in every lane.
+__device__ __forceinline__ DiffTile diff_tile_at(const DiffScratch &w, uint64_t C, uint64_t T, uint64_t *x) {
+    uint64_t lo = 0, hi = w.max_pieces;
+    while (hi - lo > 1) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (w.tstart[mid] <= T) lo = mid;
+        else hi = mid;
+    }
+    const uint64_t c = lo;
+    const StorePiece pc = w.cp[c];
+    DiffTile t;
+    t.m = (uint32_t)(pc.dst & (kDiffAlign - 1));
+    t.len = pc.len;
+    t.k = T - w.tstart[c];
+    t.head_joined = t.k == 0 && (w.cflag[c] & 1u) && last_bit_of(w, c - 1);
+    t.tail_joined = false;
+    if (t.k + 1 == diff_tiles(pc.dst, pc.len))
+        t.tail_joined = (w.cflag[c] & 2u) ||
+                        (c + 1 < C && (w.cflag[c + 1] & 1u) &&
+                         mask_bit(w.mask, w.tstart[c + 1], (uint32_t)(w.cp[c + 1].dst & (kDiffAlign - 1))));
+    *x = w.cx[c];
+    return t;
+}
+
+// Stage 4a: one wave per tile, one lane per mask word.  tcount[T] = the runs
+// that begin in tile T (0 from the tile total on, so the scan runs over
+// max_tiles); acc[1] += the set bits.
+__global__ __launch_bounds__(kFlThreads) void diff_count_kernel(DiffScratch w) {
+    const uint64_t TT = *w.n_tiles, C = *w.n_cmp;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t wave0 = (uint64_t)blockIdx.x * kFlWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t nwaves = (uint64_t)gridDim.x * kFlWaves;
+    for (uint64_t T = wave0; T < w.max_tiles; T += nwaves) {
+        if (T >= TT) {
+            if (lane == 0) w.tcount[T] = 0;
+            continue;
+        }
+        uint64_t x;
+        const DiffTile t = diff_tile_at(w, C, T, &x);
+        const uint64_t word = w.mask[T * kDiffTileWords + lane];
+        uint64_t prev = __shfl_up(word, 1) >> 63;
+        if (lane == 0) prev = t.k ? w.mask[T * kDiffTileWords - 1] >> 63 : 0;
+        const uint64_t starts = wave_sum((uint64_t)__popcll(diff_tile_starts(t, lane, word, prev)));
+        const uint64_t bits = wave_sum((uint64_t)__popcll(word));
+        if (lane == 0) {
+            w.tcount[T] = starts;
+            if (bits) atomicAdd(&w.acc[1], (unsigned long long)bits);
+        }
+    }
+}
+
+// The count of the whole answer and the stats, by one thread after the last
+// scan.  S = runs that begin below `common`.
+__global__ void diff_total_kernel(DiffSide a, DiffSide b, uint64_t common, bool tables_only, DiffScratch w,
+                                  unsigned long long *h_out) {
+    const uint64_t P = *w.n_pieces;
+    const uint64_t C = *w.n_cmp;  // tables only: S
+    const bool tail = a.size != b.size;
+    const uint64_t maxsz = a.size > b.size ? a.size : b.size;
+    uint64_t S, joined = 0, differing;
+    if (tables_only) {
+        S = C;
+        joined = tail && P && !piece_shared(a, b, w.pia, w.pib, P - 1);
+        differing = w.acc[0];
+    } else {
+        S = *w.n_starts;
+        joined = tail && C && (w.cflag[C - 1] & 2u) && last_bit_of(w, C - 1);
+        differing = w.acc[1];
+    }
+    const uint64_t R = S + (tail && !joined ? 1 : 0);
+    w.acc[2] = R;
+    w.acc[3] = joined;
+    h_out[0] = R;
+    h_out[1] = differing + (maxsz - common);
+    h_out[2] = tables_only ? 0 : w.acc[0];
+    h_out[3] = common - w.acc[0];
+    h_out[4] = P;
+}
+
+// The tail [common, max): a range of its own, or the end of the run it continues.
+__device__ __forceinline__ void diff_emit_tail(const DiffSide &a, const DiffSide &b, uint64_t common,
+                                               const unsigned long long *acc, cdc_chunk_pod *ranges) {
+    if (a.size == b.size) return;
+    const uint64_t R = acc[2], maxsz = a.size > b.size ? a.size : b.size;
+    if (acc[3]) ranges[R - 1].length = maxsz;
+    else ranges[R - 1] = cdc_chunk_pod{common, maxsz};
+}
+
+// Stage 4b (exact): run r gets its first byte from the thread that holds its
+// start bit and, in `length`, its END from the thread that holds its end bit;
+// diff_fix_kernel turns ends into lengths.  Nothing is written when the count
+// exceeds cap.
+__global__ __launch_bounds__(kFlThreads) void diff_emit_kernel(DiffSide a, DiffSide b, uint64_t common, DiffScratch w,
+                                                               cdc_chunk_pod *ranges, uint64_t cap) {
+    if (w.acc[2] > cap) return;
+    const uint64_t TT = *w.n_tiles, C = *w.n_cmp;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t wave0 = (uint64_t)blockIdx.x * kFlWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t nwaves = (uint64_t)gridDim.x * kFlWaves;
+    if (blockIdx.x == 0 && threadIdx.x == 0) diff_emit_tail(a, b, common, w.acc, ranges);
+    for (uint64_t T = wave0; T < TT; T += nwaves) {
+        uint64_t x;
+        const DiffTile t = diff_tile_at(w, C, T, &x);
+        const uint64_t word = w.mask[T * kDiffTileWords + lane];
+        uint64_t prev = __shfl_up(word, 1) >> 63, next = __shfl_down(word, 1) & 1;
+        if (lane == 0) prev = t.k ? w.mask[T * kDiffTileWords - 1] >> 63 : 0;
+        if (lane == 63) next = t.k + 1 < diff_tiles(t.m, t.len) ? w.mask[(T + 1) * kDiffTileWords] & 1 : 0;
+        uint64_t starts = diff_tile_starts(t, lane, word, prev), ends = diff_tile_ends(t, lane, word, next);
+        const uint64_t open = __shfl(lane == 0 ? diff_tile_open(t, word, starts) : 0, 0);
+        uint64_t rs = w.tcount[T] + wave_excl((uint32_t)__popcll(starts), lane);
+        uint64_t re = w.tcount[T] - open + wave_excl((uint32_t)__popcll(ends), lane);
+        for (; starts; starts &= starts - 1)
+            ranges[rs++].offset = diff_file_offset(x, t.m, t.k, lane * 64 + (uint32_t)__builtin_ctzll(starts));
+        for (; ends; ends &= ends - 1)
+            ranges[re++].length = diff_file_offset(x, t.m, t.k, lane * 64 + (uint32_t)__builtin_ctzll(ends)) + 1;
+    }
+}
+
+// The same for CDC_DIFF_TABLES_ONLY: the runs of pieces that are not shared.
+__global__ __launch_bounds__(kFlThreads) void diff_emit_tables_kernel(DiffSide a, DiffSide b, uint64_t common,
+                                                                      DiffScratch w, cdc_chunk_pod *ranges,
+                                                                      uint64_t cap) {
+    if (w.acc[2] > cap) return;
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p == 0) diff_emit_tail(a, b, common, w.acc, ranges);
+    const uint64_t P = *w.n_pieces;
+    if (p >= P || piece_shared(a, b, w.pia, w.pib, p)) return;
+    const bool start = p == 0 || piece_shared(a, b, w.pia, w.pib, p - 1);
+    const bool end = p + 1 < P ? piece_shared(a, b, w.pia, w.pib, p + 1) : a.size == b.size;
+    const uint64_t r = w.pflag[p];  // runs that begin before piece p
+    if (start) ranges[r].offset = w.pstart[p];
+    if (end) ranges[r + (start ? 1 : 0) - 1].length = p + 1 < P ? w.pstart[p + 1] : common;
+}
+
+__global__ __launch_bounds__(kFlThreads) void diff_fix_kernel(const unsigned long long *__restrict__ acc,
+                                                              cdc_chunk_pod *ranges, uint64_t cap) {
+    const uint64_t R = acc[2];
+    if (R > cap) return;
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < R; r += (uint64_t)gridDim.x * blockDim.x)
+        ranges[r].length -= ranges[r].offset;
+}
+
 }  // namespace
 
 hipError_t launch_splice_start(const uint64_t *off, uint64_t n, uint64_t offset, unsigned long long *h_out,
@@ -732,6 +993,50 @@ hipError_t launch_files_remap(const CollectSeg *d_seg, const uint64_t *d_first, 
                               uint64_t slots, const uint32_t *map, const uint64_t *new_loc, hipStream_t s) {
     if (!m) return hipSuccess;
     collect_remap_kernel<<<grid_of(m), kFlThreads, 0, s>>>(d_seg, d_first, nfiles, m, slots, map, new_loc);
+    return hipGetLastError();
+}
+
+hipError_t launch_files_diff(const DiffSide &a, const DiffSide &b, uint64_t arena, bool tables_only,
+                             const DiffScratch &w, cdc_chunk_pod *d_ranges, uint64_t cap, unsigned long long *h_out,
+                             hipStream_t s) {
+    const uint64_t common = a.size < b.size ? a.size : b.size, maxsz = a.size < b.size ? b.size : a.size;
+    const uint64_t nc = diff_candidates(a.n, b.n), mp = w.max_pieces;
+    hipError_t e = hipMemsetAsync(w.acc, 0, 4 * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    // 1. Ranks: the pieces in file order.
+    diff_flag_kernel<<<grid_of(nc), kFlThreads, 0, s>>>(a, b, common, nc, w.cand);
+    if ((e = launch_store_scan(w.cand, nc, w.bs_c, nullptr, s)) != hipSuccess) return e;
+    diff_piece_kernel<<<grid_of(nc), kFlThreads, 0, s>>>(a, b, common, nc, w.cand, w.pstart, w.pia, w.pib);
+    // 2. The sharing rule, and the compared pieces as a piece list.
+    diff_share_kernel<<<grid_of(mp), kFlThreads, 0, s>>>(a, b, common, w.n_pieces, w.pstart, w.pia, w.pib, mp,
+                                                         tables_only, w.pflag, w.acc);
+    if ((e = launch_store_scan(w.pflag, mp, w.bs_p, nullptr, s)) != hipSuccess) return e;
+    // A run holds a byte or more: the count is at most half the bytes, rounded up.
+    const uint64_t most = maxsz / 2 + 1, fix = cap < most ? cap : most;
+    const uint64_t fix_blocks = (fix + kFlThreads - 1) / kFlThreads;
+    const unsigned fix_grid = (unsigned)(fix_blocks < kDiffMaxBlocks ? fix_blocks : kDiffMaxBlocks);
+    if (tables_only) {
+        diff_total_kernel<<<1, 1, 0, s>>>(a, b, common, true, w, h_out);
+        if (!cap) return hipGetLastError();
+        diff_emit_tables_kernel<<<grid_of(mp), kFlThreads, 0, s>>>(a, b, common, w, d_ranges, cap);
+        diff_fix_kernel<<<fix_grid, kFlThreads, 0, s>>>(w.acc, d_ranges, cap);
+        return hipGetLastError();
+    }
+    diff_compact_kernel<<<grid_of(mp), kFlThreads, 0, s>>>(a, b, common, arena, w);
+    if ((e = launch_store_scan(w.tstart, mp, w.bs_t, nullptr, s)) != hipSuccess) return e;
+    // 3. One bit per compared byte.
+    if ((e = launch_store_diff_mask(w.cp, w.tstart, mp, w.max_tiles, w.n_tiles, w.mask, s)) !=
+        hipSuccess)
+        return e;
+    // 4. Runs: starts per tile, their scan, the emit.
+    const uint64_t blocks = (w.max_tiles + kFlWaves - 1) / kFlWaves;
+    const unsigned tile_grid = (unsigned)(blocks < kDiffMaxBlocks ? blocks : kDiffMaxBlocks);
+    diff_count_kernel<<<tile_grid, kFlThreads, 0, s>>>(w);
+    if ((e = launch_store_scan(w.tcount, w.max_tiles, w.bs_r, nullptr, s)) != hipSuccess) return e;
+    diff_total_kernel<<<1, 1, 0, s>>>(a, b, common, false, w, h_out);
+    if (!cap) return hipGetLastError();
+    diff_emit_kernel<<<tile_grid, kFlThreads, 0, s>>>(a, b, common, w, d_ranges, cap);
+    diff_fix_kernel<<<fix_grid, kFlThreads, 0, s>>>(w.acc, d_ranges, cap);
     return hipGetLastError();
 }
 

@@ -191,6 +191,46 @@ hipError_t launch_splice_build(const SpanTable &old, uint64_t n, uint64_t size_o
                                uint64_t m, uint64_t *val, uint64_t *block_sums, unsigned long long *d_stat,
                                unsigned long long *h_total, hipStream_t s);
 
+// ---- diff (cdc_files_diff_device; the arithmetic: diff_plan.hpp) -------------------
+// One file of the two: its table and size.  Both have spans (common > 0).
+struct DiffSide {
+    const uint64_t *off;
+    const uint64_t *loc;
+    const uint32_t *slot;
+    uint64_t n;
+    uint64_t size;
+};
+// Device scratch, sized from host-side bounds: nc = na + nb + 2 candidates,
+// max_pieces = na + nb, max_tiles = common / kStoreTile + 2 * max_pieces (0 for
+// CDC_DIFF_TABLES_ONLY: tcount and mask are not touched then).
+struct DiffScratch {
+    uint64_t *cand;    // [nc] do the candidates open a piece; scanned
+    uint64_t *pstart;  // [max_pieces] the pieces in file order: first byte
+    uint32_t *pia;     // [max_pieces] A's span
+    uint32_t *pib;     // [max_pieces] B's span
+    uint64_t *pflag;   // [max_pieces] exact: the piece is compared; tables only: it begins a run; scanned
+    StorePiece *cp;    // [max_pieces] the compared pieces: {A's address, B's address, length}
+    uint64_t *tstart;  // [max_pieces] their tile counts; scanned
+    uint64_t *cx;      // [max_pieces] their first byte in the file
+    uint32_t *cflag;   // [max_pieces] bit 0: the piece before it in the file is compared too; bit 1: it ends at
+                       // `common` and the files differ in size
+    uint64_t *tcount;  // [max_tiles] run starts per tile; scanned
+    uint64_t *mask;    // [64 * max_tiles]
+    uint64_t *bs_c, *bs_p, *bs_t, *bs_r;  // block sums of the four scans: store_scan_blocks(count) + 1 each
+    // Their totals, the last entry of each: pieces, compared pieces (tables only: runs below `common`),
+    // tiles, runs that begin below `common`.
+    const uint64_t *n_pieces, *n_cmp, *n_tiles, *n_starts;
+    unsigned long long *acc;  // [4]: bytes of the pieces not shared, differing bytes below `common`, ranges,
+                              // whether the tail continues a run
+    uint64_t max_pieces, max_tiles;
+};
+// The whole device path, no host wait inside.  h_out (pinned): [0] ranges, [1]
+// bytes_differing, [2] bytes_compared, [3] bytes_shared, [4] pieces.  d_ranges
+// receives the ranges when their number is <= cap, and is left alone otherwise.
+hipError_t launch_files_diff(const DiffSide &a, const DiffSide &b, uint64_t arena, bool tables_only,
+                             const DiffScratch &w, cdc_chunk_pod *d_ranges, uint64_t cap, unsigned long long *h_out,
+                             hipStream_t s);
+
 // ---- get_to_dedup_ratio (file_layer.rs:208-268) -----------------------------------
 // Step 1: the unique list over spans [0, m), m = n - 1, from the distribution's
 // first-occurrence flags and scan: uidx[j] = span index of the j-th distinct

@@ -16,6 +16,7 @@
 #include "../../include/chunkfs_amd_debug.h"
 #include "engine.hpp"
 #include "files.hpp"
+#include "diff_plan.hpp"
 #include "splice_plan.hpp"
 #include "store.hpp"
 #include "store_internal.hpp"
@@ -129,6 +130,10 @@ struct cdc_files {
     uint8_t *s_win = nullptr;
     unsigned long long *h_sp = nullptr;  // pinned: start {i0, off[i0]}; resync {k, j, e_k}
     unsigned long long *d_sp = nullptr;  // the smallest chunk that resyncs
+    // cdc_files_diff_device: one device block carved into the DiffScratch arrays, and the result words
+    uint64_t df_bytes = 0;
+    uint8_t *df_mem = nullptr;
+    unsigned long long *h_df = nullptr;  // pinned: ranges, bytes_differing, bytes_compared, bytes_shared, pieces
 };
 
 struct cdc_fh {
@@ -323,6 +328,8 @@ void release(cdc_files *fs) {
     (void)hipFree(fs->s_win);
     (void)hipHostFree(fs->h_sp);
     (void)hipFree(fs->d_sp);
+    (void)hipFree(fs->df_mem);
+    (void)hipHostFree(fs->h_df);
     delete fs;
 }
 
@@ -744,9 +751,166 @@ int64_t splice(cdc_fh *fh, cdc_handle_t *chunker, uint64_t offset, uint64_t remo
     return (int64_t)m;
 }
 
+// ---- diff -----------------------------------------------------------------------
+// The diff's scratch for two tables of na and nb spans: every size is a bound
+// the host has before the first launch.  A piece starts at a span boundary, so
+// there are at most na + nb of them; a compared piece adds at most two ragged
+// tiles to its whole ones.  The mask is 64 words per tile: one bit per compared
+// byte plus, per piece, the two tiles' worth that its ends may leave unused.
+int grow_diff(cdc_files *fs, uint64_t na, uint64_t nb, uint64_t common, bool tables_only, cdc::DiffScratch *w) {
+    if (!fs->h_df) FL_TRY(hipHostMalloc(&fs->h_df, 8 * sizeof(unsigned long long)));
+    const uint64_t nc = cdc::diff_candidates(na, nb), mp = na + nb;
+    const uint64_t mt = tables_only ? 0 : common / cdc::kStoreTile + 2 * mp;
+    const uint64_t words = 4 /* acc */ + nc + 4 * mp /* pstart, pflag, tstart, cx */ + 3 * mp /* cp */ +
+                           mt * (1 + cdc::kDiffTileWords) + cdc::store_scan_blocks(nc) + 1 +
+                           2 * (cdc::store_scan_blocks(mp) + 1) + cdc::store_scan_blocks(mt) + 1;
+    const uint64_t bytes = words * 8 + 3 * mp * 4 /* pia, pib, cflag */;
+    if (fs->df_bytes < bytes) {
+        (void)hipFree(fs->df_mem);
+        fs->df_mem = nullptr;
+        fs->df_bytes = 0;
+        const uint64_t cap = bytes + bytes / 8;
+        FL_TRY(hipMalloc(&fs->df_mem, cap));
+        fs->df_bytes = cap;
+    }
+    uint64_t *p = reinterpret_cast<uint64_t *>(fs->df_mem);
+    auto take = [&p](uint64_t n) {
+        uint64_t *r = p;
+        p += n;
+        return r;
+    };
+    static_assert(sizeof(cdc::StorePiece) == 24, "three words");
+    w->acc = reinterpret_cast<unsigned long long *>(take(4));
+    w->cand = take(nc);
+    w->pstart = take(mp);
+    w->pflag = take(mp);
+    w->tstart = take(mp);
+    w->cx = take(mp);
+    w->cp = reinterpret_cast<cdc::StorePiece *>(take(3 * mp));
+    w->tcount = take(mt);
+    w->mask = take(mt * cdc::kDiffTileWords);
+    w->bs_c = take(cdc::store_scan_blocks(nc) + 1);
+    w->bs_p = take(cdc::store_scan_blocks(mp) + 1);
+    w->bs_t = take(cdc::store_scan_blocks(mp) + 1);
+    w->bs_r = take(cdc::store_scan_blocks(mt) + 1);
+    w->n_pieces = w->bs_c + cdc::store_scan_blocks(nc);
+    w->n_cmp = w->bs_p + cdc::store_scan_blocks(mp);
+    w->n_tiles = w->bs_t + cdc::store_scan_blocks(mp);
+    w->n_starts = w->bs_r + cdc::store_scan_blocks(mt);
+    uint32_t *q = reinterpret_cast<uint32_t *>(p);
+    w->pia = q;
+    w->pib = q + mp;
+    w->cflag = q + 2 * mp;
+    w->max_pieces = mp;
+    w->max_tiles = mt;
+    return CDC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t cdc_files_clone(cdc_files_t *fs, const char *src, const char *dst, void *hip_stream) {
+    if (!fs || !src || !dst) return fail(CDC_EINVAL, "cdc_files_clone: NULL argument");
+    auto it = fs->files.find(src);
+    if (it == fs->files.end()) return fail(CDC_ENOTFOUND, std::string("file layer: no file named '") + src + "'");
+    const FileRec *from = it->second;
+    const cdc::StoreView v = cdc::store_view(fs->store);
+    if (from->n && from->epoch != v.epoch)
+        return fail(CDC_ENOTFOUND, std::string("file layer: the store was cleared since '") + src + "' was written");
+    if (fs->files.count(dst)) return fail(CDC_EEXIST, std::string("file layer: '") + dst + "' already exists");
+    FileRec made = *from;  // n, size, epoch, min_len, zeros; the table is its own
+    made.t = cdc::SpanTable{};
+    made.cap = 0;
+    if (from->n) {
+        FL_TRY(hipSetDevice(v.device));
+        hipStream_t s = stream_of(fs, hip_stream);
+        uint64_t cap = kTableMinCap;
+        while (cap < from->n) cap *= 2;
+        hipError_t e = fs->pool.take(cap, &made.t);
+        if (e != hipSuccess) {
+            cdc::set_error(std::string("cdc_files_clone: span table: ") + hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE;
+        }
+        const uint64_t n = from->n;
+        e = hipMemcpyAsync(made.t.off, from->t.off, (n + 1) * 8, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(made.t.digest, from->t.digest, n * 32, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(made.t.loc, from->t.loc, n * 8, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(made.t.slot, from->t.slot, n * 4, hipMemcpyDeviceToDevice, s);
+        const hipError_t hs = hipStreamSynchronize(s);  // also on failure: nothing queued still writes the table
+        if (e == hipSuccess) e = hs;
+        if (e != hipSuccess) {
+            fs->pool.give(made.t, cap);
+            cdc::set_error(std::string("cdc_files_clone: table copy: ") + hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE;
+        }
+        made.cap = cap;
+    }
+    fs->files[dst] = new FileRec(made);
+    return (int64_t)made.n;
+}
+
+int64_t cdc_files_diff_device(cdc_fh_t *a, cdc_fh_t *b, uint32_t flags, cdc_chunk_t *d_ranges, size_t cap,
+                              cdc_diff_stats_t *stats, void *hip_stream) {
+    const auto t0 = std::chrono::steady_clock::now();
+    // Everything that can refuse, before any device work.
+    if (flags & ~(uint32_t)CDC_DIFF_TABLES_ONLY)
+        return fail(CDC_EINVAL, "cdc_files_diff_device: unknown flag bits " + std::to_string(flags));
+    if (!a || !b) return fail(CDC_EINVAL, "cdc_files_diff_device: NULL file handle");
+    if (cap && !d_ranges) return fail(CDC_EINVAL, "cdc_files_diff_device: NULL destination");
+    if (a->fs && b->fs && a->fs != b->fs)
+        return fail(CDC_EINVAL, "cdc_files_diff_device: the handles belong to two file layers");
+    FileRec *fa = nullptr, *fb = nullptr;
+    int rc = lookup(a, true, &fa);
+    if (rc) return rc;
+    if ((rc = lookup(b, true, &fb)) != CDC_OK) return rc;
+    cdc_files *fs = a->fs;
+    {
+        cdc::ScrubView sv;
+        bool stale = false;
+        if (cdc::store_scrub_view(fs->store, &sv, &stale))
+            return fail(CDC_ENOTSUP, "cdc_files_diff_device: the store holds target-kind containers (scrubbed); "
+                                     "not supported");
+    }
+    const bool tables_only = (flags & CDC_DIFF_TABLES_ONLY) != 0;
+    const uint64_t common = fa->size < fb->size ? fa->size : fb->size;
+    const uint64_t maxsz = fa->size < fb->size ? fb->size : fa->size;
+    const cdc::StoreView v = cdc::store_view(fs->store);
+    FL_TRY(hipSetDevice(v.device));
+    hipStream_t s = stream_of(fs, hip_stream);
+    cdc_diff_stats_t r{};
+    r.size_a = fa->size;
+    r.size_b = fb->size;
+    if (!common) {  // no byte to place in both files: the answer is the tail
+        r.ranges = maxsz ? 1 : 0;
+        r.bytes_differing = maxsz;
+        if (r.ranges && r.ranges <= cap) {
+            const cdc_chunk_t tail{0, maxsz};
+            FL_TRY(hipMemcpyAsync(d_ranges, &tail, sizeof tail, hipMemcpyHostToDevice, s));
+            FL_TRY(hipStreamSynchronize(s));
+        }
+    } else {
+        cdc::DiffScratch w{};
+        if ((rc = grow_diff(fs, fa->n, fb->n, common, tables_only, &w)) != CDC_OK) return rc;
+        const cdc::DiffSide da{fa->t.off, fa->t.loc, fa->t.slot, fa->n, fa->size};
+        const cdc::DiffSide db{fb->t.off, fb->t.loc, fb->t.slot, fb->n, fb->size};
+        const hipError_t e = cdc::launch_files_diff(da, db, (uint64_t)(uintptr_t)v.arena, tables_only, w,
+                                                    reinterpret_cast<cdc::cdc_chunk_pod *>(d_ranges), cap, fs->h_df, s);
+        const hipError_t hs = hipStreamSynchronize(s);  // the one wait of the call
+        if (e != hipSuccess || hs != hipSuccess) {
+            cdc::set_error(std::string("cdc_files_diff_device: ") + hipGetErrorString(e != hipSuccess ? e : hs));
+            return CDC_EDEVICE;
+        }
+        r.ranges = fs->h_df[0];
+        r.bytes_differing = fs->h_df[1];
+        r.bytes_compared = fs->h_df[2];
+        r.bytes_shared = fs->h_df[3];
+        r.pieces = fs->h_df[4];
+    }
+    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) *stats = r;
+    return (int64_t)r.ranges;
+}
 
 int cdc_files_create(cdc_store_t *store, size_t seg_size, cdc_files_t **out) {
     if (!out) return fail(CDC_EINVAL, "cdc_files_create: out is NULL");

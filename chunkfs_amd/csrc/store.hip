@@ -430,6 +430,70 @@ __global__ __launch_bounds__(kStThreads) void compare_kernel(const StorePiece *_
     }
 }
 
+// ---- the difference mask -----------------------------------------------------------
+// One bit per byte of a 16-byte block: set where x and y differ.
+__device__ __forceinline__ uint32_t diff_bits4(uint32_t d) {
+    uint32_t t = d | (d >> 4);
+    t |= t >> 2;
+    t |= t >> 1;
+    t &= 0x01010101u;  // bit 0 of each byte: the byte is not zero
+    return (t | (t >> 7) | (t >> 14) | (t >> 21)) & 0xFu;
+}
+__device__ __forceinline__ uint32_t diff_bits16(const u32x4 x, const u32x4 y) {
+    return diff_bits4(x.x ^ y.x) | (diff_bits4(x.y ^ y.y) << 4) | (diff_bits4(x.z ^ y.z) << 8) |
+           (diff_bits4(x.w ^ y.w) << 12);
+}
+
+// compare_kernel with the first-difference minimum replaced by one bit per byte
+// (cdc_files_diff_device): piece p says that the bytes [dst, dst + len) and
+// [src, src + len) are the two sides.  Same mapping (wave per tile, tiles
+// aligned on dst), same loads: dst with aligned 16-byte loads strictly inside
+// the piece, src through load16, ragged heads and tails bytewise.  Tile w owns
+// the 64 words mask[64 w ..]: bit b of the tile is the byte at its address tb +
+// b, set when the two sides differ there; the bits outside the piece are
+// written as zero.  Four lanes share a word: their 16-bit parts meet by shuffle.
+__global__ __launch_bounds__(kStThreads) void diff_mask_kernel(const StorePiece *__restrict__ pieces,
+                                                               const uint64_t *__restrict__ tstart, uint64_t n,
+                                                               const uint64_t *total_ptr, uint64_t *mask) {
+    const uint64_t total = *total_ptr;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t wave0 = (uint64_t)blockIdx.x * kStWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t nwaves = (uint64_t)gridDim.x * kStWaves;
+    for (uint64_t w = wave0; w < total; w += nwaves) {
+        uint64_t lo = 0, hi = n;
+        while (hi - lo > 1) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (tstart[mid] <= w) lo = mid;
+            else hi = mid;
+        }
+        const StorePiece p = pieces[lo];
+        const uint64_t end = p.dst + p.len;
+        const uint64_t tb = (p.dst & ~(kStoreAlign - 1)) + (w - tstart[lo]) * kStoreTile;
+        const uint64_t te = tb + kStoreTile < end ? tb + kStoreTile : end;
+        const uint64_t shift = p.src - p.dst;  // A's address = B's address + shift
+        const uint32_t r = (uint32_t)shift & 15u;
+#pragma unroll
+        for (uint32_t it = 0; it < kStoreTile / (64 * 16); ++it) {
+            const uint64_t a = tb + (uint64_t)it * (64 * 16) + lane * 16;
+            uint32_t bits = 0;
+            if (a < te) {
+                if (a >= p.dst && a + 16 <= end) {
+                    bits = diff_bits16(*reinterpret_cast<gload16_t>(a), load16(a + shift, r));
+                } else {  // ragged head or tail of the piece
+                    const uint64_t b0 = a > p.dst ? a : p.dst, b1 = a + 16 < end ? a + 16 : end;
+                    for (uint64_t b = b0; b < b1; ++b)
+                        if (*reinterpret_cast<gload1_t>(b) != *reinterpret_cast<gload1_t>(b + shift))
+                            bits |= 1u << (uint32_t)(b - a);
+                }
+            }
+            uint64_t v = (uint64_t)bits << (16 * (lane & 3));
+            v |= __shfl_xor(v, 1);
+            v |= __shfl_xor(v, 2);
+            if ((lane & 3) == 0) mask[w * 64 + it * 16 + (lane >> 2)] = v;
+        }
+    }
+}
+
 // ---- scrub stage -----------------------------------------------------------------
 // A slot holds a container once a chunk has been recorded as its first insert.
 __device__ __forceinline__ bool occupied(const IndexTable &t, uint64_t s) {
@@ -962,6 +1026,13 @@ hipError_t launch_store_compare(const StorePiece *pieces, const uint64_t *tstart
                                 const uint64_t *d_total, uint64_t base, unsigned long long *d_diff, hipStream_t s) {
     if (!n || !max_tiles) return hipSuccess;
     compare_kernel<<<copy_grid(max_tiles), kStThreads, 0, s>>>(pieces, tstart, n, d_total, base, d_diff);
+    return hipGetLastError();
+}
+
+hipError_t launch_store_diff_mask(const StorePiece *pieces, const uint64_t *tstart, uint64_t n, uint64_t max_tiles,
+                                  const uint64_t *d_total, uint64_t *mask, hipStream_t s) {
+    if (!n || !max_tiles) return hipSuccess;
+    diff_mask_kernel<<<copy_grid(max_tiles), kStThreads, 0, s>>>(pieces, tstart, n, d_total, mask);
     return hipGetLastError();
 }
 

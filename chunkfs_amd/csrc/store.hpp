@@ -77,6 +77,15 @@ hipError_t launch_store_copy(const StorePiece *pieces, const uint64_t *tstart, u
 hipError_t launch_store_compare(const StorePiece *pieces, const uint64_t *tstart, uint64_t n, uint64_t max_tiles,
                                 const uint64_t *d_total, uint64_t base, unsigned long long *d_diff, hipStream_t s);
 
+// The difference mask over the same kind of piece list (cdc_files_diff_device):
+// piece {src, dst, len} names the two sides, both read and neither written.
+// Tile w of the tile scan owns mask[64 w, 64 w + 64): bit b stands for the byte
+// at (dst & ~15) + k * kStoreTile + b of its piece's tile k, set where the sides
+// differ, zero outside the piece.  mask: 64 words per tile of max_tiles.  Loads
+// follow the compare's rule on either side.
+hipError_t launch_store_diff_mask(const StorePiece *pieces, const uint64_t *tstart, uint64_t n, uint64_t max_tiles,
+                                  const uint64_t *d_total, uint64_t *mask, hipStream_t s);
+
 // Size distribution (CDCFixture::size_distribution, src/bench/mod.rs:218-232).
 // Step 1: *d_max (preset to 0) = the longest container over the occupied slots.
 hipError_t launch_store_dist_max(const IndexTable &t, unsigned long long *d_max, hipStream_t s);

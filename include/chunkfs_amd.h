@@ -42,7 +42,8 @@ extern "C" {
  *    cdc_files_write_batch_device, cdc_fwrite_t; removal and collection --
  *    cdc_files_remove, cdc_files_collect, cdc_store_retain_device,
  *    cdc_collect_stats_t; the edit in place -- cdc_file_splice_device,
- *    cdc_splice_stats_t. */
+ *    cdc_splice_stats_t; snapshots and diffs -- cdc_files_clone,
+ *    cdc_files_diff_device, cdc_diff_stats_t, CDC_DIFF_TABLES_ONLY. */
 #define CHUNKFS_AMD_ABI_VERSION 6
 
 /* Chunk{offset,length} -- reference src/lib.rs:43-47 (usize fields; u64 here). */
@@ -929,6 +930,76 @@ typedef struct {
 int64_t cdc_file_splice_device(cdc_fh_t *fh, cdc_handle_t *chunker, uint64_t offset, uint64_t remove_len,
                                const uint8_t *d_data, size_t insert_len, cdc_splice_stats_t *out,
                                void *hip_stream);
+
+/* ---- Snapshots and diffs ------------------------------------------------------------
+ * Not in the reference.  A snapshot is a copy of a span table -- 52 bytes per span
+ * and no data byte -- and a diff rarely needs the data: two spans that name the
+ * same store slot at the same file offset hold equal bytes by construction.
+ * Together with splice, remove and collect: snapshot, edit in place, ask what
+ * changed, drop the old version, collect.
+ *
+ * cdc_files_clone makes the file `dst` with a deep copy of `src`'s span table:
+ * the same offsets, digests, slots and arena locations, the same size and epoch.
+ * The table comes from the layer's pool in the smallest class that holds the
+ * spans (not src's capacity); the copy is device-to-device on the call's stream,
+ * with one host wait.  No put runs, no arena byte moves and the store's
+ * statistics are unchanged; cdc_files_collect counts the clone's references like
+ * any file's, so shared containers live as long as one version names them.  The
+ * two files share nothing afterwards: an edit of either never shows through the
+ * other.  A file without spans clones to a file without spans.  Works on a
+ * scrubbed store (reads there go through the table's slots, which the clone
+ * owns a copy of).  Returns the span count.  Refusals, each before any device
+ * work and changing nothing:
+ *   CDC_EINVAL    a NULL argument;
+ *   CDC_ENOTFOUND an unknown src, or one whose spans predate a store clear;
+ *   CDC_EEXIST    dst exists already (dst == src included);
+ *   CDC_ENOMEM    the table could not be allocated.
+ *
+ * cdc_files_diff_device.  Let common = min(size_a, size_b) and D the positions x
+ * in [0, max(size_a, size_b)) with x >= common or A[x] != B[x].  The answer is D
+ * as its maximal runs {offset, length}: ascending, no two runs touch, no run is
+ * empty -- canonical.  Returns the number of runs; d_ranges (DEVICE, cap entries)
+ * is written only when that number is <= cap, otherwise nothing is written and
+ * stats is still filled (cdc_file_distribution_device's convention).
+ *   Pieces.  The distinct span boundaries of both tables inside (0, common) cut
+ * [0, common) into pieces, each a non-empty interval inside one span of A and one
+ * span of B.  Spans of length 0 add no piece.
+ *   The sharing rule.  A piece is shared when its two spans have the same slot and
+ * the same start offset, which is to say the two sides are one arena address.  A
+ * shared piece is equal without being read.  Every other piece is compared byte
+ * for byte -- also one whose spans have the same slot at different offsets.
+ * Every compared byte of either file is read once; bytes_shared + bytes_compared
+ * == common.
+ *   CDC_DIFF_TABLES_ONLY.  No arena byte is read: every piece that is not shared
+ * counts as differing, and the answer is the maximal runs of those pieces plus
+ * the tail -- a superset of the exact answer for the price of the table pass, the
+ * changed-chunks list of a backup.  bytes_compared == 0.
+ * Read-only handles are fine; a and b on the same file give 0 runs with nothing
+ * read; cursors are not touched.  The host waits for the device once.  Refusals,
+ * each before any device work, leaving stats and d_ranges untouched:
+ *   CDC_EINVAL    unknown flag bits, a NULL handle, cap > 0 with NULL d_ranges,
+ *                 handles of two different layers;
+ *   CDC_ENOTFOUND a removed file, or one whose spans predate a store clear;
+ *   CDC_ENOTSUP   the store holds target-kind containers (it was scrubbed).
+ * Stream convention: cdc_file_write_device's. */
+typedef struct cdc_diff_stats {
+    uint64_t ranges;          /* runs of the whole answer, also when it exceeds cap */
+    uint64_t bytes_differing; /* sum of their lengths */
+    uint64_t bytes_compared;  /* bytes of each file whose data was read */
+    uint64_t bytes_shared;    /* bytes proved equal from the tables alone */
+    uint64_t pieces;          /* pieces of [0, common); 0 when common == 0 */
+    uint64_t size_a, size_b;
+    double seconds;           /* wall time of the call */
+} cdc_diff_stats_t;
+
+#define CDC_DIFF_TABLES_ONLY 1u
+
+/* Returns the span count of the new file, or a negative CDC_E* code. */
+int64_t cdc_files_clone(cdc_files_t *fs, const char *src, const char *dst, void *hip_stream);
+
+/* Returns the number of runs, or a negative CDC_E* code.  stats is nullable. */
+int64_t cdc_files_diff_device(cdc_fh_t *a, cdc_fh_t *b, uint32_t flags, cdc_chunk_t *d_ranges, size_t cap,
+                              cdc_diff_stats_t *stats, void *hip_stream);
 
 /* ---- Synthetic data -----------------------------------------
  * Fill a DEVICE buffer with the splitmix64 stream: little-endian u64 words,

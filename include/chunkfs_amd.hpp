@@ -457,6 +457,26 @@ class Files {
         check(cdc_files_collect(fs_, &s, hip_stream));
         return s;
     }
+    // cdc_files_clone: the new file `dst` with a deep copy of src's span table; no
+    // put, no arena byte moved.  Returns the span count.  Throws CDC_ENOTFOUND
+    // for an unknown or stale src, CDC_EEXIST when dst exists.
+    int64_t clone(const std::string &src, const std::string &dst, void *hip_stream = nullptr) {
+        return check(cdc_files_clone(fs_, src.c_str(), dst.c_str(), hip_stream));
+    }
+    // cdc_files_diff_device: where two files differ, as maximal runs {offset,
+    // length} in d_ranges (DEVICE, cap entries; written only when the count is <=
+    // cap), and the stats.  Shared pieces are not read; CDC_DIFF_TABLES_ONLY
+    // reads no data at all.
+    struct Diff {
+        int64_t ranges;
+        cdc_diff_stats_t stats;
+    };
+    Diff diff(File &a, File &b, uint32_t flags = 0, cdc_chunk_t *d_ranges = nullptr, size_t cap = 0,
+              void *hip_stream = nullptr) {
+        Diff d{};
+        d.ranges = check(cdc_files_diff_device(a.handle(), b.handle(), flags, d_ranges, cap, &d.stats, hip_stream));
+        return d;
+    }
     // clear_database (mod.rs:275-278): no files, an empty store, handles invalid.
     void clear() { check(cdc_files_clear(fs_)); }
     // clear_file_system (mod.rs:294-297): the target map first, so that the

@@ -84,6 +84,18 @@ split of the last call into planner, chunk, resync, hash + put and table build.
 Compare with (d): writing the whole file again is the only other way to make
 the same edit.
 
+Snapshots and diffs (skipped with --no-snapshot), on a layer of its own holding
+the 1 GiB file of (d):
+
+  (v) cdc_files_clone of the file (the clone is removed before each turn);
+  (w) cdc_files_diff_device of a clone against the original after one 4 KiB
+      overwrite in the middle, exact and with CDC_DIFF_TABLES_ONLY;
+  (x) the same call on two unrelated 1 GiB files: every byte is compared.
+
+Compare (v) with (d), writing the same bytes again under another name, and (w),
+(x) with the read_plus_verify legs beside them: read_complete_device of one file
+plus cdc_file_verify_device of the other, which names the first differing byte only.
+
 Prints one JSON line; --out also writes it to a file.
 """
 import argparse
@@ -371,6 +383,77 @@ def splice_legs(a, c, L, P, ch, buf, n, k, sp, timed, med):
     return res
 
 
+def snapshot_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med):
+    """Legs (v)-(x) on a layer of its own holding the file of (d): the clone; the
+    diff of a clone against the original after one 4 KiB overwrite, exact and
+    from the tables alone; the diff of two unrelated files.  Beside each diff,
+    what the same question costs without it: read_complete_device of one file
+    plus cdc_file_verify_device of the other (which names the first differing
+    byte only), in the same run."""
+    import torch
+    from chunkfs_amd import _lib
+
+    other = torch.empty(n, dtype=torch.uint8, device="cuda")
+    fresh = torch.empty(4096, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    _lib.check(L.cdc_fill_splitmix64_device(P(other.data_ptr()), n, a.seed + 11, None))
+    _lib.check(L.cdc_fill_splitmix64_device(P(fresh.data_ptr()), 4096, a.seed + 13, None))
+    fsys = c.FileSystem(store=c.ChunkStore(2 * k + (1 << 15), 2 * n + 32 * k + (64 << 20)))
+    w = fsys.create_file("bench", ch)
+    assert L.cdc_file_write_device(w._fh, ch._h, P(buf.data_ptr()), n, None) == k
+    res = {}
+
+    def drop():
+        if fsys.file_exists("snap"):
+            fsys.remove_file("snap")
+
+    def do_clone():
+        got = L.cdc_files_clone(fsys._h, b"bench", b"snap", P(sp))
+        assert got == k, f"cdc_files_clone: {got}"
+
+    t = timed(do_clone, before=drop)
+    res["v_clone"] = {"ms": med(t), "ms_min_max": [min(t), max(t)], "spans": k, "table_bytes": 52 * k + 8}
+
+    e = fsys.open_file("snap", ch)
+    st1 = _lib.cdc_splice_stats_t()
+    assert L.cdc_file_splice_device(e._fh, ch._h, n // 2 + 1234, 4096, P(fresh.data_ptr()), 4096, ctypes.byref(st1),
+                                    None) >= 0
+    o = fsys.create_file("other", ch)
+    assert L.cdc_file_write_device(o._fh, ch._h, P(other.data_ptr()), n, None) > 0
+    cap = 1024
+    d_ranges = torch.empty((cap, 2), dtype=torch.int64, device="cuda")
+    st, first = _lib.cdc_diff_stats_t(), ctypes.c_uint64(0)
+    torch.cuda.synchronize()
+
+    def diff_leg(name, x, y, flags):
+        def call():
+            got = L.cdc_files_diff_device(x._fh, y._fh, flags, P(d_ranges.data_ptr()), cap, ctypes.byref(st), P(sp))
+            assert got >= 0, f"cdc_files_diff_device: {got}"
+
+        t = timed(call)
+        res[name] = dict({f: getattr(st, f) for f, _ in _lib.cdc_diff_stats_t._fields_ if f != "seconds"},
+                         ms=med(t), ms_min_max=[min(t), max(t)])
+
+    def base_leg(name, x, y):
+        def call():
+            assert L.cdc_file_read_complete_device(x._fh, P(out.data_ptr()), n, None, P(sp)) == n
+            assert L.cdc_file_verify_device(y._fh, P(out.data_ptr()), n, ctypes.byref(first), P(sp)) == 0
+
+        t = timed(call)
+        res[name] = {"ms": med(t), "ms_min_max": [min(t), max(t)], "first_diff": first.value}
+
+    diff_leg("w_diff_after_4k_edit", w, e, 0)
+    if res["w_diff_after_4k_edit"]["ranges"] < 1 or res["w_diff_after_4k_edit"]["bytes_differing"] > 4096:
+        raise SystemExit("store_bench: the diff after a 4 KiB overwrite does not lie inside the 4 KiB")
+    diff_leg("w_diff_after_4k_edit_tables_only", w, e, _lib.CDC_DIFF_TABLES_ONLY)
+    base_leg("w_read_plus_verify", w, e)
+    diff_leg("x_diff_unrelated", w, o, 0)
+    if res["x_diff_unrelated"]["bytes_compared"] != n:
+        raise SystemExit("store_bench: two unrelated files share bytes")
+    base_leg("x_read_plus_verify", w, o)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--bytes", type=int, default=1 << 30)
@@ -382,6 +465,7 @@ def main():
     ap.add_argument("--no-batch-write", action="store_true", help="skip the many-files legs (o)-(p)")
     ap.add_argument("--no-collect", action="store_true", help="skip the remove-and-collect legs (q)-(r)")
     ap.add_argument("--no-splice", action="store_true", help="skip the edit-in-place legs (s)-(u)")
+    ap.add_argument("--no-snapshot", action="store_true", help="skip the clone and diff legs (v)-(x)")
     ap.add_argument("--collect-iters", type=int, default=3)
     ap.add_argument("--scrub-iters", type=int, default=3)
     ap.add_argument("--scrub-groups", default="4096,64m;65536,256m;1048576,1024m",
@@ -584,6 +668,8 @@ def main():
         res["collect"] = collect_legs(a, c, L, P, ch, buf, n, med(t_memcpy))
     if not a.no_splice:
         res["splice"] = splice_legs(a, c, L, P, ch, buf, n, k, sp, timed, med)
+    if not a.no_snapshot:
+        res["snapshot"] = snapshot_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med)
     line = json.dumps(res)
     print(line)
     if a.out:
