@@ -46,6 +46,7 @@
 #include "files.hpp"
 
 #include "diff_plan.hpp"
+#include "read_plan.hpp"
 #include "splice_plan.hpp"
 
 namespace cdc {
@@ -55,30 +56,6 @@ constexpr int kFlThreads = 256;
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
 
 inline unsigned grid_of(uint64_t n) { return (unsigned)((n + kFlThreads - 1) / kFlThreads); }
-
-// First i in [0, n) with off[i] >= x (n when there is none): the reference's
-// skip_while(span.offset < handle.offset).
-__device__ __forceinline__ uint64_t first_at_or_after(const uint64_t *__restrict__ off, uint64_t n, uint64_t x) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (off[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// Largest k in [lo, hi] with off[k] <= x; off[lo] <= x must hold.  Equal
-// offsets (length-0 spans) resolve to the last of them.
-__device__ __forceinline__ uint64_t last_at_or_before(const uint64_t *__restrict__ off, uint64_t lo, uint64_t hi,
-                                                      uint64_t x) {
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= x) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
 
 // ---- append --------------------------------------------------------------------
 // stat[0] = min over the spans of length - 1 (a length-0 span wraps to the
@@ -234,44 +211,15 @@ __global__ __launch_bounds__(kFlThreads) void resolve_kernel(const ReadReq *__re
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= nreq) return;
     const ReadReq q = req[r];
-    const uint64_t n = q.n;
-    uint64_t lo = 0, hi = 0, first = 0, count = 0;
-    if (n) {
-        const uint64_t size = q.off[n];
-        if (q.kind == kReadComplete) {
-            hi = size;
-            count = n;
-        } else if (q.kind == kReadSegment) {
-            const uint64_t i0 = first_at_or_after(q.off, n, q.a);
-            if (i0 < n) {
-                lo = q.off[i0];
-                const uint64_t limit = lo + q.b < lo ? ~0ull : lo + q.b;
-                // take_while(running total <= segment): the largest k with off[k] - off[i0] <= seg.
-                const uint64_t k = last_at_or_before(q.off, i0, n, limit);
-                hi = q.off[k];
-                first = i0;
-                count = k - i0;
-            }
-        } else {
-            lo = q.a < size ? q.a : size;
-            hi = q.b > size - lo ? size : lo + q.b;
-            if (hi > lo) {
-                // lo < size = off[n]: the span that holds byte lo is the last one starting at or before it.
-                first = last_at_or_before(q.off, 0, n, lo);
-                count = last_at_or_before(q.off, first, n, hi - 1) - first + 1;
-            }
-        }
-    }
-    const uint64_t bytes = hi - lo;
-    if (bytes > q.cap) count = 0;  // too small a destination: the request copies nothing
-    plan[r] = ReadPlan{lo, hi, first};
+    const ReadSpans x = read_resolve(q.off, q.n, q.kind, q.a, q.b, q.cap);
+    plan[r] = ReadPlan{x.lo, x.hi, x.first};
     if (single) {
         cnt[r] = 0;
-        *single = count;
+        *single = x.count;
     } else {
-        cnt[r] = count;
+        cnt[r] = x.count;
     }
-    h_res[r] = ReadResult{bytes, first, count};
+    h_res[r] = ReadResult{x.hi - x.lo, x.first, x.count};
 }
 
 // pstart = exclusive scan of the span counts, *total_pieces their sum.  Threads
@@ -701,6 +649,7 @@ __global__ __launch_bounds__(kFlThreads) void collect_remap_kernel(const Collect
 
 // ---- diff ---------------------------------------------------------------------------
 static_assert(kDiffTile == kStoreTile && kDiffAlign == kStoreAlign, "diff_plan.hpp cuts the store's tiles");
+static_assert(kReadTile == kStoreTile && kReadAlign == kStoreAlign, "read_plan.hpp bounds the store's tiles");
 constexpr int kFlWaves = kFlThreads / 64;
 constexpr unsigned kDiffMaxBlocks = 1u << 18;  // waves (threads of the fix-up) past this stride
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "read_plan.hpp"
 #include "store.hpp"
 
 namespace cdc {
@@ -17,13 +18,7 @@ struct SpanTable {
     uint32_t *slot;    // [cap] the span's table slot (the distribution counts per slot)
 };
 
-enum ReadKind : uint32_t {
-    kReadComplete = 0,  // every span: read_file_complete
-    kReadSegment = 1,   // whole spans from the cursor while their total stays <= seg: read_from_file
-    kReadRange = 2,     // the bytes [a, a + b) clipped to the file: pread
-};
-
-// One read request, built on the host.
+// One read request, built on the host (kind: ReadKind, read_plan.hpp).
 struct ReadReq {
     const uint64_t *off;
     const uint64_t *loc;

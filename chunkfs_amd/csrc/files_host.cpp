@@ -17,11 +17,16 @@
 #include "engine.hpp"
 #include "files.hpp"
 #include "diff_plan.hpp"
+#include "read_plan.hpp"
 #include "splice_plan.hpp"
 #include "store.hpp"
 #include "store_internal.hpp"
 
 namespace {
+
+using cdc::DeviceBuf;
+using cdc::PinnedBuf;
+using word = unsigned long long;
 
 struct FileRec {
     uint64_t n = 0;      // spans
@@ -82,6 +87,87 @@ struct TablePool {
     }
 };
 
+// What the kernels hand back, one member per meaning.  A kernel that writes
+// several words gets the address of the first: the members of one line are
+// adjacent, in the order the comment at its launch_ function lists them.
+struct HostWords {               // pinned host memory
+    word appended;               // append, splice build, ratio gather: bytes appended (the derived file's size)
+    word distinct;               // distribution: distinct slots
+    word least, zeros;           // DeviceWords' copy
+    word unique, unique_length;  // launch_files_ratio_unique: U and the bytes of the unique spans
+    word cycle, partial;         // launch_files_ratio_take: C = bytes of one cycle, spans of the partial cycle
+    word verify;                 // DeviceWords' copy
+    word x_pieces, x_touched;    // launch_files_plan_x: pieces in all, target-kind spans touched
+    word i0, w0;                 // launch_splice_start: the start span and off[i0]
+    word resync_k, resync_j, resync_e;  // launch_splice_resync: the smallest chunk that resyncs (~0: none), the old
+                                        // span its cut meets, the cut
+    word ranges, bytes_differing, bytes_compared, bytes_shared, pieces;  // launch_files_diff
+};
+struct DeviceWords {
+    word least, zeros;  // launch_files_append's d_stat, preset to {~0, 0}: min(length - 1) over the spans of
+                        // length > 0, spans of length 0
+    word verify;        // the smallest destination address - cmp_base at which a byte differs, preset to ~0
+    word touch;         // launch_files_plan_x's counter
+    word best;          // launch_splice_resync's
+};
+
+// Scratch kept between calls, one struct per group of buffers that grow
+// together (grow_group, store_internal.hpp); the rule is the group's own.
+struct SpanScratch {  // append / distribution / ratio: per span
+    uint64_t cap = 0;
+    DeviceBuf<uint64_t> val, block;
+    hipError_t grow(uint64_t n) {
+        const uint64_t c = n + n / 8 + 64;
+        return cdc::grow_group(cap, n, c, val, c, block, cdc::store_scan_blocks(c) + 1);
+    }
+};
+struct SlotScratch {  // distribution / ratio: per slot, as large as the store's table
+    uint64_t cap = 0;
+    DeviceBuf<uint32_t> cnt;
+    DeviceBuf<uint64_t> first;
+    hipError_t grow(uint64_t slots) { return cdc::grow_group(cap, slots, slots, cnt, slots, first, slots); }
+};
+struct WriteScratch {  // write / batch write / splice: chunk list and digests of one call, n the chunker's bound
+    uint64_t cap = 0;
+    DeviceBuf<cdc_chunk_t> chunks;
+    DeviceBuf<uint8_t> dig;
+    hipError_t grow(uint64_t n) { return cdc::grow_group(cap, n, n, chunks, n, dig, n * 32); }
+};
+// What cdc_files_write_batch_device uploads in one copy, for n requests:
+// first[n + 1], the destinations and the preset statistics.
+uint64_t batch_bytes(uint64_t n) { return (n + 1) * 8 + n * (sizeof(cdc::AppendDst) + sizeof(cdc::AppendStat)); }
+struct BatchUpload {
+    uint64_t cap = 0;
+    PinnedBuf<uint8_t> h;
+    DeviceBuf<uint8_t> d;
+    hipError_t grow(uint64_t n) {
+        const uint64_t c = n + n / 8 + 16;
+        return cdc::grow_group(cap, n, c, h, batch_bytes(c), d, batch_bytes(c));
+    }
+};
+struct RequestScratch {  // reads: per request
+    uint64_t cap = 0;
+    PinnedBuf<cdc::ReadReq> h_req;
+    PinnedBuf<cdc::ReadResult> h_res;
+    DeviceBuf<cdc::ReadReq> d_req;
+    DeviceBuf<cdc::ReadPlan> plan;
+    DeviceBuf<uint64_t> cnt, block;
+    hipError_t grow(uint64_t n) {
+        const uint64_t c = n + n / 8 + 16;
+        return cdc::grow_group(cap, n, c, h_req, c, h_res, c, d_req, c, plan, c, cnt, c, block,
+                               cdc::store_scan_blocks(c) + 1);
+    }
+};
+struct SlotArrays {  // reads in the scrubbed state: per request, the address of its file's slot array
+    uint64_t cap = 0;
+    PinnedBuf<uint64_t> h;
+    DeviceBuf<uint64_t> d;
+    hipError_t grow(uint64_t n) {
+        const uint64_t c = n + n / 8 + 16;
+        return cdc::grow_group(cap, n, c, h, c, d, c);
+    }
+};
+
 }  // namespace
 
 struct cdc_files {
@@ -89,51 +175,20 @@ struct cdc_files {
     int device = 0;  // the store's, kept so that teardown needs nothing of the store
     uint64_t seg = 0;
     TablePool pool;
-    // cdc_files_write_batch_device: per-request first[], destinations and statistics, one upload
-    uint64_t b_cap = 0;
-    uint8_t *h_batch = nullptr, *d_batch = nullptr;  // h_*: pinned host memory
     std::map<std::string, FileRec *> files;  // ordered: cdc_files_list is deterministic
     std::set<cdc_fh *> handles;
-    // cdc_file_write_device: chunk list and digests of one call
-    uint64_t w_cap = 0;
-    cdc_chunk_t *w_chunks = nullptr;
-    uint8_t *w_dig = nullptr;
-    // append / distribution: per-span scratch
-    uint64_t a_cap = 0;
-    uint64_t *a_val = nullptr, *a_block = nullptr;
-    uint64_t d_slots = 0;
-    uint32_t *d_cnt = nullptr;
-    uint64_t *d_first = nullptr;
-    // reads: per-request and per-piece scratch
-    uint64_t r_cap = 0;
-    cdc::ReadReq *h_req = nullptr, *d_req = nullptr;  // h_*: pinned host memory
-    cdc::ReadPlan *d_plan = nullptr;
-    uint64_t *d_rcnt = nullptr, *d_rblock = nullptr;
-    cdc::ReadResult *h_res = nullptr;
-    uint64_t p_cap = 0;
-    cdc::StorePiece *d_pieces = nullptr;
-    uint64_t *d_tstart = nullptr, *d_pblock = nullptr;
-    // pinned: [0] appended bytes, [1] distinct digests, [2..3] d_stat's copy, [4..7] get_to_dedup_ratio: U,
-    // unique_length, C, spans of the partial cycle, [8] verify: d_stat[2]'s copy
-    unsigned long long *h_tot = nullptr;
-    unsigned long long *d_stat = nullptr;  // [0..1] append: min(length - 1), spans of length 0; [2] verify: first difference
-    // reads in the scrubbed state: per-request slot arrays, per-span records
-    uint64_t xr_cap = 0;
-    uint64_t *h_rslot = nullptr, *d_rslot = nullptr;
-    uint64_t xs_cap = 0;
-    cdc::SpanRec *d_recs = nullptr;
-    uint64_t *d_pcnt = nullptr, *d_xblock = nullptr;
-    unsigned long long *h_xtot = nullptr;  // pinned: [0] pieces, [1] target-kind spans touched
-    unsigned long long *d_touch = nullptr;
-    // cdc_file_splice_device: the window of the new file that is chunked, and the searches' results
-    uint64_t s_cap = 0;
-    uint8_t *s_win = nullptr;
-    unsigned long long *h_sp = nullptr;  // pinned: start {i0, off[i0]}; resync {k, j, e_k}
-    unsigned long long *d_sp = nullptr;  // the smallest chunk that resyncs
-    // cdc_files_diff_device: one device block carved into the DiffScratch arrays, and the result words
-    uint64_t df_bytes = 0;
-    uint8_t *df_mem = nullptr;
-    unsigned long long *h_df = nullptr;  // pinned: ranges, bytes_differing, bytes_compared, bytes_shared, pieces
+    PinnedBuf<HostWords> hw;  // one each, allocated with the layer
+    DeviceBuf<DeviceWords> dw;
+    SpanScratch span;
+    SlotScratch slot;
+    WriteScratch wr;
+    BatchUpload batch;
+    RequestScratch req;
+    cdc::ScanScratch<cdc::StorePiece> pc;  // reads: per piece, with the tile counts
+    SlotArrays xslot;
+    cdc::ScanScratch<cdc::SpanRec> xspan;  // reads in the scrubbed state: per span, with the piece counts
+    DeviceBuf<uint8_t> window;  // cdc_file_splice_device: the window of the new file that is chunked
+    DeviceBuf<uint8_t> diff;    // cdc_files_diff_device: one block carved into the DiffScratch arrays
 };
 
 struct cdc_fh {
@@ -146,12 +201,14 @@ struct cdc_fh {
 
 namespace {
 
+int code_of(hipError_t e) { return e == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE; }
+
 #define FL_TRY(expr)                                                         \
     do {                                                                     \
         hipError_t e_ = (expr);                                              \
         if (e_ != hipSuccess) {                                              \
             cdc::set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); \
-            return e_ == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE;     \
+            return code_of(e_);                                              \
         }                                                                    \
     } while (0)
 
@@ -159,6 +216,8 @@ int fail(int code, const std::string &msg) {
     cdc::set_error(msg);
     return code;
 }
+
+int fail_hip(const std::string &what, hipError_t e) { return fail(code_of(e), what + hipGetErrorString(e)); }
 
 // The table goes back to the layer's pool.  Every call synchronises its stream
 // before it returns, so a table handed out again is no longer read or written.
@@ -176,31 +235,45 @@ void drop_files(cdc_files *fs) {
     fs->files.clear();
 }
 
+// The capacity of a table that holds `cap` spans now and is to hold `need`.
+uint64_t table_cap(uint64_t cap, uint64_t need) {
+    if (!cap) cap = kTableMinCap;
+    while (cap < need) cap *= 2;
+    return cap;
+}
+
+// A table of that capacity from the pool; `what` opens the message when there is none.
+int take_table(cdc_files *fs, uint64_t cap, cdc::SpanTable *t, const char *what) {
+    const hipError_t e = fs->pool.take(cap, t);
+    return e == hipSuccess ? CDC_OK : fail_hip(what, e);
+}
+
+// Queues the copy of n spans, and the offset that closes them.
+hipError_t copy_spans(const cdc::SpanTable &to, const cdc::SpanTable &from, uint64_t n, hipStream_t s) {
+    hipError_t e = hipMemcpyAsync(to.off, from.off, (n + 1) * 8, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(to.digest, from.digest, n * 32, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(to.loc, from.loc, n * 8, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(to.slot, from.slot, n * 4, hipMemcpyDeviceToDevice, s);
+    return e;
+}
+
 // Capacity doubles: a table of the next class from the pool, the spans copied on
 // the call's stream, the old table back to the pool.  copied == NULL: the copy is
 // waited for here.  Otherwise *copied is set when a copy was queued and the
 // caller waits once for all of them; until then only work on `s` may follow.
 int reserve(cdc_files *fs, FileRec *f, uint64_t need, hipStream_t s, bool *copied = nullptr) {
     if (need <= f->cap) return CDC_OK;
-    uint64_t cap = f->cap ? f->cap : kTableMinCap;
-    while (cap < need) cap *= 2;
+    const uint64_t cap = table_cap(f->cap, need);
     cdc::SpanTable t{};
-    hipError_t e = fs->pool.take(cap, &t);
-    if (e != hipSuccess) {
-        cdc::set_error(std::string("file layer: span table growth: ") + hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE;
-    }
+    const int rc = take_table(fs, cap, &t, "file layer: span table growth: ");
+    if (rc) return rc;
     if (f->n) {
-        e = hipMemcpyAsync(t.off, f->t.off, (f->n + 1) * 8, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(t.digest, f->t.digest, f->n * 32, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(t.loc, f->t.loc, f->n * 8, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(t.slot, f->t.slot, f->n * 4, hipMemcpyDeviceToDevice, s);
+        hipError_t e = copy_spans(t, f->t, f->n, s);
         if (e == hipSuccess && !copied) e = hipStreamSynchronize(s);
         if (e != hipSuccess) {
             (void)hipStreamSynchronize(s);  // whatever was queued is done before the table is handed out again
             fs->pool.give(t, cap);
-            cdc::set_error(std::string("file layer: span table growth: ") + hipGetErrorString(e));
-            return e == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE;
+            return fail_hip("file layer: span table growth: ", e);
         }
         if (copied) *copied = true;
     }
@@ -210,127 +283,20 @@ int reserve(cdc_files *fs, FileRec *f, uint64_t need, hipStream_t s, bool *copie
     return CDC_OK;
 }
 
-// What cdc_files_write_batch_device uploads in one copy, for n requests:
-// first[n + 1], the destinations and the preset statistics.
-uint64_t batch_bytes(uint64_t n) { return (n + 1) * 8 + n * (sizeof(cdc::AppendDst) + sizeof(cdc::AppendStat)); }
-
-int grow_batch(cdc_files *fs, uint64_t n) {
-    if (fs->b_cap >= n) return CDC_OK;
-    (void)hipHostFree(fs->h_batch);
-    (void)hipFree(fs->d_batch);
-    fs->h_batch = fs->d_batch = nullptr;
-    fs->b_cap = 0;
-    const uint64_t cap = n + n / 8 + 16;
-    FL_TRY(hipHostMalloc(&fs->h_batch, batch_bytes(cap)));
-    FL_TRY(hipMalloc(&fs->d_batch, batch_bytes(cap)));
-    fs->b_cap = cap;
-    return CDC_OK;
-}
-
-int grow_span_scratch(cdc_files *fs, uint64_t n) {
-    if (fs->a_cap >= n) return CDC_OK;
-    (void)hipFree(fs->a_val);
-    (void)hipFree(fs->a_block);
-    fs->a_val = fs->a_block = nullptr;
-    fs->a_cap = 0;
-    const uint64_t cap = n + n / 8 + 64;
-    FL_TRY(hipMalloc(&fs->a_val, cap * 8));
-    FL_TRY(hipMalloc(&fs->a_block, (cdc::store_scan_blocks(cap) + 1) * 8));
-    fs->a_cap = cap;
-    return CDC_OK;
-}
-
-// The distribution's per-slot scratch: as large as the store's table.
-int grow_slot_scratch(cdc_files *fs, uint64_t slots) {
-    if (fs->d_slots >= slots) return CDC_OK;
-    (void)hipFree(fs->d_cnt);
-    (void)hipFree(fs->d_first);
-    fs->d_cnt = nullptr;
-    fs->d_first = nullptr;
-    fs->d_slots = 0;
-    FL_TRY(hipMalloc(&fs->d_cnt, slots * 4));
-    FL_TRY(hipMalloc(&fs->d_first, slots * 8));
-    fs->d_slots = slots;
-    return CDC_OK;
-}
-
-int grow_requests(cdc_files *fs, uint64_t n) {
-    if (fs->r_cap >= n) return CDC_OK;
-    (void)hipHostFree(fs->h_req);
-    (void)hipHostFree(fs->h_res);
-    (void)hipFree(fs->d_req);
-    (void)hipFree(fs->d_plan);
-    (void)hipFree(fs->d_rcnt);
-    (void)hipFree(fs->d_rblock);
-    fs->h_req = fs->d_req = nullptr;
-    fs->h_res = nullptr;
-    fs->d_plan = nullptr;
-    fs->d_rcnt = fs->d_rblock = nullptr;
-    fs->r_cap = 0;
-    const uint64_t cap = n + n / 8 + 16;
-    FL_TRY(hipHostMalloc(&fs->h_req, cap * sizeof(cdc::ReadReq)));
-    FL_TRY(hipHostMalloc(&fs->h_res, cap * sizeof(cdc::ReadResult)));
-    FL_TRY(hipMalloc(&fs->d_req, cap * sizeof(cdc::ReadReq)));
-    FL_TRY(hipMalloc(&fs->d_plan, cap * sizeof(cdc::ReadPlan)));
-    FL_TRY(hipMalloc(&fs->d_rcnt, cap * 8));
-    FL_TRY(hipMalloc(&fs->d_rblock, (cdc::store_scan_blocks(cap) + 1) * 8));
-    fs->r_cap = cap;
-    return CDC_OK;
-}
-
-int grow_pieces(cdc_files *fs, uint64_t n) {
-    if (fs->p_cap >= n) return CDC_OK;
-    (void)hipFree(fs->d_pieces);
-    (void)hipFree(fs->d_tstart);
-    (void)hipFree(fs->d_pblock);
-    fs->d_pieces = nullptr;
-    fs->d_tstart = fs->d_pblock = nullptr;
-    fs->p_cap = 0;
-    const uint64_t cap = n + n / 8 + 64;
-    FL_TRY(hipMalloc(&fs->d_pieces, cap * sizeof(cdc::StorePiece)));
-    FL_TRY(hipMalloc(&fs->d_tstart, cap * 8));
-    FL_TRY(hipMalloc(&fs->d_pblock, (cdc::store_scan_blocks(cap) + 1) * 8));
-    fs->p_cap = cap;
-    return CDC_OK;
-}
-
 void release(cdc_files *fs) {
     (void)hipSetDevice(fs->device);
     drop_files(fs);
     for (cdc_fh *h : fs->handles) h->fs = nullptr;
     fs->pool.release();
-    (void)hipHostFree(fs->h_batch);
-    (void)hipFree(fs->d_batch);
-    (void)hipFree(fs->w_chunks);
-    (void)hipFree(fs->w_dig);
-    (void)hipFree(fs->a_val);
-    (void)hipFree(fs->a_block);
-    (void)hipFree(fs->d_cnt);
-    (void)hipFree(fs->d_first);
-    (void)hipHostFree(fs->h_req);
-    (void)hipHostFree(fs->h_res);
-    (void)hipFree(fs->d_req);
-    (void)hipFree(fs->d_plan);
-    (void)hipFree(fs->d_rcnt);
-    (void)hipFree(fs->d_rblock);
-    (void)hipFree(fs->d_pieces);
-    (void)hipFree(fs->d_tstart);
-    (void)hipFree(fs->d_pblock);
-    (void)hipHostFree(fs->h_tot);
-    (void)hipFree(fs->d_stat);
-    (void)hipHostFree(fs->h_rslot);
-    (void)hipFree(fs->d_rslot);
-    (void)hipFree(fs->d_recs);
-    (void)hipFree(fs->d_pcnt);
-    (void)hipFree(fs->d_xblock);
-    (void)hipHostFree(fs->h_xtot);
-    (void)hipFree(fs->d_touch);
-    (void)hipFree(fs->s_win);
-    (void)hipHostFree(fs->h_sp);
-    (void)hipFree(fs->d_sp);
-    (void)hipFree(fs->df_mem);
-    (void)hipHostFree(fs->h_df);
-    delete fs;
+    delete fs;  // the buffers free themselves, the device still current
+}
+
+// A file whose spans were resolved before the store was last cleared names
+// slots of another table: nothing can be read from it or added to it.
+int check_epoch(const cdc_files *fs, const FileRec *f, const std::string &name) {
+    if (f->n && f->epoch != cdc::store_view(fs->store).epoch)
+        return fail(CDC_ENOTFOUND, "file layer: the store was cleared since '" + name + "' was written");
+    return CDC_OK;
 }
 
 // The handle's file, by name as the reference finds it (file_layer.rs:116-124).
@@ -340,55 +306,61 @@ int lookup(cdc_fh *fh, bool for_read, FileRec **out) {
     if (!fh->fs) return fail(CDC_EINVAL, "file handle outlived its file layer");
     auto it = fh->fs->files.find(fh->name);
     if (it == fh->fs->files.end()) return fail(CDC_ENOTFOUND, "file layer: no file named '" + fh->name + "'");
-    FileRec *f = it->second;
-    if (for_read && f->n && f->epoch != cdc::store_view(fh->fs->store).epoch)
-        return fail(CDC_ENOTFOUND, "file layer: the store was cleared since '" + fh->name + "' was written");
-    *out = f;
-    return CDC_OK;
+    *out = it->second;
+    return for_read ? check_epoch(fh->fs, it->second, fh->name) : CDC_OK;
+}
+
+// The handle's file for a call that adds spans to it.
+int writable(cdc_fh *fh, FileRec **out) {
+    const int rc = lookup(fh, false, out);
+    if (rc) return rc;
+    if (fh->readonly) return fail(CDC_EPERM, "file handle is read-only");
+    return check_epoch(fh->fs, *out, fh->name);
 }
 
 hipStream_t stream_of(cdc_files *fs, void *hip_stream) {
     return hip_stream ? static_cast<hipStream_t>(hip_stream) : cdc::store_view(fs->store).stream;
 }
 
+// Around a launch that takes d_stat: the preset, the copy to the host, and what
+// the host keeps of it per file to bound the spans of a range (read_plan.hpp).
+hipError_t preset_stat(cdc_files *fs, hipStream_t s) {
+    const hipError_t e = hipMemsetAsync(&fs->dw->least, 0xFF, sizeof(word), s);
+    return e == hipSuccess ? hipMemsetAsync(&fs->dw->zeros, 0, sizeof(word), s) : e;
+}
+hipError_t fetch_stat(cdc_files *fs, hipStream_t s) {
+    return hipMemcpyAsync(&fs->hw->least, &fs->dw->least, 2 * sizeof(word), hipMemcpyDeviceToHost, s);
+}
+void fold_stat(FileRec *f, uint64_t least, uint64_t zeros) {
+    if (least != ~0ull && least + 1 < f->min_len) f->min_len = least + 1;
+    f->zeros += zeros;
+}
+
 int64_t append(cdc_fh *fh, const uint8_t *d_data, uint64_t data_len, const cdc_chunk_t *d_chunks,
                const uint8_t *d_digests, uint64_t n, void *hip_stream) {
     FileRec *f = nullptr;
-    int rc = lookup(fh, false, &f);
+    int rc = writable(fh, &f);
     if (rc) return rc;
-    if (fh->readonly) return fail(CDC_EPERM, "file handle is read-only");
     cdc_files *fs = fh->fs;
     cdc::StoreView v = cdc::store_view(fs->store);
-    if (f->n && f->epoch != v.epoch)
-        return fail(CDC_ENOTFOUND, "file layer: the store was cleared since '" + fh->name + "' was written");
     if (n == 0) return 0;
     FL_TRY(hipSetDevice(v.device));
     hipStream_t s = stream_of(fs, hip_stream);
     if ((rc = reserve(fs, f, f->n + n, s)) != CDC_OK) return rc;
-    if ((rc = grow_span_scratch(fs, n)) != CDC_OK) return rc;
+    FL_TRY(fs->span.grow(n));
     const int64_t put = cdc::store_put_slots(fs->store, d_data, data_len, d_chunks, d_digests, n, hip_stream);
     if (put < 0) return put;  // refused: the file is as it was
     v = cdc::store_view(fs->store);
-    FL_TRY(hipMemsetAsync(fs->d_stat, 0xFF, 8, s));
-    FL_TRY(hipMemsetAsync(fs->d_stat + 1, 0, 8, s));
-    FL_TRY(cdc::launch_files_append(f->t, f->n, f->size, v.slot_of, v.length, v.loc, d_digests, n, fs->a_val,
-                                    fs->a_block, fs->d_stat, fs->h_tot, s));
-    FL_TRY(hipMemcpyAsync(fs->h_tot + 2, fs->d_stat, 16, hipMemcpyDeviceToHost, s));
+    FL_TRY(preset_stat(fs, s));
+    FL_TRY(cdc::launch_files_append(f->t, f->n, f->size, v.slot_of, v.length, v.loc, d_digests, n, fs->span.val,
+                                    fs->span.block, &fs->dw->least, &fs->hw->appended, s));
+    FL_TRY(fetch_stat(fs, s));
     FL_TRY(hipStreamSynchronize(s));
     f->n += n;
-    f->size += fs->h_tot[0];
+    f->size += fs->hw->appended;
     f->epoch = v.epoch;
-    if (fs->h_tot[2] != ~0ull && fs->h_tot[2] + 1 < f->min_len) f->min_len = fs->h_tot[2] + 1;
-    f->zeros += fs->h_tot[3];
+    fold_stat(f, fs->hw->least, fs->hw->zeros);
     return (int64_t)n;
-}
-
-// Spans a range of at most `bytes` bytes can touch, whole spans but for its two
-// ends: the spans of length 0, the longer ones that fit, and the two ends.
-uint64_t spans_bound(const FileRec *f, uint64_t bytes) {
-    const uint64_t fit = f->min_len == ~0ull ? 0 : bytes / f->min_len;
-    const uint64_t bound = f->zeros + fit + 2;
-    return bound < f->n ? bound : f->n;
 }
 
 // One request of `kind` on a file; cap, the destination's size, also bounds the tiles.
@@ -401,33 +373,22 @@ struct HostReq {
     cdc_chunk_t *spans;
 };
 
-int grow_scrubbed(cdc_files *fs, uint64_t nreq, uint64_t spans) {
-    if (!fs->h_xtot) {
-        FL_TRY(hipHostMalloc(&fs->h_xtot, 2 * sizeof(unsigned long long)));
-        FL_TRY(hipMalloc(&fs->d_touch, sizeof(unsigned long long)));
-    }
-    if (fs->xr_cap < nreq) {
-        (void)hipHostFree(fs->h_rslot);
-        (void)hipFree(fs->d_rslot);
-        fs->h_rslot = fs->d_rslot = nullptr;
-        fs->xr_cap = 0;
-        const uint64_t cap = nreq + nreq / 8 + 16;
-        FL_TRY(hipHostMalloc(&fs->h_rslot, cap * 8));
-        FL_TRY(hipMalloc(&fs->d_rslot, cap * 8));
-        fs->xr_cap = cap;
-    }
-    if (fs->xs_cap < spans) {
-        (void)hipFree(fs->d_recs);
-        (void)hipFree(fs->d_pcnt);
-        (void)hipFree(fs->d_xblock);
-        fs->d_recs = nullptr;
-        fs->d_pcnt = fs->d_xblock = nullptr;
-        fs->xs_cap = 0;
-        const uint64_t cap = spans + spans / 8 + 64;
-        FL_TRY(hipMalloc(&fs->d_recs, cap * sizeof(cdc::SpanRec)));
-        FL_TRY(hipMalloc(&fs->d_pcnt, cap * 8));
-        FL_TRY(hipMalloc(&fs->d_xblock, (cdc::store_scan_blocks(cap) + 1) * 8));
-        fs->xs_cap = cap;
+// The host-side bounds of a call, summed over its requests (read_plan.hpp):
+// spans touched, bytes copied, and the tiles of the requests that have bytes.
+struct ReadTotals {
+    uint64_t spans = 0, bytes = 0, tiles = 0;
+};
+// Room for the requests, fs->req.h_req filled, the bounds summed.
+int prepare_reads(cdc_files *fs, const std::vector<HostReq> &reqs, ReadTotals *t) {
+    FL_TRY(fs->req.grow(reqs.size()));
+    for (uint64_t i = 0; i < reqs.size(); ++i) {
+        const HostReq &q = reqs[i];
+        fs->req.h_req[i] = cdc::ReadReq{q.f->t.off, q.f->t.loc, q.f->n, q.a, q.b, (uint64_t)(uintptr_t)q.dst, q.cap,
+                                        (uint64_t)(uintptr_t)q.spans, q.kind, 0};
+        const cdc::ReadBound b = cdc::read_bound(q.kind, q.b, q.cap, q.f->n, q.f->size, q.f->min_len, q.f->zeros);
+        t->spans += b.spans;
+        t->bytes += b.bytes;
+        if (b.bytes) t->tiles += cdc::read_tiles_bound(b.bytes, b.spans);
     }
     return CDC_OK;
 }
@@ -443,65 +404,57 @@ int run_reads_scrubbed(cdc_files *fs, const std::vector<HostReq> &reqs, const cd
     FL_TRY(hipSetDevice(v.device));
     hipStream_t s = stream_of(fs, hip_stream);
     const uint64_t nreq = reqs.size();
-    int rc = grow_requests(fs, nreq);
+    ReadTotals max;  // span lengths only: as unscrubbed
+    int rc = prepare_reads(fs, reqs, &max);
     if (rc) return rc;
-    uint64_t max_spans = 0, max_bytes = 0;
-    for (uint64_t i = 0; i < nreq; ++i) {
-        const HostReq &q = reqs[i];
-        uint64_t bytes = q.f->size < q.cap ? q.f->size : q.cap;
-        if (q.kind != cdc::kReadComplete && q.b < bytes) bytes = q.b;
-        max_spans += q.kind == cdc::kReadComplete ? q.f->n : spans_bound(q.f, bytes);  // span lengths only: as unscrubbed
-        max_bytes += bytes;
-    }
-    if ((rc = grow_scrubbed(fs, nreq, max_spans)) != CDC_OK) return rc;
-    for (uint64_t i = 0; i < nreq; ++i) {
-        const HostReq &q = reqs[i];
-        fs->h_req[i] = cdc::ReadReq{q.f->t.off, q.f->t.loc, q.f->n, q.a, q.b, (uint64_t)(uintptr_t)q.dst, q.cap,
-                                    (uint64_t)(uintptr_t)q.spans, q.kind, 0};
-        fs->h_rslot[i] = (uint64_t)(uintptr_t)q.f->t.slot;
-    }
+    FL_TRY(fs->xslot.grow(nreq));
+    FL_TRY(fs->xspan.grow(max.spans));
+    cdc::ReadReq *h_req = fs->req.h_req;
+    for (uint64_t i = 0; i < nreq; ++i) fs->xslot.h[i] = (uint64_t)(uintptr_t)reqs[i].f->t.slot;
     if (stale)  // nothing may be written if the read turns out to need the cleared target: spans go out after the check
-        for (uint64_t i = 0; i < nreq; ++i) fs->h_req[i].spans = 0;
-    FL_TRY(hipMemcpyAsync(fs->d_req, fs->h_req, nreq * sizeof(cdc::ReadReq), hipMemcpyHostToDevice, s));
-    FL_TRY(hipMemcpyAsync(fs->d_rslot, fs->h_rslot, nreq * 8, hipMemcpyHostToDevice, s));
-    FL_TRY(cdc::launch_files_plan_x(fs->d_req, fs->d_rslot, nreq, sv, fs->d_plan, fs->d_rcnt, fs->d_rblock, fs->d_recs,
-                                    fs->d_pcnt, fs->d_xblock, max_spans, fs->h_res, fs->d_touch, fs->h_xtot, s));
+        for (uint64_t i = 0; i < nreq; ++i) h_req[i].spans = 0;
+    auto plan = [&] {
+        return cdc::launch_files_plan_x(fs->req.d_req, fs->xslot.d, nreq, sv, fs->req.plan, fs->req.cnt, fs->req.block,
+                                        fs->xspan.items, fs->xspan.val, fs->xspan.block, max.spans, fs->req.h_res,
+                                        &fs->dw->touch, &fs->hw->x_pieces, s);
+    };
+    FL_TRY(hipMemcpyAsync(fs->req.d_req, h_req, nreq * sizeof(cdc::ReadReq), hipMemcpyHostToDevice, s));
+    FL_TRY(hipMemcpyAsync(fs->xslot.d, fs->xslot.h, nreq * 8, hipMemcpyHostToDevice, s));
+    FL_TRY(plan());
     FL_TRY(hipStreamSynchronize(s));
-    if (stale && fs->h_xtot[1])
+    if (stale && fs->hw->x_touched)
         return fail(CDC_ENOTFOUND, "file layer: the target store was cleared since these chunks were scrubbed");
     if (stale) {  // every span touched is chunk-kind: plan again, with the span output
         bool any = false;
         for (uint64_t i = 0; i < nreq; ++i) any = any || reqs[i].spans;
         if (any) {
-            for (uint64_t i = 0; i < nreq; ++i) fs->h_req[i].spans = (uint64_t)(uintptr_t)reqs[i].spans;
-            FL_TRY(hipMemcpyAsync(fs->d_req, fs->h_req, nreq * sizeof(cdc::ReadReq), hipMemcpyHostToDevice, s));
-            FL_TRY(cdc::launch_files_plan_x(fs->d_req, fs->d_rslot, nreq, sv, fs->d_plan, fs->d_rcnt, fs->d_rblock,
-                                            fs->d_recs, fs->d_pcnt, fs->d_xblock, max_spans, fs->h_res, fs->d_touch,
-                                            fs->h_xtot, s));
+            for (uint64_t i = 0; i < nreq; ++i) h_req[i].spans = (uint64_t)(uintptr_t)reqs[i].spans;
+            FL_TRY(hipMemcpyAsync(fs->req.d_req, h_req, nreq * sizeof(cdc::ReadReq), hipMemcpyHostToDevice, s));
+            FL_TRY(plan());
             FL_TRY(hipStreamSynchronize(s));
         }
     }
-    const uint64_t np = fs->h_xtot[0];
+    const uint64_t np = fs->hw->x_pieces;
     if (!np) return CDC_OK;
-    if ((rc = grow_pieces(fs, np)) != CDC_OK) return rc;
-    // A piece adds at most two ragged tiles to its whole ones.
-    FL_TRY(cdc::launch_files_copy_x(fs->d_recs, fs->d_pcnt, max_spans, sv, v.loc, (uint64_t)(uintptr_t)v.arena,
-                                    fs->d_pieces, fs->d_tstart, fs->d_pblock, np, max_bytes / cdc::kStoreTile + 2 * np,
-                                    s, (uint64_t)(uintptr_t)cmp_base, cmp_base ? fs->d_stat + 2 : nullptr));
-    if (cmp_base) FL_TRY(hipMemcpyAsync(fs->h_tot + 8, fs->d_stat + 2, 8, hipMemcpyDeviceToHost, s));
+    FL_TRY(fs->pc.grow(np));
+    FL_TRY(cdc::launch_files_copy_x(fs->xspan.items, fs->xspan.val, max.spans, sv, v.loc, (uint64_t)(uintptr_t)v.arena,
+                                    fs->pc.items, fs->pc.val, fs->pc.block, np,
+                                    cdc::read_tiles_bound(max.bytes, np), s, (uint64_t)(uintptr_t)cmp_base,
+                                    cmp_base ? &fs->dw->verify : nullptr));
+    if (cmp_base) FL_TRY(hipMemcpyAsync(&fs->hw->verify, &fs->dw->verify, sizeof(word), hipMemcpyDeviceToHost, s));
     FL_TRY(hipStreamSynchronize(s));
     return CDC_OK;
 }
 
-// Plans and copies every request in one pass; fs->h_res[i] holds the results.
-// cmp_base (verify): the destinations are compared with the file's bytes
-// instead of written; fs->h_tot[8] = the smallest destination address - cmp_base
-// at which a byte differs, ~0 when none does.
+// Plans and copies every request in one pass; fs->req.h_res[i] holds the
+// results.  cmp_base (verify): the destinations are compared with the file's
+// bytes instead of written; fs->hw->verify = the smallest destination address
+// - cmp_base at which a byte differs, ~0 when none does.
 int run_reads(cdc_files *fs, const std::vector<HostReq> &reqs, void *hip_stream, const uint8_t *cmp_base = nullptr) {
     if (cmp_base) {
         FL_TRY(hipSetDevice(cdc::store_view(fs->store).device));
-        fs->h_tot[8] = ~0ull;
-        FL_TRY(hipMemsetAsync(fs->d_stat + 2, 0xFF, 8, stream_of(fs, hip_stream)));
+        fs->hw->verify = ~0ull;
+        FL_TRY(hipMemsetAsync(&fs->dw->verify, 0xFF, sizeof(word), stream_of(fs, hip_stream)));
     }
     {
         cdc::ScrubView sv;
@@ -513,27 +466,16 @@ int run_reads(cdc_files *fs, const std::vector<HostReq> &reqs, void *hip_stream,
     FL_TRY(hipSetDevice(v.device));
     hipStream_t s = stream_of(fs, hip_stream);
     const uint64_t nreq = reqs.size();
-    int rc = grow_requests(fs, nreq);
+    ReadTotals max;
+    const int rc = prepare_reads(fs, reqs, &max);
     if (rc) return rc;
-    uint64_t max_pieces = 0, max_tiles = 0;
-    for (uint64_t i = 0; i < nreq; ++i) {
-        const HostReq &q = reqs[i];
-        cdc::ReadReq &d = fs->h_req[i];
-        d = cdc::ReadReq{q.f->t.off, q.f->t.loc, q.f->n, q.a, q.b, (uint64_t)(uintptr_t)q.dst, q.cap,
-                         (uint64_t)(uintptr_t)q.spans, q.kind, 0};
-        uint64_t bytes = q.f->size < q.cap ? q.f->size : q.cap;
-        if (q.kind != cdc::kReadComplete && q.b < bytes) bytes = q.b;
-        // Also without bytes: length-0 spans are pieces, and have entries in d_spans.
-        const uint64_t spans = q.kind == cdc::kReadComplete ? q.f->n : spans_bound(q.f, bytes);
-        max_pieces += spans;
-        if (bytes) max_tiles += bytes / cdc::kStoreTile + 2 * spans;  // a piece adds at most two ragged tiles
-    }
-    if ((rc = grow_pieces(fs, max_pieces)) != CDC_OK) return rc;
-    FL_TRY(hipMemcpyAsync(fs->d_req, fs->h_req, nreq * sizeof(cdc::ReadReq), hipMemcpyHostToDevice, s));
-    FL_TRY(cdc::launch_files_read(fs->d_req, nreq, (uint64_t)(uintptr_t)v.arena, fs->d_plan, fs->d_rcnt,
-                                  fs->d_rblock, fs->d_pieces, fs->d_tstart, fs->d_pblock, max_pieces, max_tiles,
-                                  fs->h_res, s, (uint64_t)(uintptr_t)cmp_base, cmp_base ? fs->d_stat + 2 : nullptr));
-    if (cmp_base) FL_TRY(hipMemcpyAsync(fs->h_tot + 8, fs->d_stat + 2, 8, hipMemcpyDeviceToHost, s));
+    FL_TRY(fs->pc.grow(max.spans));
+    FL_TRY(hipMemcpyAsync(fs->req.d_req, fs->req.h_req, nreq * sizeof(cdc::ReadReq), hipMemcpyHostToDevice, s));
+    FL_TRY(cdc::launch_files_read(fs->req.d_req, nreq, (uint64_t)(uintptr_t)v.arena, fs->req.plan, fs->req.cnt,
+                                  fs->req.block, fs->pc.items, fs->pc.val, fs->pc.block, max.spans, max.tiles,
+                                  fs->req.h_res, s, (uint64_t)(uintptr_t)cmp_base,
+                                  cmp_base ? &fs->dw->verify : nullptr));
+    if (cmp_base) FL_TRY(hipMemcpyAsync(&fs->hw->verify, &fs->dw->verify, sizeof(word), hipMemcpyDeviceToHost, s));
     FL_TRY(hipStreamSynchronize(s));
     return CDC_OK;
 }
@@ -547,42 +489,13 @@ int64_t read_one(cdc_fh *fh, uint32_t kind, uint64_t a, uint64_t b, uint8_t *d_o
     if (f->n == 0) return 0;
     std::vector<HostReq> reqs{HostReq{f, kind, a, b, d_out, cap, d_spans}};
     if ((rc = run_reads(fh->fs, reqs, hip_stream)) != CDC_OK) return rc;
-    return (int64_t)fh->fs->h_res[0].bytes;
+    return (int64_t)fh->fs->req.h_res[0].bytes;
 }
 
 // ---- splice ---------------------------------------------------------------------
 double *splice_split() {
     static thread_local double split[5];
     return split;
-}
-
-// The window buffer for `window` bytes, and the result words.
-int grow_splice(cdc_files *fs, uint64_t window) {
-    if (!fs->h_sp) {
-        FL_TRY(hipHostMalloc(&fs->h_sp, 4 * sizeof(unsigned long long)));
-        FL_TRY(hipMalloc(&fs->d_sp, sizeof(unsigned long long)));
-    }
-    if (fs->s_cap >= window) return CDC_OK;
-    (void)hipFree(fs->s_win);
-    fs->s_win = nullptr;
-    fs->s_cap = 0;
-    const uint64_t cap = (window + window / 8 + 4095) & ~4095ull;
-    FL_TRY(hipMalloc(&fs->s_win, cap));
-    fs->s_cap = cap;
-    return CDC_OK;
-}
-
-int grow_write(cdc_files *fs, uint64_t cap) {
-    if (fs->w_cap >= cap) return CDC_OK;
-    (void)hipFree(fs->w_chunks);
-    (void)hipFree(fs->w_dig);
-    fs->w_chunks = nullptr;
-    fs->w_dig = nullptr;
-    fs->w_cap = 0;
-    FL_TRY(hipMalloc(&fs->w_chunks, cap * sizeof(cdc_chunk_t)));
-    FL_TRY(hipMalloc(&fs->w_dig, cap * 32));
-    fs->w_cap = cap;
-    return CDC_OK;
 }
 
 int64_t splice(cdc_fh *fh, cdc_handle_t *chunker, uint64_t offset, uint64_t remove_len, const uint8_t *d_data,
@@ -592,13 +505,10 @@ int64_t splice(cdc_fh *fh, cdc_handle_t *chunker, uint64_t offset, uint64_t remo
     if (!chunker) return fail(CDC_EINVAL, "cdc_file_splice_device: NULL chunker");
     if (insert_len && !d_data) return fail(CDC_EINVAL, "cdc_file_splice_device: NULL data");
     FileRec *f = nullptr;
-    int rc = lookup(fh, false, &f);
+    int rc = writable(fh, &f);
     if (rc) return rc;
-    if (fh->readonly) return fail(CDC_EPERM, "file handle is read-only");
     cdc_files *fs = fh->fs;
     cdc::StoreView v = cdc::store_view(fs->store);
-    if (f->n && f->epoch != v.epoch)
-        return fail(CDC_ENOTFOUND, "file layer: the store was cleared since '" + fh->name + "' was written");
     const uint64_t n = f->n, size = f->size;
     if (offset > size)
         return fail(CDC_EINVAL, "cdc_file_splice_device: offset " + std::to_string(offset) + " is past the file's " +
@@ -629,15 +539,14 @@ int64_t splice(cdc_fh *fh, cdc_handle_t *chunker, uint64_t offset, uint64_t remo
         split[phase] += std::chrono::duration<double, std::milli>(now - last).count();
         last = now;
     };
-    if ((rc = grow_splice(fs, 0)) != CDC_OK) return rc;
 
     // 1. The start span.
     uint64_t i0 = 0, w0 = 0;
     if (n) {
-        FL_TRY(cdc::launch_splice_start(f->t.off, n, offset, fs->h_sp, s));
+        FL_TRY(cdc::launch_splice_start(f->t.off, n, offset, &fs->hw->i0, s));
         FL_TRY(hipStreamSynchronize(s));
-        i0 = fs->h_sp[0];
-        w0 = fs->h_sp[1];
+        i0 = fs->hw->i0;
+        w0 = fs->hw->w0;
     }
 
     // 2, 3. Windows of the new file from off[i0] on, until a trusted cut meets an old one.
@@ -648,35 +557,36 @@ int64_t splice(cdc_fh *fh, cdc_handle_t *chunker, uint64_t offset, uint64_t remo
     for (uint32_t round = 1; size_after > w0; ++round) {
         const uint64_t end_w = cdc::splice_window_end(size_after, offset, insert_len, maxc, round);
         wlen = end_w - w0;
-        if ((rc = grow_splice(fs, wlen)) != CDC_OK) return rc;
-        streams[0] = fs->s_win;
+        if (fs->window.cap < wlen) FL_TRY(fs->window.room((wlen + wlen / 8 + 4095) & ~4095ull));
+        uint8_t *win = fs->window;
+        streams[0] = win;
         std::vector<HostReq> reqs;
-        if (offset > w0) reqs.push_back(HostReq{f, cdc::kReadRange, w0, offset - w0, fs->s_win, offset - w0, nullptr});
+        if (offset > w0) reqs.push_back(HostReq{f, cdc::kReadRange, w0, offset - w0, win, offset - w0, nullptr});
         if (end_w > lo)
-            reqs.push_back(HostReq{f, cdc::kReadRange, offset + remove_len, end_w - lo, fs->s_win + (lo - w0),
-                                   end_w - lo, nullptr});
+            reqs.push_back(HostReq{f, cdc::kReadRange, offset + remove_len, end_w - lo, win + (lo - w0), end_w - lo,
+                                   nullptr});
         if (!reqs.empty() && (rc = run_reads(fs, reqs, hip_stream)) != CDC_OK) return rc;
         if (insert_len)
-            FL_TRY(hipMemcpyAsync(fs->s_win + (offset - w0), d_data, insert_len, hipMemcpyDeviceToDevice, s));
+            FL_TRY(hipMemcpyAsync(win + (offset - w0), d_data, insert_len, hipMemcpyDeviceToDevice, s));
         lap(0);
         const uint64_t lens[1] = {wlen};
         const uint64_t cap = cdc_batch_max_chunks(chunker, 1, lens);
-        if ((rc = grow_write(fs, cap)) != CDC_OK) return rc;
+        FL_TRY(fs->wr.grow(cap));
         uint64_t first[2] = {0, 0};
-        const int64_t cnt = cdc_chunk_batch_device(chunker, 1, streams, lens, fs->w_chunks, cap, first, s);
+        const int64_t cnt = cdc_chunk_batch_device(chunker, 1, streams, lens, fs->wr.chunks, cap, first, s);
         if (cnt < 0) return cnt;
         window_bytes += wlen;
         rounds = round;
         lap(1);
         const cdc::SpliceRound r{w0, end_w, size_after, offset, remove_len, insert_len, maxc};
-        FL_TRY(cdc::launch_splice_resync(reinterpret_cast<const cdc::cdc_chunk_pod *>(fs->w_chunks), (uint64_t)cnt, r,
-                                         f->t.off, n, fs->d_sp, fs->h_sp, s));
+        FL_TRY(cdc::launch_splice_resync(reinterpret_cast<const cdc::cdc_chunk_pod *>(fs->wr.chunks.p), (uint64_t)cnt,
+                                         r, f->t.off, n, &fs->dw->best, &fs->hw->resync_k, s));
         FL_TRY(hipStreamSynchronize(s));
         lap(2);
-        if (fs->h_sp[0] != ~0ull) {
-            m = fs->h_sp[0] + 1;
-            j = fs->h_sp[1];
-            e = fs->h_sp[2];
+        if (fs->hw->resync_k != ~0ull) {
+            m = fs->hw->resync_k + 1;
+            j = fs->hw->resync_j;
+            e = fs->hw->resync_e;
             break;
         }
         if (end_w == size_after)  // the last cut of a window that ends with the file is the file's end
@@ -688,18 +598,13 @@ int64_t splice(cdc_fh *fh, cdc_handle_t *chunker, uint64_t offset, uint64_t remo
     uint64_t bytes_new = 0;
     if (m) {
         const uint64_t hfirst[2] = {0, m};
-        if ((rc = cdc_sha256_batch_device(chunker, 1, streams, hfirst, fs->w_chunks, fs->w_dig, s)) != CDC_OK) return rc;
+        if ((rc = cdc_sha256_batch_device(chunker, 1, streams, hfirst, fs->wr.chunks, fs->wr.dig, s)) != CDC_OK) return rc;
         const bool patch = m == j - i0 && insert_len == remove_len;
         cdc::SpanTable nt = f->t;
         uint64_t cap = f->cap;
         if (!patch) {
-            if (!cap) cap = kTableMinCap;
-            while (cap < n_new) cap *= 2;
-            const hipError_t he = fs->pool.take(cap, &nt);
-            if (he != hipSuccess) {
-                cdc::set_error(std::string("file layer: span table for the splice: ") + hipGetErrorString(he));
-                return he == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE;
-            }
+            cap = table_cap(cap, n_new);
+            if ((rc = take_table(fs, cap, &nt, "file layer: span table for the splice: ")) != CDC_OK) return rc;
         }
         struct Guard {  // the fresh table goes back unless the call succeeds
             cdc_files *fs;
@@ -709,21 +614,21 @@ int64_t splice(cdc_fh *fh, cdc_handle_t *chunker, uint64_t offset, uint64_t remo
                 if (cap) fs->pool.give(t, cap);
             }
         } guard{fs, nt, patch ? 0 : cap};
-        if ((rc = grow_span_scratch(fs, m)) != CDC_OK) return rc;
+        FL_TRY(fs->span.grow(m));
         cdc_store_stats_t before{}, after{};
         (void)cdc_store_stats(fs->store, &before);
-        const int64_t put = cdc::store_put_slots(fs->store, fs->s_win, wlen, fs->w_chunks, fs->w_dig, m, hip_stream);
+        const int64_t put = cdc::store_put_slots(fs->store, fs->window, wlen, fs->wr.chunks, fs->wr.dig, m, hip_stream);
         if (put < 0) return put;  // refused: the file and its table are as they were
         (void)cdc_store_stats(fs->store, &after);
         bytes_new = after.index.unique_bytes - before.index.unique_bytes;
         v = cdc::store_view(fs->store);
         lap(3);
-        hipError_t he = hipMemsetAsync(fs->d_stat, 0xFF, 8, s);
-        if (he == hipSuccess) he = hipMemsetAsync(fs->d_stat + 1, 0, 8, s);
+        hipError_t he = preset_stat(fs, s);
         if (he == hipSuccess)
             he = cdc::launch_splice_build(f->t, n, size, nt, i0, j, w0, remove_len, insert_len, v.slot_of, v.length,
-                                          v.loc, fs->w_dig, m, fs->a_val, fs->a_block, fs->d_stat, fs->h_tot, s);
-        if (he == hipSuccess) he = hipMemcpyAsync(fs->h_tot + 2, fs->d_stat, 16, hipMemcpyDeviceToHost, s);
+                                          v.loc, fs->wr.dig, m, fs->span.val, fs->span.block, &fs->dw->least,
+                                          &fs->hw->appended, s);
+        if (he == hipSuccess) he = fetch_stat(fs, s);
         const hipError_t hs = hipStreamSynchronize(s);  // also on failure: nothing queued still writes the fresh table
         if (he == hipSuccess) he = hs;
         if (he != hipSuccess) {
@@ -736,8 +641,7 @@ int64_t splice(cdc_fh *fh, cdc_handle_t *chunker, uint64_t offset, uint64_t remo
             f->cap = cap;
             guard.cap = 0;
         }
-        if (fs->h_tot[2] != ~0ull && fs->h_tot[2] + 1 < f->min_len) f->min_len = fs->h_tot[2] + 1;
-        f->zeros += fs->h_tot[3];
+        fold_stat(f, fs->hw->least, fs->hw->zeros);
         lap(4);
     } else {
         free_table(fs, f);  // nothing is left after off[i0] = 0: the file is empty
@@ -758,22 +662,14 @@ int64_t splice(cdc_fh *fh, cdc_handle_t *chunker, uint64_t offset, uint64_t remo
 // tiles to its whole ones.  The mask is 64 words per tile: one bit per compared
 // byte plus, per piece, the two tiles' worth that its ends may leave unused.
 int grow_diff(cdc_files *fs, uint64_t na, uint64_t nb, uint64_t common, bool tables_only, cdc::DiffScratch *w) {
-    if (!fs->h_df) FL_TRY(hipHostMalloc(&fs->h_df, 8 * sizeof(unsigned long long)));
     const uint64_t nc = cdc::diff_candidates(na, nb), mp = na + nb;
     const uint64_t mt = tables_only ? 0 : common / cdc::kStoreTile + 2 * mp;
     const uint64_t words = 4 /* acc */ + nc + 4 * mp /* pstart, pflag, tstart, cx */ + 3 * mp /* cp */ +
                            mt * (1 + cdc::kDiffTileWords) + cdc::store_scan_blocks(nc) + 1 +
                            2 * (cdc::store_scan_blocks(mp) + 1) + cdc::store_scan_blocks(mt) + 1;
     const uint64_t bytes = words * 8 + 3 * mp * 4 /* pia, pib, cflag */;
-    if (fs->df_bytes < bytes) {
-        (void)hipFree(fs->df_mem);
-        fs->df_mem = nullptr;
-        fs->df_bytes = 0;
-        const uint64_t cap = bytes + bytes / 8;
-        FL_TRY(hipMalloc(&fs->df_mem, cap));
-        fs->df_bytes = cap;
-    }
-    uint64_t *p = reinterpret_cast<uint64_t *>(fs->df_mem);
+    if (fs->diff.cap < bytes) FL_TRY(fs->diff.room(bytes + bytes / 8));
+    uint64_t *p = reinterpret_cast<uint64_t *>(fs->diff.p);
     auto take = [&p](uint64_t n) {
         uint64_t *r = p;
         p += n;
@@ -810,39 +706,51 @@ int grow_diff(cdc_files *fs, uint64_t na, uint64_t nb, uint64_t common, bool tab
 
 extern "C" {
 
+int cdc_files_create(cdc_store_t *store, size_t seg_size, cdc_files_t **out) {
+    if (!out) return fail(CDC_EINVAL, "cdc_files_create: out is NULL");
+    *out = nullptr;
+    if (!store) return fail(CDC_EINVAL, "cdc_files_create: store is NULL");
+    cdc_files *fs = new cdc_files();
+    fs->store = store;
+    fs->seg = seg_size ? seg_size : (1u << 20);
+    fs->device = cdc::store_view(store).device;
+    hipError_t e = hipSetDevice(fs->device);
+    if (e == hipSuccess) e = fs->hw.room(1);
+    if (e == hipSuccess) e = fs->dw.room(1);
+    if (e != hipSuccess) {
+        delete fs;
+        return fail_hip("cdc_files_create: ", e);
+    }
+    *out = fs;
+    return CDC_OK;
+}
+
+void cdc_files_destroy(cdc_files_t *fs) {
+    if (fs) release(fs);
+}
+
 int64_t cdc_files_clone(cdc_files_t *fs, const char *src, const char *dst, void *hip_stream) {
     if (!fs || !src || !dst) return fail(CDC_EINVAL, "cdc_files_clone: NULL argument");
     auto it = fs->files.find(src);
     if (it == fs->files.end()) return fail(CDC_ENOTFOUND, std::string("file layer: no file named '") + src + "'");
     const FileRec *from = it->second;
-    const cdc::StoreView v = cdc::store_view(fs->store);
-    if (from->n && from->epoch != v.epoch)
-        return fail(CDC_ENOTFOUND, std::string("file layer: the store was cleared since '") + src + "' was written");
+    int rc = check_epoch(fs, from, src);
+    if (rc) return rc;
     if (fs->files.count(dst)) return fail(CDC_EEXIST, std::string("file layer: '") + dst + "' already exists");
     FileRec made = *from;  // n, size, epoch, min_len, zeros; the table is its own
     made.t = cdc::SpanTable{};
     made.cap = 0;
     if (from->n) {
-        FL_TRY(hipSetDevice(v.device));
+        FL_TRY(hipSetDevice(cdc::store_view(fs->store).device));
         hipStream_t s = stream_of(fs, hip_stream);
-        uint64_t cap = kTableMinCap;
-        while (cap < from->n) cap *= 2;
-        hipError_t e = fs->pool.take(cap, &made.t);
-        if (e != hipSuccess) {
-            cdc::set_error(std::string("cdc_files_clone: span table: ") + hipGetErrorString(e));
-            return e == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE;
-        }
-        const uint64_t n = from->n;
-        e = hipMemcpyAsync(made.t.off, from->t.off, (n + 1) * 8, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(made.t.digest, from->t.digest, n * 32, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(made.t.loc, from->t.loc, n * 8, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(made.t.slot, from->t.slot, n * 4, hipMemcpyDeviceToDevice, s);
+        const uint64_t cap = table_cap(0, from->n);
+        if ((rc = take_table(fs, cap, &made.t, "cdc_files_clone: span table: ")) != CDC_OK) return rc;
+        hipError_t e = copy_spans(made.t, from->t, from->n, s);
         const hipError_t hs = hipStreamSynchronize(s);  // also on failure: nothing queued still writes the table
         if (e == hipSuccess) e = hs;
         if (e != hipSuccess) {
             fs->pool.give(made.t, cap);
-            cdc::set_error(std::string("cdc_files_clone: table copy: ") + hipGetErrorString(e));
-            return e == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE;
+            return fail_hip("cdc_files_clone: table copy: ", e);
         }
         made.cap = cap;
     }
@@ -895,46 +803,22 @@ int64_t cdc_files_diff_device(cdc_fh_t *a, cdc_fh_t *b, uint32_t flags, cdc_chun
         const cdc::DiffSide da{fa->t.off, fa->t.loc, fa->t.slot, fa->n, fa->size};
         const cdc::DiffSide db{fb->t.off, fb->t.loc, fb->t.slot, fb->n, fb->size};
         const hipError_t e = cdc::launch_files_diff(da, db, (uint64_t)(uintptr_t)v.arena, tables_only, w,
-                                                    reinterpret_cast<cdc::cdc_chunk_pod *>(d_ranges), cap, fs->h_df, s);
+                                                    reinterpret_cast<cdc::cdc_chunk_pod *>(d_ranges), cap,
+                                                    &fs->hw->ranges, s);
         const hipError_t hs = hipStreamSynchronize(s);  // the one wait of the call
         if (e != hipSuccess || hs != hipSuccess) {
             cdc::set_error(std::string("cdc_files_diff_device: ") + hipGetErrorString(e != hipSuccess ? e : hs));
             return CDC_EDEVICE;
         }
-        r.ranges = fs->h_df[0];
-        r.bytes_differing = fs->h_df[1];
-        r.bytes_compared = fs->h_df[2];
-        r.bytes_shared = fs->h_df[3];
-        r.pieces = fs->h_df[4];
+        r.ranges = fs->hw->ranges;
+        r.bytes_differing = fs->hw->bytes_differing;
+        r.bytes_compared = fs->hw->bytes_compared;
+        r.bytes_shared = fs->hw->bytes_shared;
+        r.pieces = fs->hw->pieces;
     }
     r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (stats) *stats = r;
     return (int64_t)r.ranges;
-}
-
-int cdc_files_create(cdc_store_t *store, size_t seg_size, cdc_files_t **out) {
-    if (!out) return fail(CDC_EINVAL, "cdc_files_create: out is NULL");
-    *out = nullptr;
-    if (!store) return fail(CDC_EINVAL, "cdc_files_create: store is NULL");
-    cdc_files *fs = new cdc_files();
-    fs->store = store;
-    fs->seg = seg_size ? seg_size : (1u << 20);
-    fs->device = cdc::store_view(store).device;
-    hipError_t e = hipSetDevice(fs->device);
-    if (e == hipSuccess) e = hipHostMalloc(&fs->h_tot, 12 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc(&fs->d_stat, 4 * sizeof(unsigned long long));
-    if (e != hipSuccess) {
-        (void)hipHostFree(fs->h_tot);
-        delete fs;
-        return fail(e == hipErrorOutOfMemory ? CDC_ENOMEM : CDC_EDEVICE,
-                    std::string("cdc_files_create: ") + hipGetErrorString(e));
-    }
-    *out = fs;
-    return CDC_OK;
-}
-
-void cdc_files_destroy(cdc_files_t *fs) {
-    if (fs) release(fs);
 }
 
 int64_t cdc_debug_files_table_blocks(const cdc_files_t *fs) {
@@ -1091,25 +975,16 @@ int64_t cdc_file_write_device(cdc_fh_t *fh, cdc_handle_t *chunker, const uint8_t
     const uint64_t lens[1] = {len};
     const uint8_t *streams[1] = {d_data};
     const uint64_t cap = cdc_batch_max_chunks(chunker, 1, lens);
-    if (fs->w_cap < cap) {
-        (void)hipFree(fs->w_chunks);
-        (void)hipFree(fs->w_dig);
-        fs->w_chunks = nullptr;
-        fs->w_dig = nullptr;
-        fs->w_cap = 0;
-        FL_TRY(hipMalloc(&fs->w_chunks, cap * sizeof(cdc_chunk_t)));
-        FL_TRY(hipMalloc(&fs->w_dig, cap * 32));
-        fs->w_cap = cap;
-    }
+    FL_TRY(fs->wr.grow(cap));
     uint64_t first[2] = {0, 0};
     const auto t0 = std::chrono::steady_clock::now();
-    const int64_t n = cdc_chunk_batch_device(chunker, 1, streams, lens, fs->w_chunks, cap, first, s);
+    const int64_t n = cdc_chunk_batch_device(chunker, 1, streams, lens, fs->wr.chunks, cap, first, s);
     if (n < 0) return n;
     const auto t1 = std::chrono::steady_clock::now();
-    rc = cdc_sha256_batch_device(chunker, 1, streams, first, fs->w_chunks, fs->w_dig, s);
+    rc = cdc_sha256_batch_device(chunker, 1, streams, first, fs->wr.chunks, fs->wr.dig, s);
     if (rc) return rc;
     const auto t2 = std::chrono::steady_clock::now();
-    const int64_t got = append(fh, d_data, len, fs->w_chunks, fs->w_dig, (uint64_t)n, s);
+    const int64_t got = append(fh, d_data, len, fs->wr.chunks, fs->wr.dig, (uint64_t)n, s);
     if (got < 0) return got;
     fh->chunk_s += std::chrono::duration<double>(t1 - t0).count();
     fh->hash_s += std::chrono::duration<double>(t2 - t1).count();
@@ -1160,11 +1035,8 @@ int64_t cdc_files_write_batch_device(cdc_files_t *fs, cdc_handle_t *chunker, siz
         cdc_fh *fh = reqs[i].fh;
         if (fh && fh->fs && fh->fs != fs)
             return fail(CDC_EINVAL, "cdc_files_write_batch_device: a handle of another layer");
-        const int rc = lookup(fh, false, &recs[i]);
+        const int rc = writable(fh, &recs[i]);
         if (rc) return rc;
-        if (fh->readonly) return fail(CDC_EPERM, "file handle is read-only");
-        if (recs[i]->n && recs[i]->epoch != v.epoch)
-            return fail(CDC_ENOTFOUND, "file layer: the store was cleared since '" + fh->name + "' was written");
         if (reqs[i].len && !reqs[i].d_data) return fail(CDC_EINVAL, "cdc_files_write_batch_device: NULL data");
         if (!seen.insert(recs[i]).second)
             return fail(CDC_EINVAL, "cdc_files_write_batch_device: '" + fh->name + "' is named twice");
@@ -1182,30 +1054,21 @@ int64_t cdc_files_write_batch_device(cdc_files_t *fs, cdc_handle_t *chunker, siz
     FL_TRY(hipSetDevice(v.device));
     hipStream_t s = stream_of(fs, hip_stream);
     const uint64_t cap = cdc_batch_max_chunks(chunker, ns, lens.data());
-    if (fs->w_cap < cap) {
-        (void)hipFree(fs->w_chunks);
-        (void)hipFree(fs->w_dig);
-        fs->w_chunks = nullptr;
-        fs->w_dig = nullptr;
-        fs->w_cap = 0;
-        FL_TRY(hipMalloc(&fs->w_chunks, cap * sizeof(cdc_chunk_t)));
-        FL_TRY(hipMalloc(&fs->w_dig, cap * 32));
-        fs->w_cap = cap;
-    }
+    FL_TRY(fs->wr.grow(cap));
     std::vector<uint64_t> sfirst(ns + 1, 0);
     const auto t0 = std::chrono::steady_clock::now();
-    const int64_t m = cdc_chunk_batch_device(chunker, ns, streams.data(), lens.data(), fs->w_chunks, cap,
+    const int64_t m = cdc_chunk_batch_device(chunker, ns, streams.data(), lens.data(), fs->wr.chunks, cap,
                                              sfirst.data(), s);
     if (m < 0) return m;
     const auto t1 = std::chrono::steady_clock::now();
-    int rc = cdc_sha256_batch_device(chunker, ns, streams.data(), sfirst.data(), fs->w_chunks, fs->w_dig, s);
+    int rc = cdc_sha256_batch_device(chunker, ns, streams.data(), sfirst.data(), fs->wr.chunks, fs->wr.dig, s);
     if (rc) return rc;
     const auto t2 = std::chrono::steady_clock::now();
 
     // Room for every file's new spans (the contents stay as they are), then the one put.
-    if ((rc = grow_batch(fs, n)) != CDC_OK) return rc;
-    if ((rc = grow_span_scratch(fs, (uint64_t)m)) != CDC_OK) return rc;
-    uint64_t *h_first = reinterpret_cast<uint64_t *>(fs->h_batch);
+    FL_TRY(fs->batch.grow(n));
+    FL_TRY(fs->span.grow((uint64_t)m));
+    uint64_t *h_first = reinterpret_cast<uint64_t *>(fs->batch.h.p);
     cdc::AppendDst *h_dst = reinterpret_cast<cdc::AppendDst *>(h_first + n + 1);
     cdc::AppendStat *h_stat = reinterpret_cast<cdc::AppendStat *>(h_dst + n);
     bool copied = false;
@@ -1221,19 +1084,19 @@ int64_t cdc_files_write_batch_device(cdc_files_t *fs, cdc_handle_t *chunker, siz
     }
     if (copied) FL_TRY(hipStreamSynchronize(s));
     const int64_t put = cdc::store_put_batch_slots(fs->store, ns, streams.data(), lens.data(), sfirst.data(),
-                                                   fs->w_chunks, fs->w_dig, s);
+                                                   fs->wr.chunks, fs->wr.dig, s);
     if (put < 0) return put;  // refused: every file is as it was
     v = cdc::store_view(fs->store);
     for (size_t i = 0; i < n; ++i) {
         h_dst[i] = cdc::AppendDst{recs[i]->t, recs[i]->n, recs[i]->size};
         h_stat[i] = cdc::AppendStat{0, ~0ull, 0};
     }
-    uint64_t *d_first = reinterpret_cast<uint64_t *>(fs->d_batch);
+    uint64_t *d_first = reinterpret_cast<uint64_t *>(fs->batch.d.p);
     cdc::AppendDst *d_dst = reinterpret_cast<cdc::AppendDst *>(d_first + n + 1);
     cdc::AppendStat *d_stat = reinterpret_cast<cdc::AppendStat *>(d_dst + n);
-    FL_TRY(hipMemcpyAsync(fs->d_batch, fs->h_batch, batch_bytes(n), hipMemcpyHostToDevice, s));
-    FL_TRY(cdc::launch_files_append_batch(d_dst, d_first, n, (uint64_t)m, v.slot_of, v.length, v.loc, fs->w_dig,
-                                          fs->a_val, fs->a_block, d_stat, s));
+    FL_TRY(hipMemcpyAsync(fs->batch.d, fs->batch.h, batch_bytes(n), hipMemcpyHostToDevice, s));
+    FL_TRY(cdc::launch_files_append_batch(d_dst, d_first, n, (uint64_t)m, v.slot_of, v.length, v.loc, fs->wr.dig,
+                                          fs->span.val, fs->span.block, d_stat, s));
     FL_TRY(hipMemcpyAsync(h_stat, d_stat, n * sizeof(cdc::AppendStat), hipMemcpyDeviceToHost, s));
     FL_TRY(hipStreamSynchronize(s));
     const double chunk_s = std::chrono::duration<double>(t1 - t0).count();
@@ -1249,8 +1112,7 @@ int64_t cdc_files_write_batch_device(cdc_files_t *fs, cdc_handle_t *chunker, siz
         f->n += cnt;
         f->size += h_stat[i].bytes;
         f->epoch = v.epoch;
-        if (h_stat[i].least != ~0ull && h_stat[i].least + 1 < f->min_len) f->min_len = h_stat[i].least + 1;
-        f->zeros += h_stat[i].zeros;
+        fold_stat(f, h_stat[i].least, h_stat[i].zeros);
     }
     return m;
 }
@@ -1289,7 +1151,7 @@ int cdc_files_pread_batch_device(cdc_files_t *fs, size_t n, const cdc_pread_t *r
     }
     const int rc = run_reads(fs, v, hip_stream);
     if (rc) return rc;
-    for (size_t i = 0; i < n; ++i) got[i] = fs->h_res[i].bytes;
+    for (size_t i = 0; i < n; ++i) got[i] = fs->req.h_res[i].bytes;
     return CDC_OK;
 }
 
@@ -1319,12 +1181,12 @@ int64_t cdc_file_distribution_device(cdc_fh_t *fh, uint8_t *d_digests, uint32_t 
     FL_TRY(hipSetDevice(v.device));
     hipStream_t s = stream_of(fs, hip_stream);
     const uint64_t m = f->n - 1;
-    if ((rc = grow_span_scratch(fs, m)) != CDC_OK) return rc;
-    if ((rc = grow_slot_scratch(fs, v.slots)) != CDC_OK) return rc;
-    FL_TRY(cdc::launch_files_distribution(f->t, m, fs->d_cnt, fs->d_first, fs->a_val, fs->a_block, d_digests,
-                                          d_counts, d_lengths, cap, fs->h_tot + 1, s));
+    FL_TRY(fs->span.grow(m));
+    FL_TRY(fs->slot.grow(v.slots));
+    FL_TRY(cdc::launch_files_distribution(f->t, m, fs->slot.cnt, fs->slot.first, fs->span.val, fs->span.block,
+                                          d_digests, d_counts, d_lengths, cap, &fs->hw->distinct, s));
     FL_TRY(hipStreamSynchronize(s));
-    return (int64_t)fs->h_tot[1];
+    return (int64_t)fs->hw->distinct;
 }
 
 int64_t cdc_file_verify_device(cdc_fh_t *fh, const uint8_t *d_data, size_t len, uint64_t *first_diff,
@@ -1341,7 +1203,7 @@ int64_t cdc_file_verify_device(cdc_fh_t *fh, const uint8_t *d_data, size_t len, 
         std::vector<HostReq> reqs{
             HostReq{f, cdc::kReadRange, 0, common, const_cast<uint8_t *>(d_data), common, nullptr}};
         if ((rc = run_reads(fh->fs, reqs, hip_stream, d_data)) != CDC_OK) return rc;
-        diff = fh->fs->h_tot[8];
+        diff = fh->fs->hw->verify;
     }
     if (diff == ~0ull && f->size != len) diff = common;
     if (first_diff) *first_diff = diff;
@@ -1357,9 +1219,9 @@ int64_t cdc_files_get_to_dedup_ratio(cdc_files_t *fs, const char *name, double d
     auto it = fs->files.find(name);
     if (it == fs->files.end()) return fail(CDC_ENOTFOUND, std::string("file with name `") + name + "` not found");
     FileRec *src = it->second;
+    int rc = check_epoch(fs, src, name);
+    if (rc) return rc;
     const cdc::StoreView v = cdc::store_view(fs->store);
-    if (src->n && src->epoch != v.epoch)
-        return fail(CDC_ENOTFOUND, std::string("file layer: the store was cleared since '") + name + "' was written");
     char suffix[400];  // "%.2f" of the largest double has 312 characters
     std::snprintf(suffix, sizeof suffix, ".%.2f", dedup_ratio);
     const std::string new_name = std::string(name) + suffix;
@@ -1379,17 +1241,16 @@ int64_t cdc_files_get_to_dedup_ratio(cdc_files_t *fs, const char *name, double d
     if (src->n >= 2) {
         // 1. The unique list over all but the last span (the reference's zip with skip(1)).
         const uint64_t m = src->n - 1;
-        int rc = grow_span_scratch(fs, m);
-        if (rc) return rc;
-        if ((rc = grow_slot_scratch(fs, v.slots)) != CDC_OK) return rc;
+        FL_TRY(fs->span.grow(m));
+        FL_TRY(fs->slot.grow(v.slots));
         uint64_t *uidx = nullptr, *ulen = nullptr, *ublock = nullptr, *sidx = nullptr;
         FL_TRY(mem.alloc(&uidx, m));
         FL_TRY(mem.alloc(&ulen, m));
         FL_TRY(mem.alloc(&ublock, cdc::store_scan_blocks(m) + 1));
-        FL_TRY(cdc::launch_files_ratio_unique(src->t, m, fs->d_cnt, fs->d_first, fs->a_val, fs->a_block, uidx, ulen,
-                                              ublock, fs->h_tot + 4, s));
+        FL_TRY(cdc::launch_files_ratio_unique(src->t, m, fs->slot.cnt, fs->slot.first, fs->span.val, fs->span.block,
+                                              uidx, ulen, ublock, &fs->hw->unique, s));
         FL_TRY(hipStreamSynchronize(s));
-        const uint64_t U = fs->h_tot[4], unique_length = fs->h_tot[5];
+        const uint64_t U = fs->hw->unique, unique_length = fs->hw->unique_length;
         if (U) {
             // 2. file_layer.rs:233-237, in f64 as written there (`as usize` saturates).
             const double want = (double)unique_length * dedup_ratio;
@@ -1399,9 +1260,9 @@ int64_t cdc_files_get_to_dedup_ratio(cdc_files_t *fs, const char *name, double d
             if (R > U) R = U;  // take(num_repeating) of U entries
             uint64_t K = 0;
             if (R) {
-                FL_TRY(cdc::launch_files_ratio_take(ulen, ublock, m, R, total_size, fs->h_tot + 6, s));
+                FL_TRY(cdc::launch_files_ratio_take(ulen, ublock, m, R, total_size, &fs->hw->cycle, s));
                 FL_TRY(hipStreamSynchronize(s));
-                const uint64_t C = fs->h_tot[6], j = fs->h_tot[7];
+                const uint64_t C = fs->hw->cycle, j = fs->hw->partial;
                 if (C == 0)
                     return fail(CDC_EINVAL, "cdc_files_get_to_dedup_ratio: the repeating spans are all empty "
                                             "(the reference's cycle would never end)");
@@ -1414,18 +1275,16 @@ int64_t cdc_files_get_to_dedup_ratio(cdc_files_t *fs, const char *name, double d
             // 3. The new table: gather, scan, write.
             if (n) {
                 if ((rc = reserve(fs, &made, n, s)) != CDC_OK) return rc;
-                if ((rc = grow_span_scratch(fs, n)) != CDC_OK) return rc;
+                FL_TRY(fs->span.grow(n));
                 FL_TRY(mem.alloc(&sidx, n));
-                FL_TRY(hipMemsetAsync(fs->d_stat, 0xFF, 8, s));
-                FL_TRY(hipMemsetAsync(fs->d_stat + 1, 0, 8, s));
-                FL_TRY(cdc::launch_files_ratio_gather(src->t, made.t, uidx, K, R, n, sidx, fs->a_val, fs->a_block,
-                                                      fs->d_stat, fs->h_tot, s));
-                FL_TRY(hipMemcpyAsync(fs->h_tot + 2, fs->d_stat, 16, hipMemcpyDeviceToHost, s));
+                FL_TRY(preset_stat(fs, s));
+                FL_TRY(cdc::launch_files_ratio_gather(src->t, made.t, uidx, K, R, n, sidx, fs->span.val, fs->span.block,
+                                                      &fs->dw->least, &fs->hw->appended, s));
+                FL_TRY(fetch_stat(fs, s));
                 FL_TRY(hipStreamSynchronize(s));
                 made.n = n;
-                made.size = fs->h_tot[0];
-                if (fs->h_tot[2] != ~0ull) made.min_len = fs->h_tot[2] + 1;
-                made.zeros = fs->h_tot[3];
+                made.size = fs->hw->appended;
+                fold_stat(&made, fs->hw->least, fs->hw->zeros);
             }
         }
     }

@@ -30,16 +30,14 @@ struct cdc_store {
     uint64_t arena_used = 0;
     uint64_t *d_acc = nullptr;     // [12]: 0..4 index accumulators, 5 arena bytes taken, 8..11 precheck / lookup results
     uint32_t *d_pending = nullptr;
-    // per-call scratch, grown to the largest n seen
+    // per-call scratch, grown to the largest n seen; n_cap is 0 after a growth that failed
     uint64_t n_cap = 0;
-    uint32_t *d_slot = nullptr;          // [n_cap]
-    uint8_t *d_new = nullptr;            // [n_cap]
-    cdc::StorePiece *d_pieces = nullptr; // [n_cap]
-    uint64_t *d_val = nullptr;           // [n_cap]
-    uint64_t *d_tstart = nullptr;        // [n_cap]
-    uint64_t *d_block = nullptr;         // [store_scan_blocks(n_cap) + 1]
-    uint64_t s_cap = 0;
-    uint64_t *d_streams = nullptr;       // [3 * s_cap + 1]: stream addresses, lens, first
+    cdc::DeviceBuf<uint32_t> d_slot;           // [n_cap]
+    cdc::DeviceBuf<uint8_t> d_new;             // [n_cap]
+    cdc::DeviceBuf<cdc::StorePiece> d_pieces;  // [n_cap]
+    cdc::DeviceBuf<uint64_t> d_val, d_tstart;  // [n_cap]
+    cdc::DeviceBuf<uint64_t> d_block;          // [store_scan_blocks(n_cap) + 1]
+    cdc::DeviceBuf<uint64_t> d_streams;        // [3 * n_streams + 1]: stream addresses, lens, first
     std::vector<uint64_t> h_streams;     // host image of d_streams
     hipStream_t stream = nullptr;
     cdc_index_stats_t st{};
@@ -52,10 +50,7 @@ struct cdc_store {
     uint64_t key_cap = 0, keys_used = 0;
     uint64_t target_containers = 0;
     uint64_t scrubbed_bytes = 0;   // unique bytes whose containers are target-kind now
-    // get through targets: per-piece scratch
-    uint64_t x_cap = 0;
-    cdc::StorePiece *x_pieces = nullptr;
-    uint64_t *x_tstart = nullptr, *x_block = nullptr;
+    cdc::ScanScratch<cdc::StorePiece> x;  // get through targets: per piece, with the tile counts
 };
 
 namespace {
@@ -85,20 +80,6 @@ int reset(cdc_store *st) {
     return CDC_OK;
 }
 
-void free_scratch(cdc_store *st) {
-    (void)hipFree(st->d_slot);
-    (void)hipFree(st->d_new);
-    (void)hipFree(st->d_pieces);
-    (void)hipFree(st->d_val);
-    (void)hipFree(st->d_tstart);
-    (void)hipFree(st->d_block);
-    st->d_slot = nullptr;
-    st->d_new = nullptr;
-    st->d_pieces = nullptr;
-    st->d_val = st->d_tstart = st->d_block = nullptr;
-    st->n_cap = 0;
-}
-
 void release(cdc_store *st) {
     (void)hipSetDevice(st->device);
     (void)hipFree(st->t.tag);
@@ -109,18 +90,13 @@ void release(cdc_store *st) {
     (void)hipFree(st->arena);
     (void)hipFree(st->d_acc);
     (void)hipFree(st->d_pending);
-    (void)hipFree(st->d_streams);
     (void)hipFree(st->sc.kind);
     (void)hipFree(st->sc.key_first);
     (void)hipFree(st->sc.key_count);
     (void)hipFree(st->sc.key_slot);
     (void)hipFree(st->sc.key_off);
-    (void)hipFree(st->x_pieces);
-    (void)hipFree(st->x_tstart);
-    (void)hipFree(st->x_block);
-    free_scratch(st);
     if (st->stream) (void)hipStreamDestroy(st->stream);
-    delete st;
+    delete st;  // the per-call scratch goes with it, the device still current
 }
 
 int create(int device, size_t max_chunks, size_t arena_bytes, cdc_store **out) {
@@ -165,16 +141,9 @@ int create(int device, size_t max_chunks, size_t arena_bytes, cdc_store **out) {
 
 // Scratch for a call over n chunks / digests.
 int grow(cdc_store *st, uint64_t n) {
-    if (st->n_cap >= n) return CDC_OK;
-    free_scratch(st);
     const uint64_t cap = n + n / 8 + 64;
-    ST_TRY(hipMalloc(&st->d_slot, cap * 4));
-    ST_TRY(hipMalloc(&st->d_new, cap));
-    ST_TRY(hipMalloc(&st->d_pieces, cap * sizeof(cdc::StorePiece)));
-    ST_TRY(hipMalloc(&st->d_val, cap * 8));
-    ST_TRY(hipMalloc(&st->d_tstart, cap * 8));
-    ST_TRY(hipMalloc(&st->d_block, (cdc::store_scan_blocks(cap) + 1) * 8));
-    st->n_cap = cap;
+    ST_TRY(cdc::grow_group(st->n_cap, n, cap, st->d_slot, cap, st->d_new, cap, st->d_pieces, cap, st->d_val, cap,
+                           st->d_tstart, cap, st->d_block, cdc::store_scan_blocks(cap) + 1));
     return CDC_OK;
 }
 
@@ -195,13 +164,7 @@ int64_t put(cdc_store *st, size_t n_streams, const uint8_t *const *d_streams, co
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : st->stream;
     int rc = grow(st, n);
     if (rc) return rc;
-    if (st->s_cap < n_streams) {
-        (void)hipFree(st->d_streams);
-        st->d_streams = nullptr;
-        st->s_cap = 0;
-        ST_TRY(hipMalloc(&st->d_streams, (3 * n_streams + 1) * 8));
-        st->s_cap = n_streams;
-    }
+    ST_TRY(st->d_streams.room(3 * n_streams + 1));
     uint64_t *d_ptrs = st->d_streams, *d_lens = d_ptrs + n_streams, *d_first = d_lens + n_streams;
     st->h_streams.resize(3 * n_streams + 1);  // the store's own copy: outlives the upload whatever happens
     for (size_t i = 0; i < n_streams; ++i) {
@@ -562,26 +525,14 @@ int64_t get_expanded(cdc_store *st, const uint8_t *d_digests, size_t n, uint8_t 
     }
     if (res[1] > out_cap) return (int64_t)res[1];
     const uint64_t np = res[2];
-    if (st->x_cap < np) {
-        (void)hipFree(st->x_pieces);
-        (void)hipFree(st->x_tstart);
-        (void)hipFree(st->x_block);
-        st->x_pieces = nullptr;
-        st->x_tstart = st->x_block = nullptr;
-        st->x_cap = 0;
-        const uint64_t cap = np + np / 8 + 64;
-        ST_TRY(hipMalloc(&st->x_pieces, cap * sizeof(cdc::StorePiece)));
-        ST_TRY(hipMalloc(&st->x_tstart, cap * 8));
-        ST_TRY(hipMalloc(&st->x_block, (cdc::store_scan_blocks(cap) + 1) * 8));
-        st->x_cap = cap;
-    }
+    ST_TRY(st->x.grow(np));
     if (np) {
         ST_TRY(cdc::launch_store_pieces_x(st->t, v, st->loc, st->arena, st->d_slot, st->d_tstart, st->d_val, n,
-                                          (uint64_t)(uintptr_t)d_out, st->x_pieces, st->x_tstart, np, s));
-        ST_TRY(cdc::launch_store_scan(st->x_tstart, np, st->x_block, nullptr, s));
+                                          (uint64_t)(uintptr_t)d_out, st->x.items, st->x.val, np, s));
+        ST_TRY(cdc::launch_store_scan(st->x.val, np, st->x.block, nullptr, s));
         // A piece adds at most two ragged tiles to its whole ones; the exact total is read on the device.
-        ST_TRY(cdc::launch_store_copy(st->x_pieces, st->x_tstart, np, res[1] / cdc::kStoreTile + 2 * np,
-                                      st->x_block + cdc::store_scan_blocks(np), s));
+        ST_TRY(cdc::launch_store_copy(st->x.items, st->x.val, np, res[1] / cdc::kStoreTile + 2 * np,
+                                      st->x.block + cdc::store_scan_blocks(np), s));
     }
     if (d_spans) ST_TRY(cdc::launch_store_spans_x(st->t, st->d_slot, st->d_val, n, d_spans, s));
     ST_TRY(hipStreamSynchronize(s));

@@ -154,3 +154,15 @@ def test_cpp_files_mirror_compiles_and_links(tmp_path):
                     "-L", os.path.dirname(_lib.LIB_PATH), "-lchunkfs_amd",
                     "-Wl,-rpath," + os.path.dirname(_lib.LIB_PATH), "-o", exe], check=True)
     assert subprocess.call([exe]) == 0
+
+
+def test_read_planner_arithmetic_under_the_host_sanitizers(tmp_path):
+    """read_plan.hpp is header-only and free of HIP: a stand-alone program with
+    its own main checks the host's bounds against what the planner resolves,
+    under ASan and UBSan."""
+    exe = str(tmp_path / "read_plan_check")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "chunkfs_amd", "csrc"),
+                    os.path.join(ROOT, "tools", "read_plan_check.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "read plan ok" in r.stdout, r.stdout + r.stderr

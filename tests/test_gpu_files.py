@@ -638,6 +638,119 @@ def test_stream_order_on_a_user_stream():
     assert got[0] == 0x5A and got[-1] == 0x5A and (got[1:-1] == data).all()
 
 
+# ---- scratch that grows between calls ------------------------------------------------------------------
+def _pread_batch(p, hm, nreq, rng):
+    """One pread_batch of nreq ranges of the file into one guarded buffer, against the model."""
+    import torch
+    size = p.m.size(hm[1])
+    reqs = [(0, size)] + [(int(rng.integers(0, size)), int(rng.integers(1, 2000))) for _ in range(nreq - 1)]
+    at, places = sm.GUARD, []
+    for i, (_, ln) in enumerate(reqs):
+        at += (i * 7) % 16  # every alignment
+        places.append(at)
+        at += ln + 32
+    image = np.full(at + sm.GUARD, sm.POISON, dtype=np.uint8)
+    buf = torch.full((image.size,), sm.POISON, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    want = []
+    for (off, ln), where in zip(reqs, places):
+        w = p.m.pread(hm[1], off, ln)
+        image[where:where + w.size] = w
+        want.append(w.size)
+    got = p.fs.pread_batch_device([(hm[0], off, ln, buf.data_ptr() + where) for (off, ln), where in zip(reqs, places)])
+    assert got == want
+    assert (buf.cpu().numpy() == image).all()
+
+
+def _verify(p, hm, data):
+    import torch
+    d = sm.dev(data)
+    assert p.fs.verify_device(hm[0], d.data_ptr(), data.size) == (True, None)
+    d[data.size // 3] ^= 1
+    torch.cuda.synchronize()
+    assert p.fs.verify_device(hm[0], d.data_ptr(), data.size) == (False, data.size // 3)
+
+
+def test_every_call_small_then_large_then_small_again():
+    """The layer keeps its scratch between calls and frees and reallocates a
+    group when a call needs more.  Every kind of call at a size the first
+    allocation holds (a file of about 3 spans, one request), then at sizes that
+    outgrow every group (200 spans and more against the n + n/8 + 64 of a
+    3-span call, 48 requests and 20 files in a batch against the n + n/8 + 16
+    of one, a splice window past the first 4096-byte buffer), then small again:
+    all of it against the models.  A second layer does the same for the reads
+    that go through target-kind containers, which the edits refuse."""
+    import chunkfs_amd as c
+    import bench_model as bm
+    import splice_model as spm
+    from test_gpu_snapshot import Driver  # imports this module, so not at its top
+    from test_gpu_splice import SPair
+
+    def layer():
+        return c.FileSystem.new_with_scrubber(c.CopyScrubber(), max_chunks=1 << 12, arena_bytes=4 * MB,
+                                              target_max_chunks=1 << 12, target_arena_bytes=4 * MB, seg_size=8192)
+
+    d = Driver(c, "fast", fs=layer())  # the target is attached, nothing is scrubbed: every call is allowed
+    p = d.p
+    rng = np.random.default_rng(61)
+
+    def every_call(tag, size, nreq, nfiles, ins_len, seed):
+        data = spm.rand(seed, size)
+        a = d.file(tag + "_a", data)  # write
+        spans = p.fs.stat(a[0])["spans"]
+        names = [f"{tag}_b{i}" for i in range(nfiles)]  # batch write
+        hms = [p.create(name, p.chunker) for name in names]
+        datas = [spm.rand(seed + 1 + i, 300 + 40 * i) for i in range(nfiles)]
+        chunks = [spm.chunk("fast", x) for x in datas]
+        assert p.fs.write_to_files([h for h, _ in hms], datas) == [len(ch) for ch in chunks]
+        for name, hm, x, ch in zip(names, hms, datas, chunks):
+            p.m.append(hm[1], x, ch)
+            p.seen.update(p.m.hashes(hm[1]))
+            p.open_files[name] = hm
+        _pread_batch(p, a, nreq, rng)
+        assert (p.check_file(a, shift=3) == data).all()  # read_complete with its spans
+        r = p.open(tag + "_a", readonly=True)
+        p.read_segment(r)
+        _verify(p, a, data)
+        assert p.fs.chunk_count_distribution(a[0]) == p.m.distribution(a[1])
+        derived = p.fs.get_to_dedup_ratio(tag + "_a", 2.0)
+        assert derived == bm.get_to_dedup_ratio(p.m, tag + "_a", 2.0)
+        p.check_file(p.open(derived, readonly=True))
+        b = d.clone(tag + "_a", tag + "_c")
+        d.splice(b, size // 2, 5, spm.rand(seed + 50, ins_len))  # a new table, and the file against the model
+        d.splice(b, size // 4, 3, spm.rand(seed + 51, 3))
+        assert d.diff(a, b)["n_ranges"] >= 1
+        d.diff(a, b, tables_only=True)
+        p.remove(names[0])
+        p.collect()
+        for hm in [a, b] + hms[1:]:
+            p.check_file(hm)
+        return spans
+
+    assert 2 <= every_call("small", 700, 1, 1, 10, 100) <= 6
+    assert every_call("large", 96 << 10, 48, 20, 3000, 200) >= 200
+    assert 2 <= every_call("again", 700, 1, 1, 10, 300) <= 6
+    p.check_store()
+
+    # The reads through target-kind containers: small, scrub, read; large, scrub, read; small again.
+    q = SPair(c, "fast", fs=layer())
+    small, large = spm.rand(400, 700), spm.rand(401, 96 << 10)
+    s1 = q.new_file("s1", small)
+    assert q.fs.scrub().processed_data > 0
+
+    def scrubbed_reads(hm, data, nreq):
+        _pread_batch(q, hm, nreq, rng)
+        assert (q.check_file(hm, shift=5) == data).all()
+        _verify(q, hm, data)
+
+    scrubbed_reads(s1, small, 1)
+    s2 = q.new_file("s2", large)
+    assert q.fs.stat(s2[0])["spans"] >= 200 and q.fs.scrub().processed_data > 0
+    assert q.fs.store.scrub_stats()["chunk_containers"] == 0
+    scrubbed_reads(s2, large, 48)
+    scrubbed_reads(s1, small, 1)
+
+
 # ---- the C++ mirror ---------------------------------------------------------------------------------
 def test_cpp_files_mirror_runs():
     from chunkfs_amd import _lib, build
