@@ -22,6 +22,8 @@ include/chunkfs_amd.h (libchunkfs_amd.so, hand-written HIP for gfx950):
     ScrubMeasurements  system/scrub.rs:71-79  ScrubMeasurements
     FileSystem / FileLayer  system/mod.rs,    FileSystem, FileHandle
                             file_layer.rs
+    (none: this project's own)                FileSystem.pack / unpack / send / save_file /
+                                              load_file, PackStats (packs: send and receive)
 
 Every call runs on the GPU.  There is no CPU fallback: without the built
 library or a gfx950 device the constructors raise.
@@ -43,7 +45,7 @@ __all__ = [
     "FSChunker", "RabinChunker", "SuperChunker", "UltraChunker", "LeapChunker",
     "SeqChunker", "OperationMode", "SeqConfig", "AeChunker", "AeMode", "CdcError", "write_spans", "StreamWriter", "version",
     "DedupIndex", "ChunkStore", "FileSystem", "FileHandle",
-    "CopyScrubber", "DumbScrubber", "RechunkScrubber", "ScrubMeasurements",
+    "CopyScrubber", "DumbScrubber", "RechunkScrubber", "ScrubMeasurements", "PackStats",
 ]
 
 
@@ -614,6 +616,30 @@ class DiffStats:
         return "DiffStats { " + ", ".join(f"{f}: {getattr(self, f)}" for f in self.FIELDS) + " }"
 
 
+class PackStats:
+    """cdc_pack_stats_t of one FileSystem.pack / unpack: the file's spans, the
+    carried chunks, the spans whose chunk the pack does not carry, the unpadded
+    bytes of the carried chunks, the bytes of the whole pack, the file's size,
+    and -- unpack only -- the carried chunks the receiver did not hold."""
+
+    FIELDS = ("spans", "chunks", "external_spans", "chunk_bytes", "pack_bytes", "file_size", "chunks_new", "seconds")
+    __slots__ = FIELDS
+
+    def __init__(self, **kw):
+        for f in self.FIELDS:
+            setattr(self, f, float(kw.get(f, 0)) if f == "seconds" else int(kw.get(f, 0)))
+
+    @classmethod
+    def _of(cls, s):
+        return cls(**{f: getattr(s, f) for f in cls.FIELDS})
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f in self.FIELDS}
+
+    def __repr__(self):
+        return "PackStats { " + ", ".join(f"{f}: {getattr(self, f)}" for f in self.FIELDS) + " }"
+
+
 class CopyScrubber:
     """CopyScrubber (scrub.rs:85-114): every chunk moves to the target map under
     its own hash; the container keeps that one key."""
@@ -1138,6 +1164,113 @@ class FileSystem:
         r = DiffStats(n_ranges=s.ranges, **{f: getattr(s, f) for f in DiffStats.FIELDS[1:]})
         r.ranges = out[:n].cpu().numpy().view(np.uint64).reshape(n, 2)
         return r
+
+    # -- packs: send and receive ----------------------------------------------------------
+    def pack_device(self, handle, since, d_have, d_pack, cap, stats=None, stream=None):
+        """cdc_file_pack_device, raw: d_have / d_pack are device pointers (or
+        None), stats a _lib.cdc_pack_stats_t or None.  Returns total_bytes;
+        nothing is written when it exceeds cap."""
+        return check(lib().cdc_file_pack_device(handle._fh, since._fh if since is not None else None, _ptr(d_have),
+                                                _ptr(d_pack), int(cap),
+                                                ctypes.byref(stats) if stats is not None else None, _ptr(stream)))
+
+    def unpack_device(self, name, d_pack, length, hasher=None, flags=0, stats=None, stream=None):
+        """cdc_files_unpack_device, raw: d_pack is a device pointer to `length`
+        bytes, hasher a Chunker or None.  Returns the span count."""
+        return check(lib().cdc_files_unpack_device(self._h, name.encode(), _ptr(d_pack), int(length),
+                                                   hasher._h if hasher is not None else None, int(flags),
+                                                   ctypes.byref(stats) if stats is not None else None, _ptr(stream)))
+
+    def pack(self, handle, since=None, have=None, stream=None):
+        """The file behind `handle` as a pack: (uint8 CUDA tensor, PackStats).
+        The pack carries the file's distinct chunks in order of first
+        occurrence, except those some span of `since` (a handle, typically of
+        a clone taken before edits) names, and those of the spans i with
+        have[i] != 0 (`have`: the receiver's contains() answer to hashes(), a
+        CUDA uint8 tensor or a host array).  Sizes with cap = 0, allocates,
+        packs."""
+        import torch
+        dev = f"cuda:{self.device}"
+        d_have = None
+        if have is not None:
+            if isinstance(have, torch.Tensor):
+                d_have = have.to(dev).contiguous().view(torch.uint8).reshape(-1)
+            else:
+                d_have = torch.from_numpy(np.ascontiguousarray(have).astype(np.uint8).reshape(-1)).to(dev)
+            if d_have.numel() != self.stat(handle)["spans"]:
+                raise CdcError(_lib.CDC_EINVAL, "pack: `have` needs one entry per span of the file")
+        hp = d_have.data_ptr() if d_have is not None and d_have.numel() else None
+        if stream is None:
+            torch.cuda.synchronize(dev)
+        s = _lib.cdc_pack_stats_t()
+        need = self.pack_device(handle, since, hp, None, 0, s, stream)
+        out = torch.empty(need, dtype=torch.uint8, device=dev)  # torch allocations are 512-byte aligned
+        torch.cuda.synchronize(dev)
+        assert self.pack_device(handle, since, hp, out.data_ptr(), need, s, stream) == need
+        return out, PackStats._of(s)
+
+    def unpack(self, name, pack, hasher=None, trust=False, stream=None):
+        """cdc_files_unpack_device: creates the file `name` from a pack and
+        returns PackStats.  `pack` is a CUDA uint8 tensor on this device, one on
+        another device, or host bytes / a numpy array (the last two are copied
+        over).  `hasher`: any Chunker on this device, for the SHA-256 check of
+        the carried chunks; trust=True skips the check (a corrupted data byte
+        is then stored as it is) and needs no hasher.  The pack is validated
+        before anything is written: CdcError(CDC_EINVAL) names the failed
+        check, CDC_ENOTFOUND an external span whose chunk this store lacks,
+        CDC_EEXIST an existing name, CDC_ENOMEM a store that is too small."""
+        import torch
+        dev = torch.device(f"cuda:{self.device}")
+        if isinstance(pack, torch.Tensor):
+            t = pack.contiguous().view(torch.uint8).reshape(-1)
+            if t.device != dev:
+                t = t.to(dev)
+        else:
+            _, _, arr = _as_buffer(pack)
+            t = torch.from_numpy(arr.copy()).to(dev)
+        if t.data_ptr() % 16:  # a slice of a larger tensor
+            t = t.clone()
+        if stream is None:
+            torch.cuda.synchronize(dev)
+        s = _lib.cdc_pack_stats_t()
+        self.unpack_device(name, t.data_ptr() if t.numel() else None, t.numel(), hasher,
+                           _lib.CDC_UNPACK_TRUST if trust else 0, s, stream)
+        return PackStats._of(s)
+
+    def send(self, handle, to, name=None, since=None, hasher=None):
+        """Replicates the file behind `handle` into the FileSystem `to` (on this
+        device or another), moving only the chunks `to` lacks: hashes ->
+        to.store.contains -> pack(have=...) -> to.unpack.  `name`: the file's
+        name there (default: its name here); `since` also excludes what a base
+        version names; `hasher`: a Chunker on `to`'s device (None: the carried
+        chunks are trusted).  Returns (PackStats of the pack, PackStats of the
+        unpack)."""
+        import torch
+        digests = self.hashes(handle)
+        n = digests.shape[0]
+        have = np.zeros(n, dtype=np.uint8)
+        if n:
+            tdev = f"cuda:{to.device}"
+            d = torch.from_numpy(np.ascontiguousarray(digests)).to(tdev)
+            found = torch.empty(n, dtype=torch.uint8, device=tdev)
+            torch.cuda.synchronize(tdev)
+            to.store.contains_device(d.data_ptr(), n, found.data_ptr())
+            have = found.cpu().numpy()
+        pack, sent = self.pack(handle, since=since, have=have)
+        got = to.unpack(name if name is not None else handle.name(), pack, hasher=hasher, trust=hasher is None)
+        return sent, got
+
+    def save_file(self, handle, path):
+        """The file's full pack through host memory into `path` (fails if the
+        path exists, as write_file_to_disk).  Returns PackStats."""
+        pack, st = self.pack(handle)
+        with open(path, "xb") as f:
+            pack.cpu().numpy().tofile(f)
+        return st
+
+    def load_file(self, name, path, hasher=None, trust=False):
+        """unpack() of a pack that save_file wrote."""
+        return self.unpack(name, np.fromfile(path, dtype=np.uint8), hasher=hasher, trust=trust)
 
     # -- reads ----------------------------------------------------------------------
     def read_complete_device(self, handle, d_out, out_cap, d_spans=None, stream=None):

@@ -44,13 +44,15 @@ EXPORTS = [
     "cdc_files_remove", "cdc_files_collect", "cdc_store_retain_device",
     "cdc_file_splice_device",
     "cdc_files_clone", "cdc_files_diff_device",
+    "cdc_file_pack_device", "cdc_files_unpack_device",
     "cdc_fill_splitmix64_device", "cdc_version", "cdc_abi_version",
 ]
 # include/chunkfs_amd_debug.h (diagnostics, not part of the drop-in boundary)
 DEBUG_EXPORTS = ["cdc_debug_pipeline", "cdc_debug_record_cap", "cdc_debug_copy", "cdc_debug_host_stats",
                  "cdc_debug_read_bw", "cdc_debug_host_placement",
                  "cdc_debug_timing_back", "cdc_debug_walk_params", "cdc_debug_files_table_blocks",
-                 "cdc_debug_collect_split", "cdc_debug_splice_split", "cdc_debug_file_slots"]
+                 "cdc_debug_collect_split", "cdc_debug_splice_split", "cdc_debug_file_slots",
+                 "cdc_debug_pack_split"]
 
 
 class CdcError(RuntimeError):
@@ -116,6 +118,12 @@ class cdc_splice_stats_t(ctypes.Structure):
                 ("rounds", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
 
 
+class cdc_pack_stats_t(ctypes.Structure):
+    _fields_ = [("spans", ctypes.c_uint64), ("chunks", ctypes.c_uint64), ("external_spans", ctypes.c_uint64),
+                ("chunk_bytes", ctypes.c_uint64), ("pack_bytes", ctypes.c_uint64), ("file_size", ctypes.c_uint64),
+                ("chunks_new", ctypes.c_uint64), ("seconds", ctypes.c_double)]
+
+
 class cdc_diff_stats_t(ctypes.Structure):
     _fields_ = [("ranges", ctypes.c_uint64), ("bytes_differing", ctypes.c_uint64),
                 ("bytes_compared", ctypes.c_uint64), ("bytes_shared", ctypes.c_uint64),
@@ -124,6 +132,7 @@ class cdc_diff_stats_t(ctypes.Structure):
 
 
 CDC_DIFF_TABLES_ONLY = 1
+CDC_UNPACK_TRUST = 1
 
 
 class cdc_timing_t(ctypes.Structure):
@@ -318,8 +327,15 @@ def lib():
     L.cdc_files_clone.restype = ctypes.c_int64
     L.cdc_files_diff_device.argtypes = [P, P, ctypes.c_uint32, P, sz, ctypes.POINTER(cdc_diff_stats_t), P]
     L.cdc_files_diff_device.restype = ctypes.c_int64
+    L.cdc_file_pack_device.argtypes = [P, P, P, P, sz, ctypes.POINTER(cdc_pack_stats_t), P]
+    L.cdc_file_pack_device.restype = ctypes.c_int64
+    L.cdc_files_unpack_device.argtypes = [P, ctypes.c_char_p, P, sz, P, ctypes.c_uint32,
+                                          ctypes.POINTER(cdc_pack_stats_t), P]
+    L.cdc_files_unpack_device.restype = ctypes.c_int64
     L.cdc_debug_splice_split.argtypes = [ctypes.POINTER(ctypes.c_double), sz]
     L.cdc_debug_splice_split.restype = ctypes.c_int
+    L.cdc_debug_pack_split.argtypes = [ctypes.POINTER(ctypes.c_double), sz]
+    L.cdc_debug_pack_split.restype = ctypes.c_int
     L.cdc_debug_file_slots.argtypes = [P, P, P, sz]
     L.cdc_debug_file_slots.restype = ctypes.c_int64
     L.cdc_fill_splitmix64_device.argtypes = [P, sz, ctypes.c_uint64, P]

@@ -17,6 +17,8 @@
 #include "engine.hpp"
 #include "files.hpp"
 #include "diff_plan.hpp"
+#include "pack.hpp"
+#include "pack_plan.hpp"
 #include "read_plan.hpp"
 #include "splice_plan.hpp"
 #include "store.hpp"
@@ -102,6 +104,8 @@ struct HostWords {               // pinned host memory
     word resync_k, resync_j, resync_e;  // launch_splice_resync: the smallest chunk that resyncs (~0: none), the old
                                         // span its cut meets, the cut
     word ranges, bytes_differing, bytes_compared, bytes_shared, pieces;  // launch_files_diff
+    word pack_chunks, pack_data;      // launch_pack_mark: carried chunks, bytes of the data section
+    word pack_external, pack_bytes;   // DeviceWords' copy
 };
 struct DeviceWords {
     word least, zeros;  // launch_files_append's d_stat, preset to {~0, 0}: min(length - 1) over the spans of
@@ -109,6 +113,8 @@ struct DeviceWords {
     word verify;        // the smallest destination address - cmp_base at which a byte differs, preset to ~0
     word touch;         // launch_files_plan_x's counter
     word best;          // launch_splice_resync's
+    word pack_external, pack_bytes;  // launch_pack_mark's d_acc: spans whose slot is excluded, unpadded bytes of
+                                     // the carried chunks
 };
 
 // Scratch kept between calls, one struct per group of buffers that grow
@@ -158,6 +164,33 @@ struct RequestScratch {  // reads: per request
                                cdc::store_scan_blocks(c) + 1);
     }
 };
+struct PackScratch {  // pack: per span, the rank and the padded offset of the carried chunks with their scans
+    uint64_t cap = 0;
+    DeviceBuf<uint64_t> rank, poff, bs_rank, bs_off;
+    hipError_t grow(uint64_t n) {
+        const uint64_t c = n + n / 8 + 64, b = cdc::store_scan_blocks(c) + 1;
+        return cdc::grow_group(cap, n, c, rank, c, poff, c, bs_rank, b, bs_off, b);
+    }
+};
+struct UnpackHost {  // unpack: what crosses to the host, pinned
+    cdc::PackHeader header;
+    cdc::PackResult res;
+};
+struct UnpackScratch {  // unpack: per span its slot; per carried chunk the hash that is compared with its digest
+    uint64_t span_cap = 0, chunk_cap = 0;
+    DeviceBuf<uint32_t> slot;
+    DeviceBuf<uint8_t> sha;
+    PinnedBuf<UnpackHost> h;
+    DeviceBuf<cdc::PackResult> res;
+    hipError_t grow(uint64_t spans, uint64_t chunks) {
+        hipError_t e = h.room(1);
+        if (e == hipSuccess) e = res.room(1);
+        if (e == hipSuccess) e = cdc::grow_group(span_cap, spans, spans + spans / 8 + 64, slot, spans + spans / 8 + 64);
+        if (e == hipSuccess)
+            e = cdc::grow_group(chunk_cap, chunks, chunks + chunks / 8 + 64, sha, (chunks + chunks / 8 + 64) * 32);
+        return e;
+    }
+};
 struct SlotArrays {  // reads in the scrubbed state: per request, the address of its file's slot array
     uint64_t cap = 0;
     PinnedBuf<uint64_t> h;
@@ -189,6 +222,8 @@ struct cdc_files {
     cdc::ScanScratch<cdc::SpanRec> xspan;  // reads in the scrubbed state: per span, with the piece counts
     DeviceBuf<uint8_t> window;  // cdc_file_splice_device: the window of the new file that is chunked
     DeviceBuf<uint8_t> diff;    // cdc_files_diff_device: one block carved into the DiffScratch arrays
+    PackScratch pack;
+    UnpackScratch unpack;
 };
 
 struct cdc_fh {
@@ -702,6 +737,252 @@ int grow_diff(cdc_files *fs, uint64_t na, uint64_t nb, uint64_t common, bool tab
     return CDC_OK;
 }
 
+// ---- packs ------------------------------------------------------------------------
+bool scrubbed(const cdc_files *fs) {
+    cdc::ScrubView sv;
+    bool stale = false;
+    return cdc::store_scrub_view(fs->store, &sv, &stale);
+}
+
+int pack_check_failed(uint32_t check, uint64_t index, uint64_t count) {
+    return fail(CDC_EINVAL, std::string("cdc_files_unpack_device: pack check '") + cdc::pack_check_name(check) +
+                                "' failed at index " + std::to_string(index) + " (" + std::to_string(count) +
+                                " in all)");
+}
+
+// cdc_debug_pack_split: [0..1] the last pack of this thread, [2..6] the last unpack.
+double *pack_split() {
+    static thread_local double split[7];
+    return split;
+}
+struct Laps {  // wall milliseconds between the call's host waits
+    std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+    double ms[5] = {0, 0, 0, 0, 0};
+    void lap(int phase) {
+        const auto now = std::chrono::steady_clock::now();
+        ms[phase] += std::chrono::duration<double, std::milli>(now - last).count();
+        last = now;
+    }
+};
+
+int64_t pack_file(cdc_fh *fh, cdc_fh *since, const uint8_t *d_have, uint8_t *d_pack, uint64_t cap,
+                  cdc_pack_stats_t *stats, void *hip_stream) {
+    const auto t0 = std::chrono::steady_clock::now();
+    // Everything that can refuse, before any device work.
+    if ((uintptr_t)d_pack & (cdc::kPackAlign - 1))
+        return fail(CDC_EINVAL, "cdc_file_pack_device: d_pack is not 16-byte aligned");
+    if (!fh) return fail(CDC_EINVAL, "cdc_file_pack_device: NULL file handle");
+    if (cap && !d_pack) return fail(CDC_EINVAL, "cdc_file_pack_device: NULL destination");
+    if (since && fh->fs && since->fs && since->fs != fh->fs)
+        return fail(CDC_EINVAL, "cdc_file_pack_device: `since` belongs to another file layer");
+    FileRec *f = nullptr, *base = nullptr;
+    int rc = lookup(fh, true, &f);
+    if (rc) return rc;
+    if (since && (rc = lookup(since, true, &base)) != CDC_OK) return rc;
+    cdc_files *fs = fh->fs;
+    if (scrubbed(fs))
+        return fail(CDC_ENOTSUP, "cdc_file_pack_device: the store holds target-kind containers (scrubbed); "
+                                 "not supported");
+    const cdc::StoreView v = cdc::store_view(fs->store);
+    FL_TRY(hipSetDevice(v.device));
+    hipStream_t s = stream_of(fs, hip_stream);
+    const uint64_t n = f->n;
+    Laps laps;
+
+    // (a), (b): which chunks are carried and where; the one wait for the sizes.
+    cdc::PackHeader h{cdc::kPackMagic, cdc::kPackVersion, 0, f->size, n, 0, 0, 0, 0};
+    uint64_t chunk_bytes = 0;
+    if (n) {
+        FL_TRY(fs->pack.grow(n));
+        FL_TRY(fs->slot.grow(v.slots));
+        const uint64_t ns = base ? base->n : 0;
+        FL_TRY(cdc::launch_pack_mark(f->t, n, ns ? base->t.slot : nullptr, ns, d_have, v.slots, fs->slot.cnt,
+                                     fs->slot.first, fs->pack.rank, fs->pack.poff, fs->pack.bs_rank, fs->pack.bs_off,
+                                     &fs->dw->pack_external, &fs->hw->pack_chunks, s));
+        FL_TRY(hipMemcpyAsync(&fs->hw->pack_external, &fs->dw->pack_external, 2 * sizeof(word),
+                              hipMemcpyDeviceToHost, s));
+        FL_TRY(hipStreamSynchronize(s));
+        h.n_chunks = fs->hw->pack_chunks;
+        h.data_bytes = fs->hw->pack_data;
+        h.external_spans = fs->hw->pack_external;
+        chunk_bytes = fs->hw->pack_bytes;
+    }
+    laps.lap(0);
+    cdc::PackLayout l{};
+    if (!cdc::pack_layout(n, h.n_chunks, h.data_bytes, &l))
+        return fail(CDC_EINVAL, "cdc_file_pack_device: the pack would be larger than 2^64 bytes");
+    h.total_bytes = l.total;
+    cdc_pack_stats_t r{};
+    r.spans = n;
+    r.chunks = h.n_chunks;
+    r.external_spans = h.external_spans;
+    r.chunk_bytes = chunk_bytes;
+    r.pack_bytes = l.total;
+    r.file_size = f->size;
+    if (l.total <= cap) {
+        // (c), (d): everything but the data in one kernel, the data through the store's copy.
+        FL_TRY(fs->pc.grow(h.n_chunks));
+        FL_TRY(cdc::launch_pack_write(f->t, n, fs->slot.cnt, fs->slot.first, fs->pack.rank, fs->pack.poff, h, l,
+                                      d_pack, (uint64_t)(uintptr_t)v.arena, fs->pc.items, fs->pc.val, fs->pc.block,
+                                      s));
+        FL_TRY(hipStreamSynchronize(s));
+    }
+    laps.lap(1);
+    std::memcpy(pack_split(), laps.ms, 2 * sizeof(double));
+    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) *stats = r;
+    return (int64_t)l.total;
+}
+
+int64_t unpack_file(cdc_files *fs, const char *name, const uint8_t *d_pack, uint64_t len, cdc_handle_t *hasher,
+                    uint32_t flags, cdc_pack_stats_t *stats, void *hip_stream) {
+    const auto t0 = std::chrono::steady_clock::now();
+    // 1. Arguments.
+    if (flags & ~(uint32_t)CDC_UNPACK_TRUST)
+        return fail(CDC_EINVAL, "cdc_files_unpack_device: unknown flag bits " + std::to_string(flags));
+    if ((uintptr_t)d_pack & (cdc::kPackAlign - 1))
+        return fail(CDC_EINVAL, "cdc_files_unpack_device: d_pack is not 16-byte aligned");
+    if (len < cdc::kPackHeaderBytes)
+        return fail(CDC_EINVAL, "cdc_files_unpack_device: " + std::to_string(len) + " bytes are no pack (len < 64)");
+    if (!fs || !name || !d_pack) return fail(CDC_EINVAL, "cdc_files_unpack_device: NULL argument");
+    const bool trust = (flags & CDC_UNPACK_TRUST) != 0;
+    if (!hasher && !trust) return fail(CDC_EINVAL, "cdc_files_unpack_device: NULL hasher without CDC_UNPACK_TRUST");
+    cdc::StoreView v = cdc::store_view(fs->store);
+    if (hasher && cdc::handle_device(hasher) != v.device)
+        return fail(CDC_EINVAL, "cdc_files_unpack_device: the hasher is on another device than the store");
+    if (fs->files.count(name)) return fail(CDC_EEXIST, std::string("file layer: '") + name + "' already exists");
+    if (scrubbed(fs))
+        return fail(CDC_ENOTSUP, "cdc_files_unpack_device: the store holds target-kind containers (scrubbed); "
+                                 "not supported");
+    FL_TRY(hipSetDevice(v.device));
+    hipStream_t s = stream_of(fs, hip_stream);
+
+    Laps laps;
+
+    // 2. Structure: the header on the host, the index sections in one kernel.
+    FL_TRY(fs->unpack.grow(0, 0));
+    UnpackHost *host = fs->unpack.h;
+    FL_TRY(hipMemcpyAsync(&host->header, d_pack, sizeof host->header, hipMemcpyDeviceToHost, s));
+    FL_TRY(hipStreamSynchronize(s));
+    const cdc::PackHeader h = host->header;
+    laps.lap(0);
+    cdc::PackLayout l{};
+    uint32_t bad = cdc::pack_check_header(h, len, &l);
+    if (!bad && h.n_spans >= 0xFFFFFFFFull) bad = cdc::kPackSizesCheck;  // a put's own limit
+    if (bad) return pack_check_failed(bad, 0, 1);
+    const uint64_t n = h.n_spans, nc = h.n_chunks;
+    const cdc::PackView view = cdc::pack_view(d_pack, h, l);
+    // Every allocation of the call: one that fails is a refusal.
+    FL_TRY(fs->unpack.grow(n, nc));
+    FL_TRY(fs->wr.grow(nc));
+    FL_TRY(fs->span.grow(n));
+    host = fs->unpack.h;
+    cdc::PackResult *d_res = fs->unpack.res;
+    FL_TRY(cdc::pack_result_preset(d_res, s));
+    FL_TRY(cdc::launch_pack_validate(view, d_res, s));
+    // 3. Externals: the lookup reads the digests, lengths and span_chunk at [0, n) only, so it may run
+    // before the validation's verdict is known.
+    FL_TRY(cdc::launch_pack_lookup(cdc::store_index(fs->store), view, fs->unpack.slot, d_res, s));
+    FL_TRY(hipMemcpyAsync(&host->res, d_res, sizeof host->res, hipMemcpyDeviceToHost, s));
+    FL_TRY(hipStreamSynchronize(s));
+    {
+        const cdc::PackResult &res = host->res;
+        for (uint32_t c = cdc::kPackFirstDeviceCheck; c < cdc::kPackChecks; ++c)
+            if (res.count[c]) return pack_check_failed(c, res.first[c], res.count[c]);
+        if (!cdc::pack_ok_file_size(view, cdc::PackSum{res.sum_low, res.sum_wraps}))
+            return pack_check_failed(cdc::kPackFileSizeCheck, n, 1);
+        if (res.externals != h.external_spans) return pack_check_failed(cdc::kPackExternalCheck, res.externals, 1);
+        if (res.missing)
+            return fail(CDC_ENOTFOUND, "cdc_files_unpack_device: the store does not hold the chunk of external span " +
+                                           std::to_string(res.missing_first) + " (" + std::to_string(res.missing) +
+                                           " missing in all)");
+        if (res.mislen)
+            return fail(CDC_EINVAL, "cdc_files_unpack_device: the store holds the chunk of external span " +
+                                        std::to_string(res.mislen_first) + " with another length than the pack states");
+    }
+
+    laps.lap(1);
+
+    // 4. Integrity.
+    const uint8_t *data = d_pack + l.data;
+    if (nc) FL_TRY(cdc::launch_pack_gather(view, fs->wr.chunks, fs->wr.dig, s));
+    if (nc && !trust) {
+        const uint8_t *streams[1] = {data};
+        const uint64_t first[2] = {0, nc};
+        const int rc = cdc_sha256_batch_device(hasher, 1, streams, first, fs->wr.chunks, fs->unpack.sha, s);
+        if (rc) return rc;
+        FL_TRY(cdc::launch_pack_verify(fs->unpack.sha, fs->wr.dig, nc, d_res, s));
+        FL_TRY(hipMemcpyAsync(&host->res, d_res, sizeof host->res, hipMemcpyDeviceToHost, s));
+        FL_TRY(hipStreamSynchronize(s));
+        if (host->res.mismatch)
+            return fail(CDC_EINVAL, "cdc_files_unpack_device: the data of carried chunk " +
+                                        std::to_string(host->res.mismatch_first) + " does not hash to its digest (" +
+                                        std::to_string(host->res.mismatch) + " in all)");
+    }
+
+    laps.lap(2);
+
+    // 5. The put of the carried chunks; the table first, so that nothing can fail for memory after it.
+    FileRec made;
+    if (n) {
+        const uint64_t cap = table_cap(0, n);
+        const int rc = take_table(fs, cap, &made.t, "cdc_files_unpack_device: span table: ");
+        if (rc) return rc;
+        made.cap = cap;
+    }
+    struct Guard {  // the table goes back unless the call succeeds
+        cdc_files *fs;
+        FileRec *f;
+        ~Guard() {
+            if (f) free_table(fs, f);
+        }
+    } guard{fs, &made};
+    cdc_store_stats_t before{}, after{};
+    (void)cdc_store_stats(fs->store, &before);
+    int64_t put = 0;
+    if (nc) {
+        put = cdc::store_put_slots(fs->store, data, h.data_bytes, fs->wr.chunks, fs->wr.dig, nc, s);
+        if (put < 0) return put;  // refused: the store and the layer are as they were
+    }
+    (void)cdc_store_stats(fs->store, &after);
+    const uint64_t chunk_bytes = after.index.bytes_written - before.index.bytes_written;
+    laps.lap(3);
+
+    // 6. Slots for all spans, then the table as an append builds it.
+    if (n) {
+        v = cdc::store_view(fs->store);
+        if (nc) FL_TRY(cdc::launch_pack_slots(view, v.slot_of, fs->unpack.slot, s));
+        FL_TRY(preset_stat(fs, s));
+        FL_TRY(cdc::launch_files_append(made.t, 0, 0, fs->unpack.slot, v.length, v.loc, view.digest, n, fs->span.val,
+                                        fs->span.block, &fs->dw->least, &fs->hw->appended, s));
+        FL_TRY(fetch_stat(fs, s));
+        FL_TRY(hipStreamSynchronize(s));
+        made.n = n;
+        made.size = fs->hw->appended;
+        made.epoch = v.epoch;
+        fold_stat(&made, fs->hw->least, fs->hw->zeros);
+    }
+    // The file's other spans are inserts of digests the store holds: a write of the content counts them too.
+    cdc::store_count_written(fs->store, n - nc, made.size > chunk_bytes ? made.size - chunk_bytes : 0);
+    fs->files[name] = new FileRec(made);
+    guard.f = nullptr;
+    laps.lap(4);
+    std::memcpy(pack_split() + 2, laps.ms, 5 * sizeof(double));
+    if (stats) {
+        cdc_pack_stats_t r{};
+        r.spans = n;
+        r.chunks = nc;
+        r.external_spans = h.external_spans;
+        r.chunk_bytes = chunk_bytes;
+        r.pack_bytes = h.total_bytes;
+        r.file_size = made.size;
+        r.chunks_new = (uint64_t)put;
+        r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        *stats = r;
+    }
+    return (int64_t)n;
+}
+
 }  // namespace
 
 extern "C" {
@@ -819,6 +1100,22 @@ int64_t cdc_files_diff_device(cdc_fh_t *a, cdc_fh_t *b, uint32_t flags, cdc_chun
     r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (stats) *stats = r;
     return (int64_t)r.ranges;
+}
+
+int64_t cdc_file_pack_device(cdc_fh_t *fh, cdc_fh_t *since, const uint8_t *d_have, uint8_t *d_pack, size_t cap,
+                             cdc_pack_stats_t *stats, void *hip_stream) {
+    return pack_file(fh, since, d_have, d_pack, cap, stats, hip_stream);
+}
+
+int64_t cdc_files_unpack_device(cdc_files_t *fs, const char *name, const uint8_t *d_pack, size_t len,
+                                cdc_handle_t *hasher, uint32_t flags, cdc_pack_stats_t *stats, void *hip_stream) {
+    return unpack_file(fs, name, d_pack, len, hasher, flags, stats, hip_stream);
+}
+
+int cdc_debug_pack_split(double *ms, size_t n) {
+    if (n && !ms) return fail(CDC_EINVAL, "cdc_debug_pack_split: NULL argument");
+    if (n) std::memcpy(ms, pack_split(), (n < 7 ? n : 7) * sizeof(double));
+    return 7;
 }
 
 int64_t cdc_debug_files_table_blocks(const cdc_files_t *fs) {

@@ -769,6 +769,13 @@ StoreView store_view(const cdc_store *st) {
     return StoreView{st->device, st->stream, st->epoch, st->t.slots, st->t.length, st->loc, st->arena, st->d_slot};
 }
 
+IndexTable store_index(const cdc_store *st) { return st->t; }
+
+void store_count_written(cdc_store *st, uint64_t chunks, uint64_t bytes) {
+    st->st.chunks_written += chunks;
+    st->st.bytes_written += bytes;
+}
+
 int64_t store_put_slots(cdc_store *st, const uint8_t *d_data, uint64_t data_len, const cdc_chunk_t *d_chunks,
                         const uint8_t *d_digests, uint64_t n, void *hip_stream) {
     const uint64_t lens[1] = {data_len}, first[2] = {0, n};

@@ -28,6 +28,16 @@ struct StoreView {
 
 StoreView store_view(const cdc_store *st);
 
+// The store's index table, for a lookup that answers with the slot
+// (cdc_files_unpack_device, pack.hip).
+IndexTable store_index(const cdc_store *st);
+
+// Counts `chunks` inserts of `bytes` bytes in all whose digests the store held
+// already: what a put of them would add to chunks_written and bytes_written,
+// and nothing else.  An unpack puts each carried chunk once; the file's other
+// spans are such inserts.
+void store_count_written(cdc_store *st, uint64_t chunks, uint64_t bytes);
+
 // cdc_store_put_device without the new flags; on success store_view().slot_of
 // holds the n slots.  Same checks, same refusal rule, same return value.
 int64_t store_put_slots(cdc_store *st, const uint8_t *d_data, uint64_t data_len, const cdc_chunk_t *d_chunks,

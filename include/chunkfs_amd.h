@@ -43,7 +43,9 @@ extern "C" {
  *    cdc_files_remove, cdc_files_collect, cdc_store_retain_device,
  *    cdc_collect_stats_t; the edit in place -- cdc_file_splice_device,
  *    cdc_splice_stats_t; snapshots and diffs -- cdc_files_clone,
- *    cdc_files_diff_device, cdc_diff_stats_t, CDC_DIFF_TABLES_ONLY. */
+ *    cdc_files_diff_device, cdc_diff_stats_t, CDC_DIFF_TABLES_ONLY; packs --
+ *    cdc_file_pack_device, cdc_files_unpack_device, cdc_pack_stats_t,
+ *    CDC_UNPACK_TRUST. */
 #define CHUNKFS_AMD_ABI_VERSION 6
 
 /* Chunk{offset,length} -- reference src/lib.rs:43-47 (usize fields; u64 here). */
@@ -1000,6 +1002,106 @@ int64_t cdc_files_clone(cdc_files_t *fs, const char *src, const char *dst, void 
 /* Returns the number of runs, or a negative CDC_E* code.  stats is nullable. */
 int64_t cdc_files_diff_device(cdc_fh_t *a, cdc_fh_t *b, uint32_t flags, cdc_chunk_t *d_ranges, size_t cap,
                               cdc_diff_stats_t *stats, void *hip_stream);
+
+/* ---- Packs: send and receive ----------------------------------------------------------
+ * Not in the reference.  A pack is one file of the layer as a self-describing,
+ * deduplicated, deterministic byte image, built and consumed on the device: what
+ * a store sends to another store -- on the same GPU, on another GPU, or through a
+ * disk file to a later process -- so that only the chunks the other side lacks
+ * move, and nothing is chunked or (with CDC_UNPACK_TRUST) hashed again.
+ *
+ * The format, version 1, little-endian, every section at a 16-byte multiple:
+ *   header, 64 bytes:
+ *     u64 magic          the bytes "CDCPACK1"
+ *     u32 version = 1    u32 flags = 0 (reserved, must be 0)
+ *     u64 file_size      u64 n_spans
+ *     u64 n_chunks       containers carried in the pack
+ *     u64 external_spans spans whose chunk the pack does not carry
+ *     u64 data_bytes     size of the data section
+ *     u64 total_bytes    the whole pack
+ *   span_digest  [n_spans][32]  the file's digests in file order (cdc_file_hashes_device)
+ *   span_length  [n_spans] u64
+ *   span_chunk   [n_spans] u64  index k of the carried chunk holding this span's bytes, ~0 = external
+ *   chunk_span   [n_chunks] u64 span index of carried chunk k's first occurrence; strictly increasing
+ *   chunk_off    [n_chunks + 1] u64  exclusive scan of round_up(length, 16), relative to the data section
+ *   data         [data_bytes]   carried chunks back to back at 16-byte multiples
+ * Every padding byte, between sections and after each chunk, is zero: two packs of
+ * the same file with the same exclusions are byte-identical.  Carried chunks are
+ * the file's distinct slots that are not excluded, in order of first occurrence in
+ * the file -- the order in which a put lays them out.  Length-0 spans are legal.
+ * A file without spans packs to its header alone, 64 bytes, with no section.
+ *
+ * cdc_file_pack_device.  A slot is excluded when some span of `since` names it
+ * (nullable: a handle of the same layer, typically a clone taken before edits),
+ * or some span i of the file that names it has d_have[i] != 0 (nullable: DEVICE
+ * u8[spans], the receiver's cdc_store_contains_device answer to this file's
+ * cdc_file_hashes_device).  since == fh is legal and carries nothing.  Returns
+ * total_bytes (snprintf convention: a return > cap means NOTHING was written;
+ * cap = 0 sizes a pack without copying a data byte; stats is filled either way).
+ * d_pack: DEVICE, 16-byte aligned.  Cursors are untouched, read-only handles are
+ * fine.  The host waits for the device twice: for the sizes, and at the end.
+ * Refusals, each before any device work and changing nothing:
+ *   CDC_EINVAL    a misaligned d_pack, a NULL handle, cap > 0 with NULL d_pack,
+ *                 `since` of another layer;
+ *   CDC_ENOTFOUND a removed file, or one whose spans predate a store clear, on
+ *                 either handle;
+ *   CDC_ENOTSUP   the store holds target-kind containers (it was scrubbed).
+ *
+ * cdc_files_unpack_device creates the file `name` from the len bytes at d_pack
+ * (DEVICE, 16-byte aligned) and returns its span count.  `hasher` is any chunker
+ * handle on the store's device (its engine owns the SHA-256 workspaces); NULL only
+ * with CDC_UNPACK_TRUST.  The pack is untrusted input: no kernel reads outside
+ * [d_pack, d_pack + len) or indexes outside a section, whatever the bytes say.
+ * The checks, in this order, every one before the first write to the store or the
+ * layer -- a refused call changes nothing, stats included:
+ *   1. arguments: CDC_EINVAL for unknown flag bits, a misaligned pack, len < 64,
+ *      a NULL argument, a hasher on another device; CDC_EEXIST if `name` exists;
+ *      CDC_ENOTSUP on a scrubbed store;
+ *   2. structure, CDC_EINVAL with the check and the first offending index in
+ *      cdc_last_error(): on the host magic, version, flags, every section size
+ *      recomputed from n_spans / n_chunks without overflow, total_bytes <= len;
+ *      then one kernel: chunk_span strictly increasing and < n_spans; span_chunk
+ *      ~0 or < n_chunks; span_chunk[chunk_span[k]] == k; every carried span equal
+ *      in digest and length to the first span of its chunk; chunk_off[0] == 0 with
+ *      steps of round_up(length, 16); chunk_off[n_chunks] == data_bytes; the
+ *      lengths sum to file_size; external_spans counts the ~0 entries;
+ *   3. externals: every external span's digest is in the store, else
+ *      CDC_ENOTFOUND naming the first missing span (and CDC_EINVAL if the store
+ *      holds it with another length than the pack states);
+ *   4. integrity, unless CDC_UNPACK_TRUST: one cdc_sha256_batch_device over the
+ *      carried chunks, compared with their digests; a mismatch is CDC_EINVAL naming
+ *      the chunk.  With CDC_UNPACK_TRUST nothing is hashed: a corrupted data byte
+ *      is stored as it is, under the digest the pack states;
+ *   5. the put of the carried chunks, with its own refusals (CDC_ENOMEM "as if
+ *      every chunk were new").  First insert wins: a carried chunk the store holds
+ *      already adds nothing.
+ * Then every span gets its slot, the table is built as an append builds it, and
+ * the file is registered.  The store's chunks_written and bytes_written count
+ * every span of the file, as a write of the same content would.  Unpacking a full
+ * pack into an empty store gives exactly the store and the file that one
+ * cdc_file_write_device of the content with the sender's chunker gives: digests,
+ * span offsets, bytes and every field of cdc_store_stats, arena_used included.
+ * Stream convention: cdc_file_write_device's. */
+typedef struct cdc_pack_stats {
+    uint64_t spans;          /* spans of the file */
+    uint64_t chunks;         /* carried chunks */
+    uint64_t external_spans; /* spans whose chunk the pack does not carry */
+    uint64_t chunk_bytes;    /* unpadded sum of the carried lengths */
+    uint64_t pack_bytes;     /* the whole pack */
+    uint64_t file_size;      /* bytes of the file */
+    uint64_t chunks_new;     /* unpack: carried chunks the receiver did not hold; pack: 0 */
+    double seconds;          /* wall time of the call */
+} cdc_pack_stats_t;
+
+#define CDC_UNPACK_TRUST 1u /* skip the SHA-256 check of the carried chunks */
+
+/* Returns total_bytes, or a negative CDC_E* code.  since, d_have and stats are nullable. */
+int64_t cdc_file_pack_device(cdc_fh_t *fh, cdc_fh_t *since, const uint8_t *d_have, uint8_t *d_pack, size_t cap,
+                             cdc_pack_stats_t *stats, void *hip_stream);
+
+/* Returns the span count of the new file, or a negative CDC_E* code.  stats is nullable. */
+int64_t cdc_files_unpack_device(cdc_files_t *fs, const char *name, const uint8_t *d_pack, size_t len,
+                                cdc_handle_t *hasher, uint32_t flags, cdc_pack_stats_t *stats, void *hip_stream);
 
 /* ---- Synthetic data -----------------------------------------
  * Fill a DEVICE buffer with the splitmix64 stream: little-endian u64 words,

@@ -381,6 +381,15 @@ class File {
                        void *hip_stream = nullptr) {
         return check(cdc_file_verify_device(fh_, d_data, len, first_diff, hip_stream)) != 0;
     }
+    // cdc_file_pack_device: the file as a pack in d_pack (DEVICE, 16-byte aligned,
+    // cap bytes).  Chunks that a span of `since` (nullable) names, or a span i with
+    // d_have[i] != 0 (nullable, DEVICE u8[spans]), are left out.  Returns the
+    // pack's size: nothing was written when it exceeds cap, and cap = 0 sizes a
+    // pack.  stats (nullable) is filled either way.
+    int64_t pack(uint8_t *d_pack, size_t cap, File *since = nullptr, const uint8_t *d_have = nullptr,
+                 cdc_pack_stats_t *stats = nullptr, void *hip_stream = nullptr) {
+        return check(cdc_file_pack_device(fh_, since ? since->fh_ : nullptr, d_have, d_pack, cap, stats, hip_stream));
+    }
     cdc_file_stat_t stat() const {
         cdc_file_stat_t s{};
         check(cdc_file_stat(fh_, &s));
@@ -476,6 +485,19 @@ class Files {
         Diff d{};
         d.ranges = check(cdc_files_diff_device(a.handle(), b.handle(), flags, d_ranges, cap, &d.stats, hip_stream));
         return d;
+    }
+    // cdc_files_unpack_device: the new file `name` from the len bytes of a pack at
+    // d_pack (DEVICE, 16-byte aligned).  The pack is validated before anything is
+    // written; hasher (nullable only with CDC_UNPACK_TRUST) checks the carried
+    // chunks against their digests.  Throws CDC_EINVAL naming the failed check,
+    // CDC_ENOTFOUND for an external span whose chunk the store lacks, CDC_EEXIST,
+    // CDC_ENOMEM.  Returns the stats; stats.spans is the new file's span count.
+    cdc_pack_stats_t unpack(const std::string &name, const uint8_t *d_pack, size_t len, Chunker *hasher,
+                            uint32_t flags = 0, void *hip_stream = nullptr) {
+        cdc_pack_stats_t s{};
+        check(cdc_files_unpack_device(fs_, name.c_str(), d_pack, len, hasher ? hasher->handle() : nullptr, flags, &s,
+                                      hip_stream));
+        return s;
     }
     // clear_database (mod.rs:275-278): no files, an empty store, handles invalid.
     void clear() { check(cdc_files_clear(fs_)); }

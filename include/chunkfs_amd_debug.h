@@ -113,6 +113,15 @@ int cdc_debug_collect_split(double *ms, size_t n);
  * for n > 0 with NULL ms. */
 int cdc_debug_splice_split(double *ms, size_t n);
 
+/* The same for the last successful cdc_file_pack_device and the last successful
+ * cdc_files_unpack_device of this thread.  Pack: [0] mark, flags and the two
+ * scans, up to the wait for the sizes, [1] the header-and-sections kernel and the
+ * copy of the data.  Unpack: [2] the header's way to the host, [3] the validation
+ * kernel and the lookup, [4] the gather, SHA-256 and the comparison (the gather
+ * alone with CDC_UNPACK_TRUST), [5] the put, [6] slots and the table build.
+ * Copies min(n, 7) entries and returns 7; CDC_EINVAL for n > 0 with NULL ms. */
+int cdc_debug_pack_split(double *ms, size_t n);
+
 /* What a file's span table holds besides the offsets and digests the reads
  * return: per span the store's table slot and the arena offset resolved when the
  * span was written (HOST arrays of cap entries, either nullable).  Returns the

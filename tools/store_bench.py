@@ -96,6 +96,23 @@ Compare (v) with (d), writing the same bytes again under another name, and (w),
 (x) with the read_plus_verify legs beside them: read_complete_device of one file
 plus cdc_file_verify_device of the other, which names the first differing byte only.
 
+Packs (skipped with --no-pack), on a sending layer holding the 1 GiB file of (d)
+and a receiving layer of the same size:
+
+  (y) cdc_file_pack_device of the whole file -- compare with (b), the store's get
+      of the same bytes;
+  (z) the same against a clone, after the 4 KiB overwrite of (s): the pack of an
+      incremental backup;
+  (aa) cdc_files_unpack_device of the full pack into an empty store, with
+      CDC_UNPACK_TRUST -- compare with (a), the put -- and with the SHA-256 check
+      -- compare with (d), the whole write (the store is cleared before each turn);
+  (ab) cdc_files_unpack_device of the incremental pack into a store that holds
+      the base (the file is removed and the store collected before each turn).
+
+Each reports ms (HIP events around the call on its stream), the call's own wall
+time, its stats and cdc_debug_pack_split of the last call: wall time between the
+call's host waits.
+
 Prints one JSON line; --out also writes it to a file.
 """
 import argparse
@@ -454,6 +471,97 @@ def snapshot_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med):
     return res
 
 
+def pack_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med):
+    """Legs (y)-(ab): the file of (d) packed whole and against a clone after a
+    4 KiB overwrite; both packs unpacked into a second layer."""
+    import numpy as np
+    import torch
+    from chunkfs_amd import _lib
+
+    fresh = torch.empty(4096, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    _lib.check(L.cdc_fill_splitmix64_device(P(fresh.data_ptr()), 4096, a.seed + 13, None))
+    send = c.FileSystem(store=c.ChunkStore(k + (1 << 14), n + 16 * k + (64 << 20)))
+    recv = c.FileSystem(store=c.ChunkStore(k + (1 << 14), n + 16 * k + (64 << 20)))
+    w = send.create_file("bench", ch)
+    assert L.cdc_file_write_device(w._fh, ch._h, P(buf.data_ptr()), n, None) == k
+    st = _lib.cdc_pack_stats_t()
+    res = {}
+    names = ("pack_sizes", "pack_write", "unpack_header", "unpack_validate", "unpack_hash", "unpack_put",
+             "unpack_table")
+
+    def report(name, t, wall, lo, hi):
+        split = (ctypes.c_double * 7)()
+        assert L.cdc_debug_pack_split(split, 7) == 7
+        res[name] = dict({f: getattr(st, f) for f, _ in _lib.cdc_pack_stats_t._fields_ if f != "seconds"},
+                         ms=med(t), ms_min_max=[min(t), max(t)], wall_ms=float(np.median(wall)),
+                         wall_ms_min_max=[min(wall), max(wall)],
+                         GiBps=st.pack_bytes / (1 << 30) / (med(t) * 1e-3),
+                         split_ms=dict(zip(names[lo:hi], list(split)[lo:hi])))
+
+    def pack_leg(name, since, pack):
+        wall = []
+
+        def call():
+            got = L.cdc_file_pack_device(w._fh, since._fh if since else None, None, P(pack.data_ptr()), pack.numel(),
+                                         ctypes.byref(st), P(sp))
+            assert got == pack.numel(), f"cdc_file_pack_device: {got}"
+            wall.append(st.seconds * 1e3)
+
+        t = timed(call)
+        report(name, t, wall[a.warmup:], 0, 2)
+
+    def unpack_leg(name, fsys, fname, pack, flags, before):
+        wall = []
+
+        def call():
+            got = L.cdc_files_unpack_device(fsys._h, fname, P(pack.data_ptr()), pack.numel(),
+                                            None if flags else ch._h, flags, ctypes.byref(st), P(sp))
+            assert got > 0, f"cdc_files_unpack_device: {got} {L.cdc_last_error()}"
+            wall.append(st.seconds * 1e3)
+
+        t = timed(call, before=before)
+        report(name, t, wall[a.warmup:], 2, 7)
+
+    def sized(since):
+        need = L.cdc_file_pack_device(w._fh, since._fh if since else None, None, None, 0, None, None)
+        assert need > 0, f"cdc_file_pack_device: {need}"
+        t = torch.empty(need, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        return t
+
+    full = sized(None)
+    pack_leg("y_pack_full", None, full)
+    unpack_leg("aa_unpack_full_trust", recv, b"bench", full, _lib.CDC_UNPACK_TRUST, recv.clear_database)
+    unpack_leg("aa_unpack_full_verified", recv, b"bench", full, 0, recv.clear_database)
+    r = recv.open_file_readonly("bench")
+    out.zero_()
+    assert L.cdc_file_read_complete_device(r._fh, P(out.data_ptr()), n, None, None) == n
+    torch.cuda.synchronize()
+    if not torch.equal(out, buf) or recv.store.stats() != send.store.stats():
+        raise SystemExit("store_bench: the unpacked file or its store is not the sender's")
+
+    assert L.cdc_files_clone(send._h, b"bench", b"base", None) == k
+    base = send.open_file_readonly("base")
+    assert L.cdc_file_splice_device(w._fh, ch._h, n // 2 + 1234, 4096, P(fresh.data_ptr()), 4096, None, None) >= 0
+    inc = sized(base)
+    pack_leg("z_pack_after_4k_edit", base, inc)
+    assert L.cdc_files_clone(recv._h, b"bench", b"base", None) == k
+
+    def drop():
+        if recv.file_exists("v2"):
+            recv.remove_file("v2")
+            recv.collect()
+
+    unpack_leg("ab_unpack_after_4k_edit", recv, b"v2", inc, 0, drop)
+    r2 = recv.open_file_readonly("v2")
+    first = ctypes.c_uint64(0)
+    assert L.cdc_file_read_complete_device(w._fh, P(out.data_ptr()), n, None, None) == n
+    if L.cdc_file_verify_device(r2._fh, P(out.data_ptr()), n, ctypes.byref(first), None) != 1:
+        raise SystemExit("store_bench: the file unpacked from the incremental pack is not the edited one")
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--bytes", type=int, default=1 << 30)
@@ -466,6 +574,7 @@ def main():
     ap.add_argument("--no-collect", action="store_true", help="skip the remove-and-collect legs (q)-(r)")
     ap.add_argument("--no-splice", action="store_true", help="skip the edit-in-place legs (s)-(u)")
     ap.add_argument("--no-snapshot", action="store_true", help="skip the clone and diff legs (v)-(x)")
+    ap.add_argument("--no-pack", action="store_true", help="skip the pack and unpack legs (y)-(ab)")
     ap.add_argument("--collect-iters", type=int, default=3)
     ap.add_argument("--scrub-iters", type=int, default=3)
     ap.add_argument("--scrub-groups", default="4096,64m;65536,256m;1048576,1024m",
@@ -670,6 +779,8 @@ def main():
         res["splice"] = splice_legs(a, c, L, P, ch, buf, n, k, sp, timed, med)
     if not a.no_snapshot:
         res["snapshot"] = snapshot_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med)
+    if not a.no_pack:
+        res["pack"] = pack_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med)
     line = json.dumps(res)
     print(line)
     if a.out:
