@@ -191,6 +191,18 @@ class Chunker:
                                             None if stream is None else ctypes.c_void_p(stream)))
         self._drained()
 
+    def hash_batch_device(self, d_ptrs, first, d_chunks, d_digests, hash="sha256", stream=None):  # noqa: A002
+        """sha256_batch_device with the hasher named: "sha256" or "blake2sp"
+        (cdc_hash_batch_device)."""
+        ptrs = np.ascontiguousarray(np.asarray(d_ptrs, dtype=np.uint64))
+        fa = np.ascontiguousarray(np.asarray(first, dtype=np.uint64))
+        assert fa.size == ptrs.size + 1
+        check(lib().cdc_hash_batch_device(self._h, _lib.hash_code(hash), int(ptrs.size),
+                                          ctypes.c_void_p(ptrs.ctypes.data), ctypes.c_void_p(fa.ctypes.data),
+                                          ctypes.c_void_p(int(d_chunks)), ctypes.c_void_p(int(d_digests)),
+                                          None if stream is None else ctypes.c_void_p(stream)))
+        self._drained()
+
     def chunk_data(self, data, empty=None):
         """Chunker::chunk_data (src/lib.rs:80): chunks tiling `data`, appended to `empty`."""
         chunks = [] if empty is None else empty
@@ -667,13 +679,31 @@ class ChunkStore:
     insert wins) with ChunkStorage::retrieve (storage.rs:141-157) and
     FileSystem::read_file_complete (system/mod.rs:149-160) on one GPU: a dedup
     index plus an HBM arena of `arena_bytes` holding each first-seen chunk.
-    A refused call (CdcError) changes nothing.  Not thread-safe."""
+    A refused call (CdcError) changes nothing.  Not thread-safe.
 
-    def __init__(self, max_chunks, arena_bytes, device=0):
+    `hash`: the hasher of the store's digests, "sha256" (the default) or
+    "blake2sp" (DESIGN.md "Hashers"); set_hash changes it while the store is
+    empty."""
+
+    def __init__(self, max_chunks, arena_bytes, device=0, hash="sha256"):  # noqa: A002
+        code = _lib.hash_code(hash)
         h = ctypes.c_void_p()
         check(lib().cdc_store_create(device, max_chunks, arena_bytes, ctypes.byref(h)))
         self._h = h
         self.device = device
+        if code != _lib.CDC_HASH_SHA256:
+            self.set_hash(code)
+
+    def set_hash(self, hash):  # noqa: A002
+        """cdc_store_set_hash: refused (CdcError) unless the store is empty, has
+        no target and is no target."""
+        check(lib().cdc_store_set_hash(self._h, _lib.hash_code(hash)))
+
+    @property
+    def hash(self):
+        """The hasher's name: "sha256" or "blake2sp"."""
+        code = lib().cdc_store_hash(self._h)
+        return next(k for k, v in _lib.HASH.items() if v == code)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -833,6 +863,10 @@ class ChunkStore:
         d_chunks = torch.from_numpy(np.ascontiguousarray(chunks).view(np.int64)).to(dev)
         d_new = torch.empty(n, dtype=torch.uint8, device=dev)
         torch.cuda.synchronize(dev)
+        if self.hash != "sha256":  # (chunk_and_hash is SHA-256 only: hash again with the store's hasher)
+            chunker.hash_batch_device([d_data.data_ptr()], [0, n], d_chunks.data_ptr(), d_dig.data_ptr(),
+                                      hash=self.hash)
+            dig = d_dig.cpu().numpy()
         self.put_device(d_data.data_ptr(), nbytes, d_chunks.data_ptr(), d_dig.data_ptr(), n, d_new.data_ptr())
         return chunks, dig, d_new.cpu().numpy().astype(bool)
 
@@ -889,8 +923,14 @@ class FileSystem:
     longer than the segment; chunk_count_distribution leaves out the last span.
     A refused call (CdcError) changes nothing.  Not thread-safe."""
 
-    def __init__(self, store=None, max_chunks=1 << 16, arena_bytes=256 * MB, seg_size=SEG_SIZE, device=0):
-        self.store = store if store is not None else ChunkStore(max_chunks, arena_bytes, device)
+    def __init__(self, store=None, max_chunks=1 << 16, arena_bytes=256 * MB, seg_size=SEG_SIZE, device=0,
+                 hash=None):  # noqa: A002
+        """`hash`: the hasher of a store created here ("sha256" when None); with
+        `store` given it must be that store's, or None."""
+        if store is not None and hash is not None and _lib.hash_code(hash) != _lib.hash_code(store.hash):
+            raise ValueError(f"hash={hash!r}, but the store hashes with {store.hash!r}")
+        self.store = store if store is not None else ChunkStore(max_chunks, arena_bytes, device,
+                                                                hash="sha256" if hash is None else hash)
         self.device = self.store.device
         self.seg_size = int(seg_size)
         h = ctypes.c_void_p()
@@ -899,13 +939,17 @@ class FileSystem:
 
     @classmethod
     def new_with_scrubber(cls, scrubber, target=None, max_chunks=1 << 16, arena_bytes=256 * MB,
-                          target_max_chunks=1 << 18, target_arena_bytes=256 * MB, seg_size=SEG_SIZE, device=0):
+                          target_max_chunks=1 << 18, target_arena_bytes=256 * MB, seg_size=SEG_SIZE, device=0,
+                          hash="sha256"):  # noqa: A002
         """FileSystem::new_with_scrubber (mod.rs:226-239): a file system whose
         store has a target map (`target`, a ChunkStore, created here when None)
-        and whose scrub() runs `scrubber`."""
-        store = ChunkStore(max_chunks, arena_bytes, device)
+        and whose scrub() runs `scrubber`.  `hash`: the hasher of both stores
+        (a `target` passed in is set to it, which needs it empty)."""
+        store = ChunkStore(max_chunks, arena_bytes, device, hash=hash)
         if target is None:
-            target = ChunkStore(target_max_chunks, target_arena_bytes, device)
+            target = ChunkStore(target_max_chunks, target_arena_bytes, device, hash=hash)
+        elif target.hash != store.hash:
+            target.set_hash(hash)
         store.set_target(target)
         fs = cls(store=store, seg_size=seg_size)
         fs.target, fs._scrubber = target, scrubber
@@ -976,7 +1020,7 @@ class FileSystem:
     # -- writes ---------------------------------------------------------------------
     def write_to_file(self, handle, data, stream=None):
         """FileSystem::write_to_file (mod.rs:93-110): one chunk_data over the whole
-        call, SHA-256, put, append -- all on the GPU.  `data` is host bytes
+        call, the store's hasher (SHA-256 or BLAKE2sp), put, append -- all on the GPU.  `data` is host bytes
         (uploaded once) or a CUDA uint8 tensor (no host copy).  Returns the
         number of spans appended."""
         import torch
@@ -1213,8 +1257,9 @@ class FileSystem:
         """cdc_files_unpack_device: creates the file `name` from a pack and
         returns PackStats.  `pack` is a CUDA uint8 tensor on this device, one on
         another device, or host bytes / a numpy array (the last two are copied
-        over).  `hasher`: any Chunker on this device, for the SHA-256 check of
-        the carried chunks; trust=True skips the check (a corrupted data byte
+        over).  `hasher`: any Chunker on this device, for the check of the
+        carried chunks' digests (with the store's hasher; a pack made by a
+        store with another hasher fails the 'flags' check); trust=True skips the check (a corrupted data byte
         is then stored as it is) and needs no hasher.  The pack is validated
         before anything is written: CdcError(CDC_EINVAL) names the failed
         check, CDC_ENOTFOUND an external span whose chunk this store lacks,
@@ -1246,6 +1291,9 @@ class FileSystem:
         chunks are trusted).  Returns (PackStats of the pack, PackStats of the
         unpack)."""
         import torch
+        if self.store.hash != to.store.hash:  # (what the unpack would answer, before anything is packed)
+            raise _lib.CdcError(_lib.CDC_EINVAL, f"send: the pack fails the check 'flags': this store hashes with "
+                                                 f"{self.store.hash}, the receiving store with {to.store.hash}")
         digests = self.hashes(handle)
         n = digests.shape[0]
         have = np.zeros(n, dtype=np.uint8)

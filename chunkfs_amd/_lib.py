@@ -45,6 +45,7 @@ EXPORTS = [
     "cdc_file_splice_device",
     "cdc_files_clone", "cdc_files_diff_device",
     "cdc_file_pack_device", "cdc_files_unpack_device",
+    "cdc_hash_batch_device", "cdc_store_set_hash", "cdc_store_hash",
     "cdc_fill_splitmix64_device", "cdc_version", "cdc_abi_version",
 ]
 # include/chunkfs_amd_debug.h (diagnostics, not part of the drop-in boundary)
@@ -133,6 +134,18 @@ class cdc_diff_stats_t(ctypes.Structure):
 
 CDC_DIFF_TABLES_ONLY = 1
 CDC_UNPACK_TRUST = 1
+CDC_HASH_SHA256 = 0
+CDC_HASH_BLAKE2SP = 1
+HASH = {"sha256": CDC_HASH_SHA256, "blake2sp": CDC_HASH_BLAKE2SP}
+
+
+def hash_code(name):
+    """CDC_HASH_* of a hasher's name ("sha256" | "blake2sp") or of a code."""
+    if isinstance(name, str):
+        if name not in HASH:
+            raise ValueError(f"unknown hasher {name!r}: one of {sorted(HASH)}")
+        return HASH[name]
+    return int(name)
 
 
 class cdc_timing_t(ctypes.Structure):
@@ -262,6 +275,12 @@ def lib():
     L.cdc_store_get_device.restype = ctypes.c_int64
     L.cdc_store_contains_device.argtypes = [P, P, sz, P, P]
     L.cdc_store_contains_device.restype = ctypes.c_int64
+    L.cdc_hash_batch_device.argtypes = [P, ctypes.c_int, sz, P, P, P, P, P]
+    L.cdc_hash_batch_device.restype = ctypes.c_int
+    L.cdc_store_set_hash.argtypes = [P, ctypes.c_int]
+    L.cdc_store_set_hash.restype = ctypes.c_int
+    L.cdc_store_hash.argtypes = [P]
+    L.cdc_store_hash.restype = ctypes.c_int
     L.cdc_store_set_target.argtypes = [P, P]
     L.cdc_store_set_target.restype = ctypes.c_int
     L.cdc_store_scrub.argtypes = [P, ctypes.c_int, P, ctypes.POINTER(cdc_scrub_measurements_t), P]

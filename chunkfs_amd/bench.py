@@ -113,7 +113,7 @@ class DedupMeasurement:
 
 class CDCFixture:
     """CDCFixture (bench/mod.rs:54-283) over a device FileSystem: `fs`, or one
-    created from **fs_kwargs (max_chunks, arena_bytes, ...).  A dataset is
+    created from **fs_kwargs (max_chunks, arena_bytes, hash, ...).  A dataset is
     written with one write_to_file, so it must fit in HBM beside the store, the
     buffer it is read back into and -- during verify -- a second copy of it."""
 

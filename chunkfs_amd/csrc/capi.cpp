@@ -206,8 +206,21 @@ int cdc_sha256_batch_device(cdc_handle_t *h, size_t n_streams, const uint8_t *co
                             const uint64_t *first, const cdc_chunk_t *d_chunks, uint8_t *d_digests,
                             void *hip_stream) {
     if (!h) return (int)bad_handle();
-    return h->engine->sha256_batch(n_streams, d_streams, first, d_chunks, d_digests,
-                                   static_cast<hipStream_t>(hip_stream));
+    return h->engine->hash_batch(CDC_HASH_SHA256, n_streams, d_streams, first, d_chunks, d_digests,
+                                 static_cast<hipStream_t>(hip_stream));
+}
+
+int cdc_hash_batch_device(cdc_handle_t *h, int hash, size_t n_streams, const uint8_t *const *d_streams,
+                          const uint64_t *first, const cdc_chunk_t *d_chunks, uint8_t *d_digests,
+                          void *hip_stream) {
+    if (hash != CDC_HASH_SHA256 && hash != CDC_HASH_BLAKE2SP) {
+        cdc::set_error("cdc_hash_batch_device: unknown hasher " + std::to_string(hash) +
+                       " (CDC_HASH_SHA256 or CDC_HASH_BLAKE2SP)");
+        return CDC_EINVAL;
+    }
+    if (!h) return (int)bad_handle();
+    return h->engine->hash_batch(hash, n_streams, d_streams, first, d_chunks, d_digests,
+                                 static_cast<hipStream_t>(hip_stream), "cdc_hash_batch_device");
 }
 
 int64_t cdc_chunk_and_hash(cdc_handle_t *h, const uint8_t *data, size_t len,

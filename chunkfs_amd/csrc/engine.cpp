@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "blake2sp.hpp"
 #include "fast_engine.hpp"
 #include "sha256.hpp"
 #include "walk_engine.hpp"
@@ -419,39 +420,40 @@ int64_t Engine::fs_write(const uint8_t *data, size_t len, size_t seg_size, std::
 int Engine::sha256_device(const uint8_t *d_data, const cdc_chunk_t *d_chunks, size_t n,
                           uint8_t *d_digests, hipStream_t s) {
     const uint64_t first[2] = {0, n};
-    return sha256_batch(1, &d_data, first, d_chunks, d_digests, s);
+    return hash_batch(CDC_HASH_SHA256, 1, &d_data, first, d_chunks, d_digests, s);
 }
 
-// One launch over every chunk of every stream (sha256.hip); the stream table
-// (first[], bases) goes up through a pinned block with one H2D copy.
-int Engine::sha256_batch(size_t n, const uint8_t *const *d_streams, const uint64_t *first,
-                         const cdc_chunk_t *d_chunks, uint8_t *d_digests, hipStream_t s) {
+// One launch over every chunk of every stream (sha256.hip / blake2sp.hip); the
+// stream table (first[], bases) goes up through a pinned block with one H2D
+// copy.  `who` names the C entry point in the refusals.
+int Engine::hash_batch(int hash, size_t n, const uint8_t *const *d_streams, const uint64_t *first,
+                       const cdc_chunk_t *d_chunks, uint8_t *d_digests, hipStream_t s, const char *who) {
     if (n == 0) return CDC_OK;
     if (!d_streams || !first) {
-        set_error("cdc_sha256_batch_device: NULL stream table");
+        set_error(std::string(who) + ": NULL stream table");
         return CDC_EINVAL;
     }
     if (first[0] != 0) {
-        set_error("cdc_sha256_batch_device: first[0] must be 0");
+        set_error(std::string(who) + ": first[0] must be 0");
         return CDC_EINVAL;
     }
     for (size_t i = 0; i < n; ++i) {
         if (first[i + 1] < first[i]) {
-            set_error("cdc_sha256_batch_device: first[] must be non-decreasing");
+            set_error(std::string(who) + ": first[] must be non-decreasing");
             return CDC_EINVAL;
         }
         if (first[i + 1] > first[i] && !d_streams[i]) {
-            set_error("cdc_sha256_batch_device: NULL stream with chunks");
+            set_error(std::string(who) + ": NULL stream with chunks");
             return CDC_EINVAL;
         }
     }
     const uint64_t total = first[n];
     if (total >= (1ull << 32)) {
-        set_error("cdc_sha256_batch_device: more than 2^32 - 1 chunks in one batch");
+        set_error(std::string(who) + ": more than 2^32 - 1 chunks in one batch");
         return CDC_EINVAL;
     }
     if (total && (!d_chunks || !d_digests)) {
-        set_error("cdc_sha256_chunks_device: NULL argument");
+        set_error(std::string(hash == CDC_HASH_SHA256 ? "cdc_sha256_chunks_device" : who) + ": NULL argument");
         return CDC_EINVAL;
     }
     HIP_TRY(hipSetDevice(device_));
@@ -496,7 +498,7 @@ int Engine::sha256_batch(size_t n, const uint8_t *const *d_streams, const uint64
     }
     b.order = d_sha_order_;
     HIP_TRY(hipEventRecord(ev_[3], st));
-    HIP_TRY(launch_sha256(b, num_cus_, st));
+    HIP_TRY(hash == CDC_HASH_BLAKE2SP ? launch_blake2sp(b, num_cus_, st) : launch_sha256(b, num_cus_, st));
     HIP_TRY(hipEventRecord(ev_[2], st));
     HIP_TRY(hipStreamSynchronize(st));  // (also: the pinned table may be rewritten by the next call)
     float ms = 0;

@@ -61,9 +61,12 @@ class Engine {
     // SHA-256 of chunks of one device-resident stream (Sha256Hasher::hash).
     int sha256_device(const uint8_t *d_data, const cdc_chunk_t *d_chunks, size_t n,
                       uint8_t *d_digests, hipStream_t s);
-    // The same over n streams in one launch (cdc_sha256_batch_device).
-    int sha256_batch(size_t n, const uint8_t *const *d_streams, const uint64_t *first, const cdc_chunk_t *d_chunks,
-                     uint8_t *d_digests, hipStream_t s);
+    // The same over n streams in one launch, with either hasher (CDC_HASH_*:
+    // cdc_hash_batch_device, cdc_sha256_batch_device); `who` names the entry
+    // point in the refusals.
+    int hash_batch(int hash, size_t n, const uint8_t *const *d_streams, const uint64_t *first,
+                   const cdc_chunk_t *d_chunks, uint8_t *d_digests, hipStream_t s,
+                   const char *who = "cdc_sha256_batch_device");
     int64_t chunk_batch_device(size_t n, const uint8_t *const *d_streams,
                                const uint64_t *lens, cdc_chunk_t *d_out,
                                size_t out_cap, uint64_t *first, hipStream_t stream);

@@ -633,7 +633,7 @@ int64_t splice(cdc_fh *fh, cdc_handle_t *chunker, uint64_t offset, uint64_t remo
     uint64_t bytes_new = 0;
     if (m) {
         const uint64_t hfirst[2] = {0, m};
-        if ((rc = cdc_sha256_batch_device(chunker, 1, streams, hfirst, fs->wr.chunks, fs->wr.dig, s)) != CDC_OK) return rc;
+        if ((rc = cdc_hash_batch_device(chunker, cdc_store_hash(fs->store), 1, streams, hfirst, fs->wr.chunks, fs->wr.dig, s)) != CDC_OK) return rc;
         const bool patch = m == j - i0 && insert_len == remove_len;
         cdc::SpanTable nt = f->t;
         uint64_t cap = f->cap;
@@ -790,7 +790,7 @@ int64_t pack_file(cdc_fh *fh, cdc_fh *since, const uint8_t *d_have, uint8_t *d_p
     Laps laps;
 
     // (a), (b): which chunks are carried and where; the one wait for the sizes.
-    cdc::PackHeader h{cdc::kPackMagic, cdc::kPackVersion, 0, f->size, n, 0, 0, 0, 0};
+    cdc::PackHeader h{cdc::kPackMagic, cdc::kPackVersion, cdc::pack_flags((uint32_t)cdc_store_hash(fs->store)), f->size, n, 0, 0, 0, 0};
     uint64_t chunk_bytes = 0;
     if (n) {
         FL_TRY(fs->pack.grow(n));
@@ -867,7 +867,7 @@ int64_t unpack_file(cdc_files *fs, const char *name, const uint8_t *d_pack, uint
     const cdc::PackHeader h = host->header;
     laps.lap(0);
     cdc::PackLayout l{};
-    uint32_t bad = cdc::pack_check_header(h, len, &l);
+    uint32_t bad = cdc::pack_check_header(h, len, &l, (uint32_t)cdc_store_hash(fs->store));
     if (!bad && h.n_spans >= 0xFFFFFFFFull) bad = cdc::kPackSizesCheck;  // a put's own limit
     if (bad) return pack_check_failed(bad, 0, 1);
     const uint64_t n = h.n_spans, nc = h.n_chunks;
@@ -909,7 +909,7 @@ int64_t unpack_file(cdc_files *fs, const char *name, const uint8_t *d_pack, uint
     if (nc && !trust) {
         const uint8_t *streams[1] = {data};
         const uint64_t first[2] = {0, nc};
-        const int rc = cdc_sha256_batch_device(hasher, 1, streams, first, fs->wr.chunks, fs->unpack.sha, s);
+        const int rc = cdc_hash_batch_device(hasher, cdc_store_hash(fs->store), 1, streams, first, fs->wr.chunks, fs->unpack.sha, s);
         if (rc) return rc;
         FL_TRY(cdc::launch_pack_verify(fs->unpack.sha, fs->wr.dig, nc, d_res, s));
         FL_TRY(hipMemcpyAsync(&host->res, d_res, sizeof host->res, hipMemcpyDeviceToHost, s));
@@ -1278,7 +1278,7 @@ int64_t cdc_file_write_device(cdc_fh_t *fh, cdc_handle_t *chunker, const uint8_t
     const int64_t n = cdc_chunk_batch_device(chunker, 1, streams, lens, fs->wr.chunks, cap, first, s);
     if (n < 0) return n;
     const auto t1 = std::chrono::steady_clock::now();
-    rc = cdc_sha256_batch_device(chunker, 1, streams, first, fs->wr.chunks, fs->wr.dig, s);
+    rc = cdc_hash_batch_device(chunker, cdc_store_hash(fs->store), 1, streams, first, fs->wr.chunks, fs->wr.dig, s);
     if (rc) return rc;
     const auto t2 = std::chrono::steady_clock::now();
     const int64_t got = append(fh, d_data, len, fs->wr.chunks, fs->wr.dig, (uint64_t)n, s);
@@ -1358,7 +1358,7 @@ int64_t cdc_files_write_batch_device(cdc_files_t *fs, cdc_handle_t *chunker, siz
                                              sfirst.data(), s);
     if (m < 0) return m;
     const auto t1 = std::chrono::steady_clock::now();
-    int rc = cdc_sha256_batch_device(chunker, ns, streams.data(), sfirst.data(), fs->wr.chunks, fs->wr.dig, s);
+    int rc = cdc_hash_batch_device(chunker, cdc_store_hash(fs->store), ns, streams.data(), sfirst.data(), fs->wr.chunks, fs->wr.dig, s);
     if (rc) return rc;
     const auto t2 = std::chrono::steady_clock::now();
 

@@ -31,6 +31,11 @@ struct PackHeader {
 };
 static_assert(sizeof(PackHeader) == kPackHeaderBytes, "the header is 64 bytes");
 
+// The flags word: bits 0-7 carry the hasher of the pack's digests (CDC_HASH_*:
+// 0 is SHA-256, so a default store's pack has flags 0); every other bit is 0.
+constexpr uint32_t kPackHashMask = 0xFFu;
+CDC_PACK_HD uint32_t pack_flags(uint32_t hash) { return hash & kPackHashMask; }
+
 // Byte offsets of the sections from the start of the pack.
 struct PackLayout {
     uint64_t digest, length, span_chunk, chunk_span, chunk_off, data, total;
@@ -123,10 +128,11 @@ CDC_PACK_HD const char *pack_check_name(uint32_t c) {
 
 // The host's check of a header read from a pack of `len` bytes (len >= 64).
 // On kPackOk *out holds the section offsets, every one of them <= len.
-CDC_PACK_HD uint32_t pack_check_header(const PackHeader &h, uint64_t len, PackLayout *out) {
+// `hash`: the receiving store's hasher (CDC_HASH_*), which the pack must name.
+CDC_PACK_HD uint32_t pack_check_header(const PackHeader &h, uint64_t len, PackLayout *out, uint32_t hash = 0) {
     if (h.magic != kPackMagic) return kPackMagicCheck;
     if (h.version != kPackVersion) return kPackVersionCheck;
-    if (h.flags != 0) return kPackFlagsCheck;
+    if (h.flags != pack_flags(hash)) return kPackFlagsCheck;
     if (h.n_chunks > h.n_spans || (h.data_bytes & (kPackAlign - 1))) return kPackSizesCheck;
     if (!pack_layout(h.n_spans, h.n_chunks, h.data_bytes, out)) return kPackSizesCheck;
     if (out->total != h.total_bytes) return kPackTotalCheck;

@@ -353,8 +353,7 @@ __global__ __launch_bounds__(256) void sha_scatter_kernel(const cdc_chunk_pod *_
 
 }  // namespace
 
-hipError_t launch_sha256(const ShaBatch &b, int num_cus, hipStream_t s) {
-    if (!b.n_chunks) return hipSuccess;
+hipError_t launch_sha_order(const ShaBatch &b, int num_cus, hipStream_t s) {
     hipError_t e = hipMemsetAsync(b.counter, 0, (1 + kShaBuckets) * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
     unsigned long long *hist = b.counter + 1;
@@ -363,6 +362,13 @@ hipError_t launch_sha256(const ShaBatch &b, int num_cus, hipStream_t s) {
     sha_scan_kernel<<<1, 256, 0, s>>>(hist);
     const unsigned tgrid = (unsigned)std::min<uint64_t>((b.n_chunks + kShaTile - 1) / kShaTile, (uint64_t)num_cus * 4);
     sha_scatter_kernel<<<tgrid, 256, 0, s>>>(b.chunks, b.n_chunks, hist, b.order);
+    return hipSuccess;
+}
+
+hipError_t launch_sha256(const ShaBatch &b, int num_cus, hipStream_t s) {
+    if (!b.n_chunks) return hipSuccess;
+    hipError_t e = launch_sha_order(b, num_cus, s);
+    if (e != hipSuccess) return e;
     // Resident waves only (the counter spreads the chunks over them): one
     // block of 4 waves per SIMD-wave slot the kernel's registers allow.
     const bool lds = b.n_streams <= kShaLdsStreams;

@@ -26,4 +26,9 @@ constexpr uint32_t kShaBuckets = 256;  // length classes of the longest-first cl
 
 hipError_t launch_sha256(const ShaBatch &b, int num_cus, hipStream_t s);
 
+// The claim order alone (both hashers start with it): zeroes b.counter, then
+// fills b.order with the chunk indices, longest length class first.  Needs
+// b.n_chunks > 0.
+hipError_t launch_sha_order(const ShaBatch &b, int num_cus, hipStream_t s);
+
 }  // namespace cdc

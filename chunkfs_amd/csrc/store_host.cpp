@@ -51,6 +51,10 @@ struct cdc_store {
     uint64_t target_containers = 0;
     uint64_t scrubbed_bytes = 0;   // unique bytes whose containers are target-kind now
     cdc::ScanScratch<cdc::StorePiece> x;  // get through targets: per piece, with the tile counts
+    // The hasher of every digest in the table (CDC_HASH_*): the file layer and
+    // the re-chunk scrub hash with it; nothing else here reads digests' origin.
+    int hash = CDC_HASH_SHA256;
+    bool is_target = false;        // some store has been given this one as its target
 };
 
 namespace {
@@ -289,6 +293,10 @@ int set_target(cdc_store *st, cdc_store *target) {
         cdc::set_error("cdc_store_set_target: the store holds containers that refer to its present target");
         return CDC_EINVAL;
     }
+    if (st->hash != target->hash) {
+        cdc::set_error("cdc_store_set_target: the two stores have different hashers (cdc_store_set_hash)");
+        return CDC_EINVAL;
+    }
     ST_TRY(hipSetDevice(st->device));
     if (!st->sc.kind) {
         cdc::ScrubState sc{};
@@ -308,6 +316,7 @@ int set_target(cdc_store *st, cdc_store *target) {
     }
     st->target = target;
     st->target_epoch = target->epoch;
+    target->is_target = true;
     return CDC_OK;
 }
 
@@ -473,7 +482,7 @@ int scrub(cdc_store *st, int scrubber, cdc_handle_t *chunker, cdc_scrub_measurem
         const uint64_t a = gstart[g], ng = gstart[g + 1] - a;
         const int64_t n = chunk_group(g);
         if (n < 0) return (int)n;
-        int rc = cdc_sha256_batch_device(chunker, ng, &ptrs[a], first.data(), d_sub, d_dig, s);
+        int rc = cdc_hash_batch_device(chunker, st->hash, ng, &ptrs[a], first.data(), d_sub, d_dig, s);
         if (rc) return rc;
         if (groups == 1 && (rc = reserve_keys(st, st->keys_used + (uint64_t)n, s)) != CDC_OK) return rc;
         const int64_t got = put(tg, ng, &ptrs[a], &lens[a], first.data(), d_sub, d_dig, nullptr, s);
@@ -813,6 +822,23 @@ int cdc_store_clear(cdc_store_t *st) {
     }
     return reset(st);
 }
+
+int cdc_store_set_hash(cdc_store_t *st, int hash) {
+    const char *why = hash != CDC_HASH_SHA256 && hash != CDC_HASH_BLAKE2SP ? "unknown hasher (CDC_HASH_SHA256 or CDC_HASH_BLAKE2SP)"
+                      : !st                                                  ? "NULL store"
+                      : st->st.unique_chunks                                 ? "the store holds chunks (cdc_store_clear it first)"
+                      : st->target                                           ? "a target store is attached"
+                      : st->is_target                                        ? "the store is another store's target"
+                                                                             : nullptr;
+    if (why) {
+        cdc::set_error(std::string("cdc_store_set_hash: ") + why);
+        return CDC_EINVAL;
+    }
+    st->hash = hash;
+    return CDC_OK;
+}
+
+int cdc_store_hash(const cdc_store_t *st) { return st ? st->hash : CDC_HASH_SHA256; }
 
 int cdc_store_stats(const cdc_store_t *st, cdc_store_stats_t *out) {
     if (!st || !out) {

@@ -45,7 +45,9 @@ extern "C" {
  *    cdc_splice_stats_t; snapshots and diffs -- cdc_files_clone,
  *    cdc_files_diff_device, cdc_diff_stats_t, CDC_DIFF_TABLES_ONLY; packs --
  *    cdc_file_pack_device, cdc_files_unpack_device, cdc_pack_stats_t,
- *    CDC_UNPACK_TRUST. */
+ *    CDC_UNPACK_TRUST; the second hasher -- CDC_HASH_SHA256,
+ *    CDC_HASH_BLAKE2SP, cdc_hash_batch_device, cdc_store_set_hash,
+ *    cdc_store_hash. */
 #define CHUNKFS_AMD_ABI_VERSION 6
 
 /* Chunk{offset,length} -- reference src/lib.rs:43-47 (usize fields; u64 here). */
@@ -332,6 +334,21 @@ int cdc_sha256_batch_device(cdc_handle_t *h, size_t n_streams,
                             const cdc_chunk_t *d_chunks, uint8_t *d_digests,
                             void *hip_stream);
 
+/* The chunk hashers (the reference is generic over its Hasher trait,
+ * src/hashers.rs).  Both give 32-byte digests, so every table, index key and
+ * pack section has one layout.  CDC_HASH_BLAKE2SP is unkeyed BLAKE2sp-256
+ * (8 BLAKE2s leaves and a root: DESIGN.md "Hashers"), digest bytes in
+ * BLAKE2's own order. */
+#define CDC_HASH_SHA256 0
+#define CDC_HASH_BLAKE2SP 1
+
+/* cdc_sha256_batch_device with the hasher as an argument: the same arrays,
+ * validation, refusals and hash_ms.  An unknown `hash` is CDC_EINVAL.
+ * cdc_sha256_batch_device is this call with CDC_HASH_SHA256. */
+int cdc_hash_batch_device(cdc_handle_t *h, int hash, size_t n_streams,
+                          const uint8_t *const *d_streams, const uint64_t *first,
+                          const cdc_chunk_t *d_chunks, uint8_t *d_digests, void *hip_stream);
+
 /* chunk_data + SHA-256 of each chunk on a HOST buffer: as cdc_chunk_data, and
  * digests[32*i ..] for the first min(count, cap) chunks. */
 int64_t cdc_chunk_and_hash(cdc_handle_t *h, const uint8_t *data, size_t len,
@@ -520,8 +537,20 @@ typedef struct cdc_scrub_stats {
 /* ChunkStorage::new_with_scrubber's target_map (storage.rs:165-178): `target`
  * becomes the target map of `base` (not owned: destroy the base first).
  * CDC_EINVAL if either is NULL, base == target, they are on different devices,
- * `target` has a target itself, or `base` holds target-kind containers. */
+ * `target` has a target itself, `base` holds target-kind containers, or the
+ * two stores have different hashers (cdc_store_set_hash). */
 int cdc_store_set_target(cdc_store_t *base, cdc_store_t *target);
+/* The hasher of the store's digests (CDC_HASH_*; a new store: CDC_HASH_SHA256):
+ * the file layer (single and batch write, splice, the unpack's integrity
+ * check) and the RECHUNK scrub hash with it, and a pack carries it in its
+ * header.  cdc_store_put_device takes digests as given: the caller hashes with
+ * cdc_hash_batch_device(cdc_store_hash(st)).  Changing it is allowed only
+ * while the store is empty and stands alone: CDC_EINVAL if the store holds a
+ * chunk (after cdc_store_clear it is allowed again), a target store is
+ * attached, the store has been made another store's target, or `hash` is
+ * unknown. */
+int cdc_store_set_hash(cdc_store_t *st, int hash);
+int cdc_store_hash(const cdc_store_t *st);
 /* ChunkStorage::scrub (storage.rs:180-190) with one of the CDC_SCRUB_*
  * scrubbers; CDC_EINVAL without a target ("scrubber cannot be used with CDC
  * filesystem").  `chunker` is used by RECHUNK only and must be on the store's

@@ -117,6 +117,13 @@ class Chunker {
         return spans;
     }
 
+    // cdc_hash_batch_device: the digests of a batch's chunks with either
+    // hasher (CDC_HASH_SHA256 / CDC_HASH_BLAKE2SP).
+    void hash_batch_device(int hash, size_t n_streams, const uint8_t *const *d_streams, const uint64_t *first,
+                           const cdc_chunk_t *d_chunks, uint8_t *d_digests, void *hip_stream = nullptr) {
+        check(cdc_hash_batch_device(h_, hash, n_streams, d_streams, first, d_chunks, d_digests, hip_stream));
+    }
+
     cdc_handle_t *handle() { return h_; }
 
   protected:
@@ -218,9 +225,17 @@ using ChunkerRef = std::shared_ptr<Chunker>;
 // DEVICE pointers; a refused call throws and changes nothing.  Not thread-safe.
 class Store {
   public:
-    Store(size_t max_chunks, size_t arena_bytes, int device = 0) {
+    Store(size_t max_chunks, size_t arena_bytes, int device = 0, int hash = CDC_HASH_SHA256) {
         check(cdc_store_create(device, max_chunks, arena_bytes, &st_));
+        if (hash != CDC_HASH_SHA256 && cdc_store_set_hash(st_, hash) != CDC_OK) {
+            cdc_store_destroy(st_);
+            check(CDC_EINVAL);
+        }
     }
+    // The hasher of the store's digests; set_hash only while the store is
+    // empty, has no target and is no target.
+    void set_hash(int hash) { check(cdc_store_set_hash(st_, hash)); }
+    int hash() const { return cdc_store_hash(st_); }
     ~Store() { cdc_store_destroy(st_); }
     Store(const Store &) = delete;
     Store &operator=(const Store &) = delete;

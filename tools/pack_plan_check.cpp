@@ -113,6 +113,20 @@ void check_header() {
     CHECK(cdc::pack_check_header(h, l.total, &got) == cdc::kPackVersionCheck);
     h = good, h.flags = 1;
     CHECK(cdc::pack_check_header(h, l.total, &got) == cdc::kPackFlagsCheck);
+    // The hasher in bits 0-7: accepted by a receiver with the same hasher only,
+    // and no other bit may be set.
+    CHECK(cdc::pack_flags(0) == 0 && cdc::pack_flags(1) == 1);
+    CHECK(cdc::pack_check_header(h, l.total, &got, 1) == cdc::kPackOk && got.total == l.total);
+    CHECK(cdc::pack_check_header(good, l.total, &got, 0) == cdc::kPackOk);
+    CHECK(cdc::pack_check_header(good, l.total, &got, 1) == cdc::kPackFlagsCheck);
+    CHECK(cdc::pack_check_header(h, l.total, &got, 0) == cdc::kPackFlagsCheck);
+    for (uint32_t bit = 8; bit < 32; ++bit) {
+        h = good, h.flags = 1u << bit;
+        CHECK(cdc::pack_check_header(h, l.total, &got, 0) == cdc::kPackFlagsCheck);
+        h.flags |= 1;
+        CHECK(cdc::pack_check_header(h, l.total, &got, 1) == cdc::kPackFlagsCheck);
+        CHECK(cdc::pack_check_header(h, l.total, &got, 0) == cdc::kPackFlagsCheck);
+    }
     h = good, h.n_chunks = 6;
     CHECK(cdc::pack_check_header(h, l.total, &got) == cdc::kPackSizesCheck);
     h = good, h.data_bytes = 65;

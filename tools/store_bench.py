@@ -113,6 +113,19 @@ Each reports ms (HIP events around the call on its stream), the call's own wall
 time, its stats and cdc_debug_pack_split of the last call: wall time between the
 call's host waits.
 
+The two hashers (skipped with --no-hash, alone with --only-hash), SHA-256 and
+BLAKE2sp in the same run, each leg on layers of its own per hasher:
+
+  (ac) hash_ms of cdc_hash_batch_device over 4 chunks of 16 KiB, and over one;
+  (ad) the 4 KiB overwrite of (s);
+  (ae) the incremental unpack with the check of (ab);
+  (af) the whole write of (d);
+  (ag) hash_ms over config 3's chunk list (RabinCDC 2/4/8 KiB over a 256 MiB base
+       and 15 edited copies, about 4 GiB), the two hashers alternating.
+
+Each reports the median and the min-max per hasher and SHA-256's time over
+BLAKE2sp's; the two conditions of DESIGN.md "Hashers" are evaluated at the end.
+
 Prints one JSON line; --out also writes it to a file.
 """
 import argparse
@@ -562,6 +575,144 @@ def pack_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med):
     return res
 
 
+def hash_legs(a, c, L, P, ch, buf, n, k, sp, timed, med):
+    """Legs (ac)-(ag): both hashers, SHA-256 and BLAKE2sp, side by side in one
+    run (DESIGN.md "Hashers").  (ac) hash_ms of a batch of 4 chunks of 16 KiB and
+    of one; (ad) the 4 KiB overwrite of (s); (ae) the incremental unpack with the
+    check of (ab); (af) the whole write of (d); (ag) the bulk hash over config 3's
+    chunk list (bench.py: RabinCDC 2/4/8 KiB over a 256 MiB base and 15 edited
+    copies).  Every figure is the median of a.iters calls after a.warmup."""
+    import torch
+    from chunkfs_amd import _lib
+    from chunkfs_amd.synthetic import versioned_archive
+
+    hashers = ("sha256", "blake2sp")
+    res = {}
+
+    def both(name, leg):
+        r = {h: leg(h) for h in hashers}
+        r["sha256_over_blake2sp"] = r["sha256"]["ms"] / r["blake2sp"]["ms"]
+        res[name] = r
+
+    def stat(ms, **more):
+        return dict(ms=med(ms), ms_min_max=[min(ms), max(ms)], **more)
+
+    # (ac) few chunks: the engine's own hash_ms (order kernels + hash kernel)
+    few = torch.tensor([[i * 16384, 16384] for i in range(4)], dtype=torch.int64, device="cuda")
+    fdig = torch.empty((4, 32), dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+
+    def few_leg(count):
+        def leg(h):
+            ms = []
+            for _ in range(a.warmup + a.iters):
+                ch.hash_batch_device([buf.data_ptr()], [0, count], few.data_ptr(), fdig.data_ptr(), hash=h, stream=sp)
+                ms.append(ch.last_timing()["hash_ms"])
+            return stat(ms[a.warmup:])
+        return leg
+
+    both("ac_hash_4x16k", few_leg(4))
+    both("ac_hash_1x16k", few_leg(1))
+
+    # (ad) the 4 KiB overwrite in the file of (d), (af) the whole write
+    edit = 4096
+    fresh = torch.empty(edit * 64, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    _lib.check(L.cdc_fill_splitmix64_device(P(fresh.data_ptr()), fresh.numel(), a.seed + 7, None))
+
+    def overwrite_leg(h):
+        fsys = c.FileSystem(store=c.ChunkStore(k + (1 << 14), n + 16 * k + (256 << 20), hash=h))
+        w = fsys.create_file("bench", ch)
+        assert L.cdc_file_write_device(w._fh, ch._h, P(buf.data_ptr()), n, None) == k
+        turn = {"i": 0}
+
+        def call():
+            src = fresh.data_ptr() + (turn["i"] % 64) * edit
+            turn["i"] += 1
+            assert L.cdc_file_splice_device(w._fh, ch._h, n // 2 + 1234, edit, P(src), edit, None, P(sp)) >= 0
+
+        ms = timed(call)
+        split = (ctypes.c_double * 5)()
+        assert L.cdc_debug_splice_split(split, 5) == 5
+        return stat(ms, hash_ms=ch.last_timing()["hash_ms"],
+                    split_ms=dict(zip(("planner", "chunk", "resync", "hash_put", "table_build"), split)))
+
+    def write_leg(h):
+        fsys = c.FileSystem(store=c.ChunkStore(k, n + 16 * k, hash=h))
+        state = {}
+
+        def new_file():
+            fsys.clear_database()
+            state["w"] = fsys.create_file("bench", ch)
+
+        def call():
+            assert L.cdc_file_write_device(state["w"]._fh, ch._h, P(buf.data_ptr()), n, P(sp)) == k
+
+        ms = timed(call, before=new_file)
+        return stat(ms, hash_ms=ch.last_timing()["hash_ms"], GiBps=n / (1 << 30) / (med(ms) * 1e-3))
+
+    # (ae) the incremental unpack with the check
+    def unpack_leg(h):
+        send = c.FileSystem(store=c.ChunkStore(k + (1 << 14), n + 16 * k + (64 << 20), hash=h))
+        recv = c.FileSystem(store=c.ChunkStore(k + (1 << 14), n + 16 * k + (64 << 20), hash=h))
+        w = send.create_file("bench", ch)
+        assert L.cdc_file_write_device(w._fh, ch._h, P(buf.data_ptr()), n, None) == k
+        full, _ = send.pack(w)
+        recv.unpack("bench", full, trust=True)
+        del full
+        assert L.cdc_files_clone(send._h, b"bench", b"base", None) == k
+        base = send.open_file_readonly("base")
+        assert L.cdc_file_splice_device(w._fh, ch._h, n // 2 + 1234, edit, P(fresh.data_ptr()), edit, None, None) >= 0
+        inc, pst = send.pack(w, since=base)
+        st = _lib.cdc_pack_stats_t()
+
+        def drop():
+            if recv.file_exists("v2"):
+                recv.remove_file("v2")
+                recv.collect()
+
+        def call():
+            got = L.cdc_files_unpack_device(recv._h, b"v2", P(inc.data_ptr()), inc.numel(), ch._h, 0,
+                                            ctypes.byref(st), P(sp))
+            assert got > 0, f"cdc_files_unpack_device: {got} {L.cdc_last_error()}"
+
+        ms = timed(call, before=drop)
+        split = (ctypes.c_double * 7)()
+        assert L.cdc_debug_pack_split(split, 7) == 7
+        return stat(ms, chunks=pst.chunks, chunk_bytes=pst.chunk_bytes, hash_ms=ch.last_timing()["hash_ms"],
+                    unpack_hash_ms=split[4])
+
+    both("ad_overwrite_4k", overwrite_leg)
+    both("ae_unpack_after_4k_edit", unpack_leg)
+    both("af_file_write", write_leg)
+
+    # (ag) the bulk hash: config 3's chunk list, the hashers alternating
+    files = versioned_archive(256 << 20, 16)
+    bufs = [torch.from_numpy(f).cuda() for f in files]
+    lens = [f.size for f in files]
+    total = sum(lens)
+    rabin = c.RabinChunker(c.SizeParams(2048, 4096, 8192))
+    cap = rabin.batch_max_chunks(lens)
+    recs = torch.empty((cap, 2), dtype=torch.int64, device="cuda")
+    dig = torch.empty((cap, 32), dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    ptrs = [b.data_ptr() for b in bufs]
+    first = rabin.chunk_batch_device(ptrs, lens, recs.data_ptr(), cap)
+    bulk = {h: [] for h in hashers}
+    for it in range(a.warmup + a.iters):
+        for h in hashers:
+            rabin.hash_batch_device(ptrs, first, recs.data_ptr(), dig.data_ptr(), hash=h)
+            if it >= a.warmup:
+                bulk[h].append(rabin.last_timing()["hash_ms"])
+    res["ag_bulk_hash_config3"] = {h: stat(bulk[h], GiBps=total / (1 << 30) / (med(bulk[h]) * 1e-3)) for h in hashers}
+    res["ag_bulk_hash_config3"].update(bytes=int(total), chunks=int(first[-1]),
+                                       sha256_over_blake2sp=med(bulk["sha256"]) / med(bulk["blake2sp"]))
+    # The two conditions of DESIGN.md "Hashers".
+    res["condition_few_chunks_3p9x"] = res["ac_hash_4x16k"]["sha256_over_blake2sp"] >= 3.9
+    res["condition_bulk_no_slower"] = med(bulk["blake2sp"]) <= max(bulk["sha256"])
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--bytes", type=int, default=1 << 30)
@@ -575,6 +726,8 @@ def main():
     ap.add_argument("--no-splice", action="store_true", help="skip the edit-in-place legs (s)-(u)")
     ap.add_argument("--no-snapshot", action="store_true", help="skip the clone and diff legs (v)-(x)")
     ap.add_argument("--no-pack", action="store_true", help="skip the pack and unpack legs (y)-(ab)")
+    ap.add_argument("--no-hash", action="store_true", help="skip the two-hasher legs (ac)-(ag)")
+    ap.add_argument("--only-hash", action="store_true", help="the two-hasher legs (ac)-(ag) alone")
     ap.add_argument("--collect-iters", type=int, default=3)
     ap.add_argument("--scrub-iters", type=int, default=3)
     ap.add_argument("--scrub-groups", default="4096,64m;65536,256m;1048576,1024m",
@@ -625,6 +778,19 @@ def main():
             if it >= warmup:
                 ms.append(e0.elapsed_time(e1))
         return ms
+
+    def finish(res):
+        print(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
+
+    if a.only_hash:
+        med = lambda v: float(np.median(v))  # noqa: E731
+        return finish({"tool": "store_bench", "bytes": n, "chunks": k, "iters": a.iters, "warmup": a.warmup,
+                       "device": torch.cuda.get_device_name(0), "source_digest": build.source_digest(),
+                       "hash": hash_legs(a, c, _lib.lib(), ctypes.c_void_p, ch, buf, n, k, sp, timed, med)})
 
     def do_put():
         got = store.put_batch_device([buf.data_ptr()], [n], first, chunks.data_ptr(), dig.data_ptr(), stream=sp)
@@ -781,12 +947,9 @@ def main():
         res["snapshot"] = snapshot_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med)
     if not a.no_pack:
         res["pack"] = pack_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med)
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(json.dumps(res, indent=1) + "\n")
+    if not a.no_hash:
+        res["hash"] = hash_legs(a, c, L, P, ch, buf, n, k, sp, timed, med)
+    finish(res)
 
 
 if __name__ == "__main__":
