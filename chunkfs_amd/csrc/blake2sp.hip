@@ -11,18 +11,20 @@
 // its chunk (512 contiguous bytes) and every lane compresses its own; after
 // the last leaf step the group spends 4 more steps on the root, in which lane
 // 0 compresses the leaf digests (read from its neighbours by ds_bpermute) and
-// the other 7 lanes idle.  Work distribution is sha256.hip's at group
-// granularity: a resident grid, the longest-first claim order
-// (launch_sha_order), and groups that refill from the global counter after
-// every step through the same claim / describe / take-over pipeline.
+// the other 7 lanes idle.  Work distribution is the SHA-256 kernel's at group
+// granularity (hash_feed.hpp, ChunkFeed<8>): a resident grid, the
+// longest-first claim order (launch_sha_order), and groups that refill from
+// the global counter after every step through the claim / describe /
+// take-over pipeline.
 //
 // Message words are little-endian, so a block is 17 aligned dwords funnelled
-// by one v_perm per word with no byte swap; the load forms (16-byte loads
-// where the 68-byte window cannot leave the stream's buffer, guarded dword
-// loads at a stream's tail) are sha256.hip's.
+// by one v_perm per word with no byte swap; the load forms are the shared
+// load_window's.
 #include "blake2sp.hpp"
 
 #include <algorithm>
+
+#include "hash_feed.hpp"
 
 namespace cdc {
 namespace {
@@ -44,19 +46,6 @@ constexpr uint32_t kParam0 = 0x02080020u;
 constexpr uint32_t kParam3Leaf = 0x20000000u, kParam3Root = 0x20010000u;
 
 constexpr int kB2Threads = 256;
-constexpr uint32_t kB2LdsStreams = 2048;  // stream tables up to this many streams are staged in LDS
-constexpr uint64_t kLeaders = 0x0101010101010101ull;  // lane 0 of every group
-
-typedef const __attribute__((address_space(1))) uint32_t g_u32;
-typedef const __attribute__((address_space(1))) uint64_t g_u64c;
-typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-typedef const __attribute__((address_space(1))) u32x4_a4 g_u32x4_a4;
-
-__device__ __forceinline__ uint32_t rotr(uint32_t x, int n) { return __builtin_rotateright32(x, n); }
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
-    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-}
-
 // One BLAKE2s compression of block m into h: byte counter t, finalisation
 // flags f0 (last block of the node) and f1 (last node of its layer).
 __device__ __forceinline__ void compress(uint32_t (&h)[8], const uint32_t (&m)[16], uint64_t t, uint32_t f0,
@@ -99,32 +88,11 @@ __device__ __forceinline__ void compress(uint32_t (&h)[8], const uint32_t (&m)[1
 // The 16 little-endian message words of the 64 bytes at offset p of the chunk
 // at src (len bytes): zeros from the chunk's end on (a final partial block goes
 // to its leaf zero-filled; p >= len gives an all-zero block and loads nothing).
-// `over`: the 68-byte window may run past the chunk's end (sha256.hip's rule).
+// `over`: the 68-byte window may run past the chunk's end (hash_feed.hpp).
 // Wave-synchronous (the tail mask runs when any lane needs it).
 __device__ __forceinline__ void block_words_le(uint32_t (&W)[16], uint64_t src, uint64_t len, uint64_t p, bool over) {
-    const uint64_t a = src + p;
-    const uint32_t sh = (uint32_t)(a & 3);
-    const uint64_t al = a - sh;
     uint32_t d[17];
-    if (p >= len) {
-#pragma unroll
-        for (int i = 0; i < 17; ++i) d[i] = 0;
-    } else if (over || p + 68 <= len) {
-        g_u32x4_a4 *q = (g_u32x4_a4 *)al;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const u32x4_a4 v = q[i];
-            d[4 * i] = v.x;
-            d[4 * i + 1] = v.y;
-            d[4 * i + 2] = v.z;
-            d[4 * i + 3] = v.w;
-        }
-        d[16] = sh ? *(g_u32 *)(al + 64) : 0u;
-    } else {
-        const uint64_t end = src + len;
-#pragma unroll
-        for (int i = 0; i < 17; ++i) d[i] = al + 4 * i < end ? *(g_u32 *)(al + 4 * i) : 0u;
-    }
+    const uint32_t sh = load_window(d, src, len, p, over);
     const uint32_t sel = ((sh + 3) << 24) | ((sh + 2) << 16) | ((sh + 1) << 8) | sh;
 #pragma unroll
     for (int i = 0; i < 16; ++i) W[i] = __builtin_amdgcn_perm(d[i + 1], d[i], sel);
@@ -143,19 +111,12 @@ __device__ __forceinline__ void block_words_le(uint32_t (&W)[16], uint64_t src, 
 
 template <bool kLds>
 __global__ __launch_bounds__(kB2Threads) void blake2sp_kernel(const ShaBatch j) {
-    extern __shared__ uint64_t tab[];  // (kLds) first[n+1] ++ base[n], (2n+1) * 8 bytes of dynamic LDS
-    const uint64_t *first = j.first, *sbase = j.base;
-    if constexpr (kLds) {
-        for (uint32_t i = threadIdx.x; i <= 2 * j.n_streams; i += kB2Threads)
-            tab[i] = i <= j.n_streams ? *(g_u64c *)(j.first + i) : *(g_u64c *)(j.base + (i - j.n_streams - 1));
-        __syncthreads();
-        first = tab;
-        sbase = tab + j.n_streams + 1;
-    }
+    extern __shared__ uint64_t tab[];  // (kLds) the stream table
+    const uint64_t *first, *sbase;
+    stage_stream_table<kLds, kB2Threads>(j, tab, first, sbase);
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t g = lane & 7;        // the lane's leaf
     const uint32_t glead = lane & ~7u;  // lane 0 of its group
-    const uint64_t leaders_lt = kLeaders & ((1ull << glead) - 1);
     // The group's chunk (the same in its 8 lanes; ci ~0: idle): steps 0 ..
     // nsteps-1 hash the leaves, nsteps .. nsteps+3 the root.
     uint64_t ci = ~0ull, src = 0, len = 0, nb = 0, step = 0, nsteps = 0;
@@ -163,50 +124,22 @@ __global__ __launch_bounds__(kB2Threads) void blake2sp_kernel(const ShaBatch j) 
     uint32_t h[8], dg[8];  // the running state; the lane's finished leaf digest
 #pragma unroll
     for (int i = 0; i < 8; ++i) h[i] = dg[i] = 0;
-    // next chunk: stage 0 = none, 1 = index claimed, 2 = described, 3 = counter exhausted
-    uint32_t nst = 0;
-    uint64_t ni = 0, nsrc = 0;
-    cdc_chunk_pod nc{}, nn{};
-    bool nhas = false;
+    ChunkFeed<8> next;
     for (;;) {
         // (3) an idle group takes the next chunk over
-        if (nst == 2 && ci == ~0ull) {
-            ci = ni;
-            src = nsrc + nc.offset;
-            len = nc.length;
-            over = nhas && nn.offset == nc.offset + nc.length && nn.length >= 68;
+        if (next.ready() && ci == ~0ull) {
+            ci = next.index();
+            src = next.src();
+            len = next.length();
+            over = next.over();
             nb = (len + 63) / 64;
             nsteps = nb ? (nb + 7) / 8 : 1;  // (an empty chunk still finalises 8 empty leaves)
             step = 0;
-            nst = 0;
+            next.taken();
         }
-        // (2) describe a claimed index: its stream, and the loads of its record
-        if (nst == 1) {
-            ni = j.order[ni];  // claims go longest chunk first
-            uint32_t lo = 0, hi = j.n_streams;  // largest s with first[s] <= ni
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (first[mid] <= ni) lo = mid; else hi = mid;
-            }
-            nsrc = sbase[lo];
-            nhas = ni + 1 < first[lo + 1];
-            nc = j.chunks[ni];
-            nn = j.chunks[nhas ? ni + 1 : ni];
-            nst = 2;
-        }
-        // (1) claim indices for the groups with an empty next stage
-        const uint64_t want = __ballot(nst == 0) & kLeaders;
-        if (want) {
-            unsigned long long base = 0;
-            if (lane == 0) base = atomicAdd(j.counter, (unsigned long long)__popcll(want));
-            base = __shfl(base, 0);
-            if (nst == 0) {
-                ni = base + (uint64_t)__popcll(want & leaders_lt);
-                nst = ni < j.n_chunks ? 1u : 3u;
-            }
-        }
+        next.advance(j, first, sbase, lane);
         const bool have = ci != ~0ull;
-        if (__ballot(have || nst == 1 || nst == 2) == 0) break;  // nothing left anywhere in the wave
+        if (__ballot(have || next.pending()) == 0) break;  // nothing left anywhere in the wave
         if (__ballot(have) == 0) continue;  // (the pipeline is still filling)
         // One step of every group: a leaf block per lane, or a root block in
         // lane 0.  Lanes with nothing to do compress a zero block and keep
@@ -282,21 +215,13 @@ hipError_t launch_blake2sp(const ShaBatch &b, int num_cus, hipStream_t s) {
     if (!b.n_chunks) return hipSuccess;
     hipError_t e = launch_sha_order(b, num_cus, s);
     if (e != hipSuccess) return e;
-    // Resident waves only, as launch_sha256: a wave takes 8 chunks at a time.
-    const bool lds = b.n_streams <= kB2LdsStreams;
+    const bool lds = b.n_streams <= kHashLdsStreams;
     const size_t dyn = lds ? (2 * b.n_streams + 1) * sizeof(uint64_t) : 0;
-    int per_cu = 0;
-    e = lds ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, blake2sp_kernel<true>, kB2Threads, dyn)
-            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, blake2sp_kernel<false>, kB2Threads, 0);
+    const auto kernel = lds ? blake2sp_kernel<true> : blake2sp_kernel<false>;
+    unsigned grid = 0;
+    e = hash_grid(kernel, kB2Threads, dyn, b.n_chunks, 8, num_cus, &grid);  // a wave takes 8 chunks at a time
     if (e != hipSuccess) return e;
-    const uint64_t waves = (b.n_chunks + 7) / 8;
-    const uint64_t want = (waves + 3) / 4;
-    const uint64_t cap = (uint64_t)num_cus * (uint64_t)(per_cu > 0 ? per_cu : 1);
-    const unsigned grid = (unsigned)(want < cap ? want : cap);
-    if (lds)
-        blake2sp_kernel<true><<<grid, kB2Threads, dyn, s>>>(b);
-    else
-        blake2sp_kernel<false><<<grid, kB2Threads, 0, s>>>(b);
+    kernel<<<grid, kB2Threads, dyn, s>>>(b);
     return hipGetLastError();
 }
 

@@ -1,4 +1,5 @@
-// blake2sp.hpp -- launch interface of the per-chunk BLAKE2sp kernel (blake2sp.hip).
+// blake2sp.hpp -- launch interface of the per-chunk BLAKE2sp kernel
+// (blake2sp.hip); called by HashEngine (hash_engine.cpp).
 #pragma once
 #include "sha256.hpp"
 

@@ -1,7 +1,8 @@
 // engine.cpp -- the handle behind the C ABI: argument checks, dispatch of the
 // device batches to the handle's backend (FastEngine, WalkEngine or the
-// fixed-size launch below), the drain results held for cdc_batch_sync,
-// SHA-256 and the debug entries.  The host boundary is in hostpath.cpp.
+// fixed-size launch below), the drain results held for cdc_batch_sync, the
+// hash calls (HashEngine) and the debug entries.  The host boundary is in
+// hostpath.cpp.
 #include "engine.hpp"
 
 #include <algorithm>
@@ -9,9 +10,8 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "blake2sp.hpp"
 #include "fast_engine.hpp"
-#include "sha256.hpp"
+#include "hash_engine.hpp"
 #include "walk_engine.hpp"
 
 namespace cdc {
@@ -117,8 +117,7 @@ int Engine::init() {
     num_cus_ = prop.multiProcessorCount;
     HIP_TRY(hipStreamCreateWithFlags(&own_stream_, hipStreamNonBlocking));
     for (auto &ev : ev_) HIP_TRY(hipEventCreate(&ev));
-    HIP_TRY(hipMalloc(&d_counter_, (1 + kShaBuckets) * sizeof(unsigned long long)));  // SHA-256 counter + histogram
-    return CDC_OK;
+    return HashEngine::create(num_cus_, hash_);
 }
 
 Engine::~Engine() {
@@ -127,15 +126,12 @@ Engine::~Engine() {
     walk_.reset();
     if (own_stream_) (void)hipStreamSynchronize(own_stream_);
     fast_.reset();
+    hash_.reset();
     (void)hipFree(fixed_.d_block);
     (void)hipHostFree(fixed_.h_block);
     (void)hipFree(d_data_);
     (void)hipFree(d_out_);
     (void)hipFree(d_dig_);
-    (void)hipFree(d_sha_tab_);
-    (void)hipHostFree(h_sha_tab_);
-    (void)hipFree(d_sha_order_);
-    (void)hipFree(d_counter_);
     if (copy_stream_) (void)hipStreamSynchronize(copy_stream_);
     (void)hipHostFree(h_ring_);
     (void)hipHostFree(h_ready_);
@@ -337,13 +333,13 @@ int64_t Engine::run_fixed(size_t n, const uint8_t *const *d_streams, const uint6
     HIP_TRY(hipEventRecord(ev_[0], s));
     HIP_TRY(hipMemcpyAsync(f.d_first, f.h_first, (n + 1) * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(launch_fixed(st, min_, f.d_first, d_out, t, s));
-    HIP_TRY(hipEventRecord(ev_[3], s));
+    HIP_TRY(hipEventRecord(ev_[1], s));
     HIP_TRY(hipStreamSynchronize(s));
     std::memcpy(first, f.h_first, (n + 1) * 8);
-    float t03 = 0;
-    HIP_TRY(hipEventElapsedTime(&t03, ev_[0], ev_[3]));
-    timing_.total_ms = t03;
-    timing_.scan_ms = t03;
+    float t01 = 0;
+    HIP_TRY(hipEventElapsedTime(&t01, ev_[0], ev_[1]));
+    timing_.total_ms = t01;
+    timing_.scan_ms = t01;
     timing_.path = CDC_PATH_FIXED;
     timing_.timed = 1;
     return (int64_t)first[n];
@@ -359,7 +355,7 @@ const cdc_timing_t &Engine::timing() {
 }
 
 // A batch's timing as cdc_last_timing reports it: hash_ms stays the last
-// SHA-256 call's (reported with the batch it hashed, until the next hash).
+// hash call's (reported with the batch it hashed, until the next hash).
 void Engine::report(const cdc_timing_t &batch) {
     const double hash_ms = timing_.hash_ms;
     timing_ = batch;
@@ -391,7 +387,7 @@ int64_t Engine::debug_copy(int what, void *out, size_t max_bytes) {
     return fast_->debug_copy(what, out, max_bytes);
 }
 
-// ---- write of one buffer, SHA-256, device utilities ----------------------------------
+// ---- write of one buffer, the hashers, device utilities ------------------------------
 
 int64_t Engine::fs_write(const uint8_t *data, size_t len, size_t seg_size, std::vector<uint64_t> &spans,
                          double *seconds) {
@@ -423,9 +419,8 @@ int Engine::sha256_device(const uint8_t *d_data, const cdc_chunk_t *d_chunks, si
     return hash_batch(CDC_HASH_SHA256, 1, &d_data, first, d_chunks, d_digests, s);
 }
 
-// One launch over every chunk of every stream (sha256.hip / blake2sp.hip); the
-// stream table (first[], bases) goes up through a pinned block with one H2D
-// copy.  `who` names the C entry point in the refusals.
+// One launch over every chunk of every stream (HashEngine::run).  `who` names
+// the C entry point in the refusals.
 int Engine::hash_batch(int hash, size_t n, const uint8_t *const *d_streams, const uint64_t *first,
                        const cdc_chunk_t *d_chunks, uint8_t *d_digests, hipStream_t s, const char *who) {
     if (n == 0) return CDC_OK;
@@ -461,48 +456,13 @@ int Engine::hash_batch(int hash, size_t n, const uint8_t *const *d_streams, cons
         const int64_t r = drain_implicit();
         if (r < 0) return (int)r;
     }
-    hipStream_t st = s ? s : own_stream_;
     if (total == 0) {
         timing_.hash_ms = 0;
         return CDC_OK;
     }
-    const size_t words = 2 * n + 1;
-    if (sha_tab_cap_ < words) {
-        (void)hipFree(d_sha_tab_);
-        (void)hipHostFree(h_sha_tab_);
-        d_sha_tab_ = h_sha_tab_ = nullptr;
-        sha_tab_cap_ = 0;
-        const size_t want = words + 64;
-        HIP_TRY(hipMalloc(&d_sha_tab_, want * 8));
-        HIP_TRY(hipHostMalloc(&h_sha_tab_, want * 8, hipHostMallocDefault));
-        sha_tab_cap_ = want;
-    }
-    std::memcpy(h_sha_tab_, first, (n + 1) * 8);
-    for (size_t i = 0; i < n; ++i) h_sha_tab_[n + 1 + i] = reinterpret_cast<uint64_t>(d_streams[i]);
-    HIP_TRY(hipMemcpyAsync(d_sha_tab_, h_sha_tab_, words * 8, hipMemcpyHostToDevice, st));
-    ShaBatch b{};
-    b.chunks = reinterpret_cast<const cdc_chunk_pod *>(d_chunks);
-    b.n_chunks = total;
-    b.first = d_sha_tab_;
-    b.base = d_sha_tab_ + n + 1;
-    b.n_streams = (uint32_t)n;
-    b.digests = reinterpret_cast<uint32_t *>(d_digests);
-    b.counter = d_counter_;
-    if (sha_order_cap_ < total) {
-        (void)hipFree(d_sha_order_);
-        d_sha_order_ = nullptr;
-        sha_order_cap_ = 0;
-        const uint64_t want = total + total / 8 + 1024;
-        HIP_TRY(hipMalloc(&d_sha_order_, want * sizeof(uint32_t)));
-        sha_order_cap_ = want;
-    }
-    b.order = d_sha_order_;
-    HIP_TRY(hipEventRecord(ev_[3], st));
-    HIP_TRY(hash == CDC_HASH_BLAKE2SP ? launch_blake2sp(b, num_cus_, st) : launch_sha256(b, num_cus_, st));
-    HIP_TRY(hipEventRecord(ev_[2], st));
-    HIP_TRY(hipStreamSynchronize(st));  // (also: the pinned table may be rewritten by the next call)
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, ev_[3], ev_[2]));
+    const int rc = hash_->run(hash, n, d_streams, first, d_chunks, d_digests, total, s ? s : own_stream_, &ms);
+    if (rc != CDC_OK) return rc;
     timing_.hash_ms = ms;
     return CDC_OK;
 }
@@ -520,10 +480,10 @@ int Engine::read_bw(const uint8_t *d_buf, size_t len, int reps, double *ms) {
     if (e == hipSuccess) e = launch_read_reduce(d_buf, len, d_acc, num_cus_, own_stream_);  // (warm-up)
     if (e == hipSuccess) e = hipEventRecord(ev_[0], own_stream_);
     for (int r = 0; e == hipSuccess && r < reps; ++r) e = launch_read_reduce(d_buf, len, d_acc, num_cus_, own_stream_);
-    if (e == hipSuccess) e = hipEventRecord(ev_[3], own_stream_);
-    if (e == hipSuccess) e = hipEventSynchronize(ev_[3]);
+    if (e == hipSuccess) e = hipEventRecord(ev_[1], own_stream_);
+    if (e == hipSuccess) e = hipEventSynchronize(ev_[1]);
     float t = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&t, ev_[0], ev_[3]);
+    if (e == hipSuccess) e = hipEventElapsedTime(&t, ev_[0], ev_[1]);
     (void)hipFree(d_acc);
     if (e != hipSuccess) {
         set_error(std::string("read_bw: ") + hipGetErrorString(e));

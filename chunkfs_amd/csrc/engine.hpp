@@ -5,9 +5,10 @@
 // dispatches device batches to its backend -- FastCDC's FastEngine
 // (fast_engine.hpp), a segment-walk rule's (Rabin / Ultra / Leap / Seq / AE)
 // WalkEngine (walk_engine.hpp), or the fixed-size path, which is one launch
-// here -- keeps the result of a drain made on the caller's behalf, hashes
-// (SHA-256) and owns the host boundary (hostpath.cpp).  Not thread-safe (the
-// reference serialises through a Mutex, src/lib.rs:89-90).
+// here -- keeps the result of a drain made on the caller's behalf, hands the
+// hash calls (SHA-256, BLAKE2sp) to its HashEngine (hash_engine.hpp) and owns
+// the host boundary (hostpath.cpp).  Not thread-safe (the reference serialises
+// through a Mutex, src/lib.rs:89-90).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,6 +21,7 @@
 namespace cdc {
 
 class FastEngine;
+class HashEngine;
 class WalkEngine;
 struct WalkConfig;
 
@@ -91,7 +93,7 @@ class Engine {
     int set_rabin_poly(uint64_t poly);
     const char *describe() const { return describe_.c_str(); }
     // Kernel durations of the last batch (the backend's, read on request),
-    // with hash_ms of the last SHA-256 call.
+    // with hash_ms of the last hash call (either hasher).
     const cdc_timing_t &timing();
     // Kernel times of the FastCDC batch `back` calls before the last one
     // (event ring, include/chunkfs_amd_debug.h).
@@ -133,6 +135,7 @@ class Engine {
     // handle; a fixed-size handle has neither.
     std::unique_ptr<FastEngine> fast_;
     std::unique_ptr<WalkEngine> walk_;
+    std::unique_ptr<HashEngine> hash_;  // every handle's: the hashers' scratch and launch
     // Host boundary (hostpath.cpp).
     int ensure_ring();
     int ensure_host_out(size_t chunks);
@@ -147,11 +150,11 @@ class Engine {
     std::string describe_;
 
     hipStream_t own_stream_ = nullptr;
-    hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};  // [0], [3]: fixed-size batch, read_bw; [3], [2]: SHA-256
+    hipEvent_t ev_[2] = {nullptr, nullptr};  // start, end: of a fixed-size batch, of read_bw's timed launches
     int64_t held_ = 0;              // result of the last implicit drain (hold)
     bool held_valid_ = false;
     // What cdc_last_timing reports: the backend's timing (the fixed-size
-    // path's own) with hash_ms carried from the last SHA-256 call.
+    // path's own) with hash_ms carried from the last hash call.
     cdc_timing_t timing_{};
 
     // Fixed-size path: one call's stream tables ++ first[n+1], staged in a
@@ -208,11 +211,6 @@ class Engine {
     size_t d_out_cap_ = 0;
     uint8_t *d_dig_ = nullptr;               // [d_dig_cap_ * 32] digests (host path)
     size_t d_dig_cap_ = 0;
-    unsigned long long *d_counter_ = nullptr;  // SHA-256 work counter
-    uint64_t *d_sha_tab_ = nullptr, *h_sha_tab_ = nullptr;  // SHA-256 batch stream table: first[n+1] ++ bases[n]
-    size_t sha_tab_cap_ = 0;
-    uint32_t *d_sha_order_ = nullptr;  // SHA-256 claim order (longest chunk first)
-    uint64_t sha_order_cap_ = 0;
 };
 
 }  // namespace cdc

@@ -7,10 +7,12 @@
 //
 // Layout: one LANE per chunk (a chunk's 64-byte blocks are inherently
 // sequential); a launch takes the chunks of many streams at once (a batch:
-// cdc_sha256_batch_device), so a 4 GiB archive is one launch of ~1M lanes.  Chunk lengths vary (min..max), so lanes are refilled
-// dynamically: after every block, lanes whose chunk is done take the next
-// chunk indices from a global counter (one atomic per wave per refill), and a
-// wave leaves only when the counter is exhausted and all its lanes are idle.
+// cdc_sha256_batch_device), so a 4 GiB archive is one launch of ~1M lanes.
+// Chunk lengths vary (min..max), so lanes are refilled dynamically: after
+// every block, lanes whose chunk is done take the next chunk indices from a
+// global counter, and a wave leaves only when the counter is exhausted and all
+// its lanes are idle.  That pipeline, the block loads and the grid size are
+// shared with blake2sp.hip (hash_feed.hpp); the claim order (below) is too.
 // Each block's 16 big-endian words are built from 17 aligned dwords with one
 // v_perm_b32 per word (funnel shift + byte swap in one instruction); the last
 // one or two blocks (0x80 terminator, bit length) are masked in registers.
@@ -19,6 +21,8 @@
 #include "sha256.hpp"
 
 #include <algorithm>
+
+#include "hash_feed.hpp"
 
 namespace cdc {
 namespace {
@@ -38,119 +42,52 @@ constexpr uint32_t kH0[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
 
 constexpr int kShaThreads = 256;
 
-typedef const __attribute__((address_space(1))) uint32_t g_u32;
-typedef const __attribute__((address_space(1))) uint64_t g_u64c;
-// 16-byte loads at a 4-byte-aligned address (a chunk starts at any byte).
-typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-typedef const __attribute__((address_space(1))) u32x4_a4 g_u32x4_a4;
-
-__device__ __forceinline__ uint32_t rotr(uint32_t x, int n) { return __builtin_rotateright32(x, n); }
-// Three-input XOR in one v_bitop3_b32 (truth table 0x96); LLVM emits two
-// v_xor_b32 for the plain expression.
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
-    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-}
-
-// kS independent messages at once (a lane's chunk slots): the rounds of all
-// of them in one unrolled body, so their dependency chains interleave.
-template <int kS>
-__device__ __forceinline__ void compress(uint32_t (&H)[kS][8], uint32_t (&W)[kS][16]) {
-    uint32_t a[kS], b[kS], c[kS], d[kS], e[kS], f[kS], g[kS], h[kS];
-#pragma unroll
-    for (int k = 0; k < kS; ++k) {
-        a[k] = H[k][0]; b[k] = H[k][1]; c[k] = H[k][2]; d[k] = H[k][3];
-        e[k] = H[k][4]; f[k] = H[k][5]; g[k] = H[k][6]; h[k] = H[k][7];
-    }
+// One message block into the state.
+__device__ __forceinline__ void compress(uint32_t (&H)[8], uint32_t (&W)[16]) {
+    uint32_t a = H[0], b = H[1], c = H[2], d = H[3], e = H[4], f = H[5], g = H[6], h = H[7];
 #pragma unroll
     for (int t = 0; t < 64; ++t) {
-#pragma unroll
-        for (int k = 0; k < kS; ++k) {
-            uint32_t w;
-            if (t < 16) {
-                w = W[k][t];
-            } else {
-                const uint32_t w15 = W[k][(t + 1) & 15], w2 = W[k][(t + 14) & 15];
-                const uint32_t s0 = xor3(rotr(w15, 7), rotr(w15, 18), w15 >> 3);
-                const uint32_t s1 = xor3(rotr(w2, 17), rotr(w2, 19), w2 >> 10);
-                w = W[k][t & 15] + s0 + W[k][(t + 9) & 15] + s1;
-                W[k][t & 15] = w;
-            }
-            const uint32_t S1 = xor3(rotr(e[k], 6), rotr(e[k], 11), rotr(e[k], 25));
-            const uint32_t ch = (e[k] & f[k]) ^ (~e[k] & g[k]);
-            const uint32_t t1 = h[k] + S1 + ch + kK[t] + w;
-            const uint32_t S0 = xor3(rotr(a[k], 2), rotr(a[k], 13), rotr(a[k], 22));
-            const uint32_t mj = (a[k] & b[k]) ^ (a[k] & c[k]) ^ (b[k] & c[k]);
-            const uint32_t t2 = S0 + mj;
-            h[k] = g[k];
-            g[k] = f[k];
-            f[k] = e[k];
-            e[k] = d[k] + t1;
-            d[k] = c[k];
-            c[k] = b[k];
-            b[k] = a[k];
-            a[k] = t1 + t2;
+        uint32_t w;
+        if (t < 16) {
+            w = W[t];
+        } else {
+            const uint32_t w15 = W[(t + 1) & 15], w2 = W[(t + 14) & 15];
+            const uint32_t s0 = xor3(rotr(w15, 7), rotr(w15, 18), w15 >> 3);
+            const uint32_t s1 = xor3(rotr(w2, 17), rotr(w2, 19), w2 >> 10);
+            w = W[t & 15] + s0 + W[(t + 9) & 15] + s1;
+            W[t & 15] = w;
         }
+        const uint32_t S1 = xor3(rotr(e, 6), rotr(e, 11), rotr(e, 25));
+        const uint32_t ch = (e & f) ^ (~e & g);
+        const uint32_t t1 = h + S1 + ch + kK[t] + w;
+        const uint32_t S0 = xor3(rotr(a, 2), rotr(a, 13), rotr(a, 22));
+        const uint32_t mj = (a & b) ^ (a & c) ^ (b & c);
+        const uint32_t t2 = S0 + mj;
+        h = g;
+        g = f;
+        f = e;
+        e = d + t1;
+        d = c;
+        c = b;
+        b = a;
+        a = t1 + t2;
     }
-#pragma unroll
-    for (int k = 0; k < kS; ++k) {
-        H[k][0] += a[k]; H[k][1] += b[k]; H[k][2] += c[k]; H[k][3] += d[k];
-        H[k][4] += e[k]; H[k][5] += f[k]; H[k][6] += g[k]; H[k][7] += h[k];
-    }
+    H[0] += a; H[1] += b; H[2] += c; H[3] += d;
+    H[4] += e; H[5] += f; H[6] += g; H[7] += h;
 }
 
 __device__ __forceinline__ uint32_t bswap(uint32_t x) { return __builtin_bswap32(x); }
 
-// Work distribution: a lane hashes one chunk at a time and keeps the NEXT
-// chunk claimed and described ahead of time, in a three-stage pipeline that
-// advances one stage per block step -- (1) claim an index (one atomic per wave
-// for all lanes that need one), (2) find its stream (binary search of the
-// batch's first[] in LDS) and issue the loads of its record and its
-// successor's, (3) take it over when the current chunk ends.  Each stage's
-// latency (L2 atomic, record loads) then hides behind a step of compression
-// instead of stalling the wave at every refill (~2 of 3 steps see a lane
-// finish: 64 lanes, ~65 blocks per 4 KiB chunk).  Waves leave when every lane
-// is idle and the counter is exhausted.
-//
-// A block of the message is 17 dwords from the 4-byte-aligned address below
-// it, realigned by one v_perm per big-endian word; the 68-byte window is read
-// with four 16-byte loads and one dword load whenever it cannot run past
-// readable memory: inside the chunk, or past its end into the next chunk of
-// the same stream when that one is contiguous and >= 68 bytes ("over": every
-// chunk but the last one or two of a stream).  Otherwise (a stream's last
-// chunk tail) each dword is loaded only if it holds a chunk byte.  The words
-// of the last one or two blocks (0x80 terminator, zeros, 64-bit bit length)
-// are masked in registers, without byte loops.
-constexpr uint32_t kShaLdsStreams = 2048;  // stream tables up to this many streams are staged in LDS
-
 // The 16 big-endian message words of block `blk` of the chunk at src (len
-// bytes, nblk blocks with the padding): see the kernel's comment for the
-// load forms.  Wave-synchronous (the padding mask runs when any lane needs it).
+// bytes, nblk blocks with the padding), from load_window's 17 dwords by one
+// v_perm_b32 per word.  The words of the last one or two blocks (0x80
+// terminator, zeros, 64-bit bit length) are masked in registers, without byte
+// loops.  Wave-synchronous (the padding mask runs when any lane needs it).
 __device__ __forceinline__ void block_words(uint32_t (&W)[16], uint64_t src, uint64_t len, uint64_t blk,
                                             uint64_t nblk, bool over) {
     const uint64_t p = 64 * blk;  // block start within the chunk
-    const uint64_t a = src + p;
-    const uint32_t sh = (uint32_t)(a & 3);
-    const uint64_t al = a - sh;
     uint32_t d[17];
-    if (p >= len) {  // a padding-only block (or an idle slot: len 0)
-#pragma unroll
-        for (int i = 0; i < 17; ++i) d[i] = 0;
-    } else if (over || p + 68 <= len) {
-        g_u32x4_a4 *q = (g_u32x4_a4 *)al;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const u32x4_a4 v = q[i];
-            d[4 * i] = v.x;
-            d[4 * i + 1] = v.y;
-            d[4 * i + 2] = v.z;
-            d[4 * i + 3] = v.w;
-        }
-        d[16] = sh ? *(g_u32 *)(al + 64) : 0u;
-    } else {
-        const uint64_t end = src + len;
-#pragma unroll
-        for (int i = 0; i < 17; ++i) d[i] = al + 4 * i < end ? *(g_u32 *)(al + 4 * i) : 0u;
-    }
+    const uint32_t sh = load_window(d, src, len, p, over);
     const uint32_t sel = (sh << 24) | ((sh + 1) << 16) | ((sh + 2) << 8) | (sh + 3);
 #pragma unroll
     for (int i = 0; i < 16; ++i) W[i] = __builtin_amdgcn_perm(d[i + 1], d[i], sel);
@@ -175,109 +112,45 @@ __device__ __forceinline__ void block_words(uint32_t (&W)[16], uint64_t src, uin
     }
 }
 
-#ifndef CDC_SHA_WPE  // min waves per SIMD (VGPR cap 512 / n); 0: the compiler's choice
-#define CDC_SHA_WPE 0
-#endif
-#if CDC_SHA_WPE
-#define CDC_SHA_ATTR __attribute__((amdgpu_waves_per_eu(CDC_SHA_WPE)))
-#else
-#define CDC_SHA_ATTR
-#endif
-#ifndef CDC_SHA_SLOTS  // chunks per lane hashed at once (interleaved compression chains)
-#define CDC_SHA_SLOTS 1  // (2: measured slower, 7.4 vs 6.9 ms per 4 GiB, profiles/r06/r06d_*)
-#endif
-template <bool kLds, int kS>
-__global__ __launch_bounds__(kShaThreads) CDC_SHA_ATTR void sha256_kernel(const ShaBatch j) {
-    extern __shared__ uint64_t tab[];  // (kLds) first[n+1] ++ base[n], (2n+1) * 8 bytes of dynamic LDS
-    const uint64_t *first = j.first, *sbase = j.base;
-    if constexpr (kLds) {
-        for (uint32_t i = threadIdx.x; i <= 2 * j.n_streams; i += kShaThreads)
-            tab[i] = i <= j.n_streams ? *(g_u64c *)(j.first + i) : *(g_u64c *)(j.base + (i - j.n_streams - 1));
-        __syncthreads();
-        first = tab;
-        sbase = tab + j.n_streams + 1;
-    }
+// One chunk per lane at a time, fed by ChunkFeed<1> (hash_feed.hpp).  (2 chunks
+// per lane, their compression chains interleaved: 7.4 vs 6.9 ms per 4 GiB.)
+template <bool kLds>
+__global__ __launch_bounds__(kShaThreads) void sha256_kernel(const ShaBatch j) {
+    extern __shared__ uint64_t tab[];  // (kLds) the stream table
+    const uint64_t *first, *sbase;
+    stage_stream_table<kLds, kShaThreads>(j, tab, first, sbase);
     const uint32_t lane = threadIdx.x & 63;
-    const uint64_t lanemask_lt = (1ull << lane) - 1;
-    // the lane's chunk slots (ci ~0: idle, len 0)
-    uint64_t ci[kS], src[kS], len[kS], blk[kS], nblk[kS];
-    bool over[kS];
-    uint32_t H[kS][8];
-#pragma unroll
-    for (int k = 0; k < kS; ++k) {
-        ci[k] = ~0ull;
-        src[k] = len[k] = blk[k] = nblk[k] = 0;
-        over[k] = false;
-    }
-    // next chunk: stage 0 = none, 1 = index claimed, 2 = described, 3 = counter exhausted
-    uint32_t nst = 0;
-    uint64_t ni = 0, nsrc = 0;
-    cdc_chunk_pod nc{}, nn{};
-    bool nhas = false;
+    // the lane's chunk (ci ~0: idle, len 0)
+    uint64_t ci = ~0ull, src = 0, len = 0, blk = 0, nblk = 0;
+    bool over = false;
+    uint32_t H[8];
+    ChunkFeed<1> next;
     for (;;) {
-        // (3) an idle slot takes the next chunk over
-        if (nst == 2) {
-            bool took = false;
+        // (3) an idle lane takes the next chunk over
+        if (next.ready() && ci == ~0ull) {
+            ci = next.index();
+            src = next.src();
+            len = next.length();
+            over = next.over();
+            blk = 0;
+            nblk = (len + 9 + 63) / 64;  // message + 0x80 + 64-bit length, padded
 #pragma unroll
-            for (int k = 0; k < kS; ++k) {
-                if (!took && ci[k] == ~0ull) {
-                    ci[k] = ni;
-                    src[k] = nsrc + nc.offset;
-                    len[k] = nc.length;
-                    over[k] = nhas && nn.offset == nc.offset + nc.length && nn.length >= 68;
-                    blk[k] = 0;
-                    nblk[k] = (nc.length + 9 + 63) / 64;  // message + 0x80 + 64-bit length, padded
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) H[k][i] = kH0[i];
-                    took = true;
-                }
-            }
-            if (took) nst = 0;
+            for (int i = 0; i < 8; ++i) H[i] = kH0[i];
+            next.taken();
         }
-        // (2) describe a claimed index: its stream, and the loads of its record
-        if (nst == 1) {
-            ni = j.order[ni];  // claims go longest chunk first
-            uint32_t lo = 0, hi = j.n_streams;  // largest s with first[s] <= ni
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (first[mid] <= ni) lo = mid; else hi = mid;
-            }
-            nsrc = sbase[lo];
-            nhas = ni + 1 < first[lo + 1];
-            nc = j.chunks[ni];
-            nn = j.chunks[nhas ? ni + 1 : ni];
-            nst = 2;
-        }
-        // (1) claim indices for the lanes with an empty next stage
-        const uint64_t want = __ballot(nst == 0);
-        if (want) {
-            unsigned long long base = 0;
-            if (lane == 0) base = atomicAdd(j.counter, (unsigned long long)__popcll(want));
-            base = __shfl(base, 0);
-            if (nst == 0) {
-                ni = base + (uint64_t)__popcll(want & lanemask_lt);
-                nst = ni < j.n_chunks ? 1u : 3u;
-            }
-        }
-        bool busy = nst == 1 || nst == 2;
+        next.advance(j, first, sbase, lane);
+        if (__ballot(next.pending() || ci != ~0ull) == 0) break;  // nothing left anywhere in the wave
+        // one block (an idle lane hashes a dummy block: the lanes run in
+        // lockstep anyway, and its state is reset at take-over)
+        uint32_t W[16];
+        block_words(W, src, len, blk, nblk, over);
+        compress(H, W);
+        if (ci != ~0ull && ++blk == nblk) {
+            uint32_t *o = j.digests + 8 * ci;
 #pragma unroll
-        for (int k = 0; k < kS; ++k) busy |= ci[k] != ~0ull;
-        if (__ballot(busy) == 0) break;  // nothing left anywhere in the wave
-        // one block of every slot (an idle slot hashes a dummy block: the
-        // lanes run in lockstep anyway, and its state is reset at take-over)
-        uint32_t W[kS][16];
-#pragma unroll
-        for (int k = 0; k < kS; ++k) block_words(W[k], src[k], len[k], blk[k], nblk[k], over[k]);
-        compress<kS>(H, W);
-#pragma unroll
-        for (int k = 0; k < kS; ++k) {
-            if (ci[k] != ~0ull && ++blk[k] == nblk[k]) {
-                uint32_t *o = j.digests + 8 * ci[k];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) o[i] = bswap(H[k][i]);  // big-endian digest bytes
-                ci[k] = ~0ull;
-                len[k] = blk[k] = nblk[k] = 0;
-            }
+            for (int i = 0; i < 8; ++i) o[i] = bswap(H[i]);  // big-endian digest bytes
+            ci = ~0ull;
+            len = blk = nblk = 0;
         }
     }
 }
@@ -369,22 +242,13 @@ hipError_t launch_sha256(const ShaBatch &b, int num_cus, hipStream_t s) {
     if (!b.n_chunks) return hipSuccess;
     hipError_t e = launch_sha_order(b, num_cus, s);
     if (e != hipSuccess) return e;
-    // Resident waves only (the counter spreads the chunks over them): one
-    // block of 4 waves per SIMD-wave slot the kernel's registers allow.
-    const bool lds = b.n_streams <= kShaLdsStreams;
+    const bool lds = b.n_streams <= kHashLdsStreams;
     const size_t dyn = lds ? (2 * b.n_streams + 1) * sizeof(uint64_t) : 0;
-    int per_cu = 0;
-    e = lds ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sha256_kernel<true, CDC_SHA_SLOTS>, kShaThreads, dyn)
-            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sha256_kernel<false, CDC_SHA_SLOTS>, kShaThreads, 0);
+    const auto kernel = lds ? sha256_kernel<true> : sha256_kernel<false>;
+    unsigned grid = 0;
+    e = hash_grid(kernel, kShaThreads, dyn, b.n_chunks, 64, num_cus, &grid);  // a wave takes 64 chunks at a time
     if (e != hipSuccess) return e;
-    const uint64_t waves = (b.n_chunks + 64 * CDC_SHA_SLOTS - 1) / (64 * CDC_SHA_SLOTS);
-    const uint64_t want = (waves + 3) / 4;
-    const uint64_t cap = (uint64_t)num_cus * (uint64_t)(per_cu > 0 ? per_cu : 1);
-    const unsigned grid = (unsigned)(want < cap ? want : cap);
-    if (lds)
-        sha256_kernel<true, CDC_SHA_SLOTS><<<grid, kShaThreads, dyn, s>>>(b);
-    else
-        sha256_kernel<false, CDC_SHA_SLOTS><<<grid, kShaThreads, 0, s>>>(b);
+    kernel<<<grid, kShaThreads, dyn, s>>>(b);
     return hipGetLastError();
 }
 

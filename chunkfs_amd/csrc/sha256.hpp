@@ -1,4 +1,7 @@
-// sha256.hpp -- launch interface of the per-chunk SHA-256 kernel (sha256.hip).
+// sha256.hpp -- launch interface of the per-chunk SHA-256 kernel (sha256.hip),
+// with the batch description and the claim order that both hashers use
+// (blake2sp.hpp; the kernels' shared device code is hash_feed.hpp).  The caller
+// is HashEngine (hash_engine.cpp), which owns the scratch a batch points to.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,8 +12,9 @@ namespace cdc {
 
 // A batch: the chunks of n_streams streams, stream i's chunks at
 // chunks[first[i] .. first[i+1]) with offsets relative to base[i] (DEVICE
-// arrays).  digests[8*k .. 8*k+8) (u32, big-endian bytes) = SHA-256 of chunk
-// k.  counter / order: device scratch (work distribution, claim order).
+// arrays).  digests[8*k .. 8*k+8) (u32) = the digest of chunk k (SHA-256:
+// big-endian bytes).  counter / order: device scratch (work distribution,
+// claim order).
 struct ShaBatch {
     const cdc_chunk_pod *chunks;
     uint64_t n_chunks;

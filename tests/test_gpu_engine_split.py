@@ -1,7 +1,8 @@
 """The seams between the handle (Engine) and its backends (-m gpu): the
-fixed-size path on its own buffers, cdc_last_timing across backends and the
-small kernel's hand-over to the pipeline.  Every chunk list and every first[]
-is compared bit for bit with the CPU oracle (no tolerances).
+fixed-size path on its own buffers, cdc_last_timing across backends, the
+hashers' scratch (HashEngine) across hashers and regrowth, and the small
+kernel's hand-over to the pipeline.  Every chunk list, every first[] and every
+digest is compared bit for bit with the CPU oracle (no tolerances).
 """
 import hashlib
 
@@ -158,6 +159,56 @@ def test_timing_across_backends_rabin():
     import chunkfs_amd as c
     ch = c.RabinChunker(c.SizeParams(*FAST))
     _hash_then_batch(ch, torch, lambda a: oracle.cdc("rabin", a, *FAST), PATH_WALK)
+    ch.close()
+
+
+def test_hash_scratch_across_hashers_and_regrowth():
+    """The HashEngine's buffers on one handle, both hashers alternating: a first
+    call that sizes them for 1 stream and 3 chunks (1 / 67 / 69 bytes from an odd
+    address), 5000 chunks (the order buffer regrows; past the 4096-chunk scatter
+    tile), 2049 streams (the stream table regrows and is read from global
+    memory), a chunking batch in between that leaves hash_ms alone, and a last
+    call smaller than everything allocated.  Every digest against the host's."""
+    import torch
+    import chunkfs_amd as c
+    from test_gpu_blake2sp import _assert_rows, _run, _want
+    from test_gpu_sha256 import _digests
+    rng = np.random.default_rng(41)
+    host = rng.integers(0, 256, MIB + 4096, dtype=np.uint8)
+    dev = torch.from_numpy(host).to("cuda:0")
+    ch = c.FastChunker(c.SizeParams(*FAST))
+
+    # 1. SHA-256: the first chunk starts at byte 1 of the buffer
+    recs = np.array([(1, 1), (2, 67), (69, 69)], dtype=np.uint64)
+    got = _run(ch, [dev.data_ptr()], [0, 3], recs, hash="sha256")
+    _assert_rows(got, _digests(host, recs), recs, "call 1, SHA-256, 3 chunks")
+    assert ch.last_timing()["hash_ms"] > 0
+
+    # 2. BLAKE2sp: 5000 chunks of 64..600 bytes
+    recs = np.stack([rng.integers(64, MIB - 700, 5000), rng.integers(64, 601, 5000)], axis=1).astype(np.uint64)
+    got = _run(ch, [dev.data_ptr()], [0, 5000], recs)
+    _assert_rows(got, _want(host, recs), recs, "call 2, BLAKE2sp, 5000 chunks")
+
+    # 3. SHA-256: 2049 streams (4-byte aligned) of one chunk each
+    starts = 4 * rng.integers(0, (MIB - 700) // 4, 2049)
+    recs = np.stack([rng.integers(0, 4, 2049), rng.integers(0, 601, 2049)], axis=1).astype(np.uint64)
+    got = _run(ch, [dev.data_ptr() + int(s) for s in starts], list(range(2050)), recs, hash="sha256")
+    absolute = np.stack([starts + recs[:, 0].astype(np.int64), recs[:, 1].astype(np.int64)], axis=1)
+    _assert_rows(got, _digests(host, absolute), recs, "call 3, SHA-256, 2049 streams")
+    t3 = ch.last_timing()
+    assert t3["hash_ms"] > 0
+
+    # 4. a chunking batch reports its own timing and call 3's hash_ms
+    out, first = _device_batch(ch, torch, dev, 0, MIB)
+    _same(_rows(out, first, 1)[0], oracle.fastcdc(host[:MIB], *FAST), "call 4, 1 MiB batch")
+    t4 = ch.last_timing()
+    assert t4["bytes"] == MIB and t4["hash_ms"] == t3["hash_ms"], (t3, t4)
+
+    # 5. BLAKE2sp: an empty chunk and one of 513 bytes
+    recs = np.array([(5, 0), (7, 513)], dtype=np.uint64)
+    got = _run(ch, [dev.data_ptr()], [0, 2], recs)
+    _assert_rows(got, _want(host, recs), recs, "call 5, BLAKE2sp, 2 chunks")
+    assert ch.last_timing()["hash_ms"] > 0
     ch.close()
 
 
