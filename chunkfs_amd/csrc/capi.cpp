@@ -6,6 +6,7 @@
 #include "../../include/chunkfs_amd.h"
 #include "../../include/chunkfs_amd_debug.h"
 #include "engine.hpp"
+#include "host_path.hpp"
 
 struct cdc_handle {
     cdc::Engine *engine;
@@ -66,7 +67,7 @@ void cdc_destroy(cdc_handle_t *h) {
 int64_t cdc_chunk_data(cdc_handle_t *h, const uint8_t *data, size_t len,
                        cdc_chunk_t *out, size_t cap) {
     if (!h) return bad_handle();
-    return h->engine->chunk_host(data, len, out, cap);
+    return h->engine->host().chunk_host(data, len, out, cap);
 }
 
 size_t cdc_estimate_chunk_count(const cdc_handle_t *h, size_t len) {
@@ -136,7 +137,7 @@ int cdc_debug_read_bw(cdc_handle_t *h, const uint8_t *d_buf, size_t len, int rep
 
 int64_t cdc_debug_host_placement(cdc_handle_t *h, char *buf, size_t cap) {
     if (!h || (cap && !buf)) return bad_handle();
-    return h->engine->host_placement_json(buf, cap);
+    return h->engine->host().host_placement_json(buf, cap);
 }
 
 int cdc_last_timing(const cdc_handle_t *h, cdc_timing_t *t, size_t t_size) {
@@ -155,7 +156,7 @@ int64_t cdc_fs_write(cdc_handle_t *h, const uint8_t *data, size_t len,
         return CDC_EINVAL;
     }
     std::vector<uint64_t> spans;
-    const int64_t n = h->engine->fs_write(data, len, seg_size, spans, chunk_seconds);
+    const int64_t n = h->engine->host().fs_write(data, len, seg_size, spans, chunk_seconds);
     if (n < 0) return n;
     for (size_t i = 0; i < spans.size() && i < cap; ++i) span_lengths[i] = spans[i];
     return n;
@@ -163,12 +164,12 @@ int64_t cdc_fs_write(cdc_handle_t *h, const uint8_t *data, size_t len,
 
 int cdc_write_begin(cdc_handle_t *h) {
     if (!h) return (int)bad_handle();
-    return h->engine->write_begin();
+    return h->engine->host().write_begin();
 }
 
 int cdc_write_segment(cdc_handle_t *h, const uint8_t *data, size_t len) {
     if (!h) return (int)bad_handle();
-    return h->engine->write_segment(data, len);
+    return h->engine->host().write_segment(data, len);
 }
 
 int64_t cdc_write_finish(cdc_handle_t *h, uint64_t *span_lengths, size_t cap, double *seconds) {
@@ -178,7 +179,7 @@ int64_t cdc_write_finish(cdc_handle_t *h, uint64_t *span_lengths, size_t cap, do
         return CDC_EINVAL;
     }
     std::vector<uint64_t> spans;
-    const int64_t n = h->engine->write_finish(spans, seconds);
+    const int64_t n = h->engine->host().write_finish(spans, seconds);
     if (n < 0) return n;
     for (size_t i = 0; i < spans.size() && i < cap; ++i) span_lengths[i] = spans[i];
     return n;
@@ -186,12 +187,12 @@ int64_t cdc_write_finish(cdc_handle_t *h, uint64_t *span_lengths, size_t cap, do
 
 int64_t cdc_write_drain(cdc_handle_t *h, uint64_t *span_lengths, size_t cap) {
     if (!h) return bad_handle();
-    return h->engine->write_drain(span_lengths, cap);
+    return h->engine->host().write_drain(span_lengths, cap);
 }
 
 int cdc_debug_host_stats(const cdc_handle_t *h, double *v, size_t n) {
     if (!h || (n && !v)) return (int)bad_handle();
-    return h->engine->host_stats(v, n);
+    return h->engine->host().host_stats(v, n);
 }
 
 int cdc_sha256_chunks_device(cdc_handle_t *h, const uint8_t *d_data,
@@ -230,7 +231,7 @@ int64_t cdc_chunk_and_hash(cdc_handle_t *h, const uint8_t *data, size_t len,
         cdc::set_error("cdc_chunk_and_hash: digests is NULL");
         return CDC_EINVAL;
     }
-    return h->engine->chunk_host(data, len, out, cap, digests);
+    return h->engine->host().chunk_host(data, len, out, cap, digests);
 }
 
 int cdc_fill_splitmix64_device(uint8_t *d_buf, size_t len, uint64_t seed, void *hip_stream) {

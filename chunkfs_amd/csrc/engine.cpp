@@ -1,8 +1,8 @@
 // engine.cpp -- the handle behind the C ABI: argument checks, dispatch of the
 // device batches to the handle's backend (FastEngine, WalkEngine or the
 // fixed-size launch below), the drain results held for cdc_batch_sync, the
-// hash calls (HashEngine) and the debug entries.  The host boundary is in
-// hostpath.cpp.
+// hash calls (HashEngine) and the debug entries.  The host boundary is the
+// handle's HostPath (host_path.hpp, hostpath.cpp).
 #include "engine.hpp"
 
 #include <algorithm>
@@ -12,6 +12,7 @@
 
 #include "fast_engine.hpp"
 #include "hash_engine.hpp"
+#include "host_path.hpp"
 #include "walk_engine.hpp"
 
 namespace cdc {
@@ -117,7 +118,16 @@ int Engine::init() {
     num_cus_ = prop.multiProcessorCount;
     HIP_TRY(hipStreamCreateWithFlags(&own_stream_, hipStreamNonBlocking));
     for (auto &ev : ev_) HIP_TRY(hipEventCreate(&ev));
+    host_.reset(new HostPath(*this));
     return HashEngine::create(num_cus_, hash_);
+}
+
+const HostPlacement &Engine::placement() {
+    if (!place_probed_) {
+        place_ = HostPlacement::probe(device_);
+        place_probed_ = true;
+    }
+    return place_;
 }
 
 Engine::~Engine() {
@@ -127,21 +137,9 @@ Engine::~Engine() {
     if (own_stream_) (void)hipStreamSynchronize(own_stream_);
     fast_.reset();
     hash_.reset();
+    host_.reset();  // (its work ran on own_stream_, synchronised above and destroyed below)
     (void)hipFree(fixed_.d_block);
     (void)hipHostFree(fixed_.h_block);
-    (void)hipFree(d_data_);
-    (void)hipFree(d_out_);
-    (void)hipFree(d_dig_);
-    if (copy_stream_) (void)hipStreamSynchronize(copy_stream_);
-    (void)hipHostFree(h_ring_);
-    (void)hipHostFree(h_ready_);
-    (void)hipHostFree(h_out_);
-    for (auto &w : ws_win_) (void)hipFree(w);
-    for (auto &e : ring_ev_)
-        if (e) (void)hipEventDestroy(e);
-    if (copy_done_) (void)hipEventDestroy(copy_done_);
-    if (ws_ev_) (void)hipEventDestroy(ws_ev_);
-    if (copy_stream_) (void)hipStreamDestroy(copy_stream_);
     for (auto &ev : ev_)
         if (ev) (void)hipEventDestroy(ev);
     if (own_stream_) (void)hipStreamDestroy(own_stream_);
@@ -156,7 +154,7 @@ int Engine::set_gear(const uint64_t *gear) {
         const int64_t r = drain_implicit();
         if (r < 0) return (int)r;
     }
-    if (wr_.active) {  // windows already chunked used the old table: a write never mixes two
+    if (host_->write_active()) {  // windows already chunked used the old table: a write never mixes two
         set_error("cdc_set_gear: a streaming write is in progress (cdc_write_finish it first)");
         return CDC_EINVAL;
     }
@@ -387,31 +385,7 @@ int64_t Engine::debug_copy(int what, void *out, size_t max_bytes) {
     return fast_->debug_copy(what, out, max_bytes);
 }
 
-// ---- write of one buffer, the hashers, device utilities ------------------------------
-
-int64_t Engine::fs_write(const uint8_t *data, size_t len, size_t seg_size, std::vector<uint64_t> &spans,
-                         double *seconds) {
-    spans.clear();
-    if (seg_size == 0) {
-        set_error("cdc_fs_write: seg_size must be > 0");
-        return CDC_EINVAL;
-    }
-    if (len && !data) {
-        set_error("cdc_fs_write: data is NULL");
-        return CDC_EINVAL;
-    }
-    // ChunkStorage::write (storage.rs:84-100): StorageWriter::write per
-    // seg_size slice, then flush -- through the streaming write path.
-    int rc = write_begin();
-    if (rc) return rc;  // (e.g. a streaming write in progress: left alone)
-    for (size_t off = 0; !rc && off < len; off += seg_size)
-        rc = write_segment(data + off, std::min(seg_size, len - off));
-    if (rc) {
-        wr_.active = false;
-        return rc;
-    }
-    return write_finish(spans, seconds);
-}
+// ---- the hashers, device utilities ----------------------------------------------------
 
 int Engine::sha256_device(const uint8_t *d_data, const cdc_chunk_t *d_chunks, size_t n,
                           uint8_t *d_digests, hipStream_t s) {
@@ -511,7 +485,7 @@ int Engine::set_rabin_poly(uint64_t P) {
         set_error("cdc_set_rabin_poly: polynomial degree must be 9..56");
         return CDC_EINVAL;
     }
-    if (wr_.active) {  // windows already chunked used the old polynomial: a write never mixes two
+    if (host_->write_active()) {  // windows already chunked used the old polynomial: a write never mixes two
         set_error("cdc_set_rabin_poly: a streaming write is in progress (cdc_write_finish it first)");
         return CDC_EINVAL;
     }

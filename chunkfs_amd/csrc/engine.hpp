@@ -6,9 +6,9 @@
 // (fast_engine.hpp), a segment-walk rule's (Rabin / Ultra / Leap / Seq / AE)
 // WalkEngine (walk_engine.hpp), or the fixed-size path, which is one launch
 // here -- keeps the result of a drain made on the caller's behalf, hands the
-// hash calls (SHA-256, BLAKE2sp) to its HashEngine (hash_engine.hpp) and owns
-// the host boundary (hostpath.cpp).  Not thread-safe (the reference serialises
-// through a Mutex, src/lib.rs:89-90).
+// hash calls (SHA-256, BLAKE2sp) to its HashEngine (hash_engine.hpp) and the
+// calls on host memory to its HostPath (host_path.hpp).  Not thread-safe (the
+// reference serialises through a Mutex, src/lib.rs:89-90).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,6 +22,7 @@ namespace cdc {
 
 class FastEngine;
 class HashEngine;
+class HostPath;
 class WalkEngine;
 struct WalkConfig;
 
@@ -40,26 +41,9 @@ class Engine {
                          Engine **out);
     ~Engine();
 
-    // chunk_data on a host buffer; with `digests` (32 B per chunk, cap
-    // entries) also the SHA-256 of every chunk (StorageWriter's hashing).
-    int64_t chunk_host(const uint8_t *data, size_t len, cdc_chunk_t *out, size_t cap,
-                       uint8_t *digests = nullptr);
-    // ChunkStorage::write of one whole write (storage.rs:78-103, 302-383):
-    // the span lengths of the StorageWriter loop over seg_size segments, run
-    // through the streaming write path below (hostpath.cpp).
-    int64_t fs_write(const uint8_t *data, size_t len, size_t seg_size, std::vector<uint64_t> &spans,
-                     double *seconds);
-    // Streaming write path (hostpath.cpp): one file write as a sequence of
-    // segments (write_from_stream, storage.rs:105-137); spans at finish.
-    int write_begin();
-    int write_segment(const uint8_t *data, size_t len);
-    int64_t write_finish(std::vector<uint64_t> &spans, double *seconds);
-    int64_t write_drain(uint64_t *out, size_t cap);
-    // Host-path statistics: calls, upload s, total s of chunk_host; chunking s
-    // and segments of the current / last streaming write; small-kernel calls
-    // and fallbacks; chunk_host's guard trips.
-    int host_stats(double *v, size_t n) const;
-    int64_t host_placement_json(char *out, size_t cap);
+    // The host boundary: cdc_chunk_data, cdc_chunk_and_hash, cdc_fs_write,
+    // cdc_write_* and the host-path debug entries are HostPath's.
+    HostPath &host() { return *host_; }
     // SHA-256 of chunks of one device-resident stream (Sha256Hasher::hash).
     int sha256_device(const uint8_t *d_data, const cdc_chunk_t *d_chunks, size_t n,
                       uint8_t *d_digests, hipStream_t s);
@@ -116,7 +100,8 @@ class Engine {
     static int create_handle(cdc_algo_t algo, WalkConfig &cfg, uint32_t min, uint32_t avg, uint32_t max, int device,
                              Engine **out);
     int init();
-    // skip_small: the small kernel already declined these bytes (chunk_host).
+    friend class HostPath;  // (what it uses: host_path.hpp)
+    // skip_small: the small kernel already declined these bytes (HostPath::chunk_host).
     int64_t batch_device(size_t n, const uint8_t *const *d_streams, const uint64_t *lens, cdc_chunk_t *d_out,
                          size_t out_cap, uint64_t *first, hipStream_t stream, bool async, bool skip_small = false);
     // "A batch is in flight", whichever backend took it.  drain() completes
@@ -136,12 +121,7 @@ class Engine {
     std::unique_ptr<FastEngine> fast_;
     std::unique_ptr<WalkEngine> walk_;
     std::unique_ptr<HashEngine> hash_;  // every handle's: the hashers' scratch and launch
-    // Host boundary (hostpath.cpp).
-    int ensure_ring();
-    int ensure_host_out(size_t chunks);
-    int ensure_device_data(size_t len);
-    int upload(const uint8_t *src, size_t len, uint8_t *dst, hipStream_t s, size_t piece);
-    int write_window(bool final);
+    std::unique_ptr<HostPath> host_;    // every handle's: the host boundary, allocated on first use
 
     cdc_algo_t algo_ = CDC_ALGO_FASTCDC;
     uint32_t min_ = 0, avg_ = 0, max_ = 0;
@@ -168,49 +148,11 @@ class Engine {
         uint64_t gen = 0;
     } fixed_;
 
-    // Host path (hostpath.cpp): pinned upload ring (slot k reused once its
-    // DMA event completes), host-mapped chunk output written by the kernels,
-    // a copy stream for the streaming writes and two device windows.
-    static constexpr uint32_t kRingSlots = 4;
-    static constexpr size_t kRingSlot = size_t(4) << 20;
-    static constexpr size_t kWriteWindow = size_t(256) << 20;
-    static constexpr size_t kRingDirect = size_t(16) << 20;  // chunk_data above this: pageable hipMemcpyAsync
-    void *h_ring_ = nullptr;
-    uint8_t *h_ring_dev_ = nullptr;  // the ring as the device addresses it (small-path kernel reads)
-    CopyPool *pool_ = nullptr;  // CopyPool::for_node(the device's node)
+    // Where pinned host memory and the copy helpers go: probed once, on first
+    // use, for every backend and the host path.
     HostPlacement place_;
     bool place_probed_ = false;
     const HostPlacement &placement();
-    hipEvent_t ring_ev_[kRingSlots] = {};
-    uint32_t ring_next_ = 0;
-    // Feed words of the small path's streamed input: kFeedPieces per ring
-    // slot (pinned, coherent), and their device address.
-    uint64_t *h_ready_ = nullptr, *h_ready_dev_ = nullptr;
-    hipStream_t copy_stream_ = nullptr;
-    hipEvent_t copy_done_ = nullptr, ws_ev_ = nullptr;
-    cdc_chunk_t *h_out_ = nullptr, *d_hout_ = nullptr;
-    size_t h_out_cap_ = 0;
-    uint8_t *ws_win_[2] = {nullptr, nullptr};
-    struct WriteState {
-        bool active = false, failed = false;
-        int cur = 0;
-        size_t drained = 0;  // spans already returned by cdc_write_drain
-        size_t reserve = 0, carry = 0, fill = 0;
-        uint64_t bytes = 0, segments = 0;
-        double t0 = 0, chunk_s = 0;
-        std::vector<uint64_t> spans;
-    } wr_;
-    struct HostStats {
-        uint64_t calls = 0;
-        uint64_t guard_trips = 0;  // chunk lists that did not tile their buffer at first read (chunk_host)
-        double upload_s = 0, total_s = 0;
-    } host_;
-    uint8_t *d_data_ = nullptr;
-    size_t d_data_bytes_ = 0;
-    cdc_chunk_t *d_out_ = nullptr;
-    size_t d_out_cap_ = 0;
-    uint8_t *d_dig_ = nullptr;               // [d_dig_cap_ * 32] digests (host path)
-    size_t d_dig_cap_ = 0;
 };
 
 }  // namespace cdc

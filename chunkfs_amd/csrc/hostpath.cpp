@@ -1,4 +1,7 @@
-// hostpath.cpp -- the host-memory boundary of the engine:
+// hostpath.cpp -- the host-memory boundary of a handle, in
+// three sections: HostPlacement (where pinned memory and the copy helpers go),
+// CopyPool (the pageable -> pinned copies) and HostPath (host_path.hpp), the
+// handle's object that uses both.  HostPath is
 // Chunker::chunk_data on a host buffer (reference src/lib.rs:80, called by
 // StorageWriter::write, src/system/storage.rs:302-357) and the write path of
 // one file (ChunkStorage::write / write_from_stream, storage.rs:78-137) as a
@@ -9,10 +12,14 @@
 //                copy of piece k+1 runs while piece k's DMA is in flight
 //   chunk_host   upload + the device pipeline; the chunk list is written by
 //                the kernels straight into host-mapped pinned memory (no D2H
-//                copy, no extra sync)
+//                copy) and read through chunk_to_host, the one reader that
+//                waits for the stream and checks that the list tiles its bytes
+//                (the one-launch small kernel waits for its done word instead,
+//                and runs the same check)
 //   write_*      StorageWriter over a stream of segments: bytes accumulate in
 //                a device window (double-buffered) while later segments
-//                upload; a full window is chunked on the device, every chunk
+//                upload; a full window is chunked on the device (chunk_to_host
+//                again: a stale last chunk would be a wrong carry), every chunk
 //                but the last becomes a span and the last one is carried into
 //                the next window in HBM (the reference's `rest`, storage.rs:
 //                309-322); finish = flush (storage.rs:360-383).
@@ -36,6 +43,7 @@
 
 #include "engine.hpp"
 #include "fast_engine.hpp"
+#include "host_path.hpp"
 
 #include <atomic>
 
@@ -274,19 +282,24 @@ void CopyPool::copy_feed(void *dst, const void *src, size_t n, size_t piece, vol
     job(dst, src, n, piece, ready, seq);
 }
 
-// ---- host boundary --------------------------------------------------------------
+// ---- HostPath: resources ----------------------------------------------------------
 
-const HostPlacement &Engine::placement() {
-    if (!place_probed_) {
-        place_ = HostPlacement::probe(device_);
-        place_probed_ = true;
-    }
-    return place_;
+HostPath::~HostPath() {
+    (void)hipSetDevice(eng_.device_);
+    if (copy_stream_) (void)hipStreamSynchronize(copy_stream_);  // uploads still reading the ring
+    (void)hipHostFree(h_ring_);
+    (void)hipHostFree(h_ready_);
+    (void)hipHostFree(h_out_);
+    for (auto &e : ring_ev_)
+        if (e) (void)hipEventDestroy(e);
+    if (copy_done_) (void)hipEventDestroy(copy_done_);
+    if (ws_ev_) (void)hipEventDestroy(ws_ev_);
+    if (copy_stream_) (void)hipStreamDestroy(copy_stream_);
 }
 
-int Engine::ensure_ring() {
+int HostPath::ensure_ring() {
     if (h_ring_) return CDC_OK;
-    const HostPlacement &pl = placement();
+    const HostPlacement &pl = eng_.placement();
     if (!pool_) pool_ = &CopyPool::for_node(pl.enabled ? pl.node : -1, pl.cpus);
     // Coherent (fine-grained): the small kernel reads a slot while the host is
     // still filling it (streamed input), so the device must never cache it.
@@ -302,57 +315,101 @@ int Engine::ensure_ring() {
     return CDC_OK;
 }
 
-int Engine::ensure_host_out(size_t chunks) {
+int HostPath::ensure_host_out(size_t chunks) {
     if (h_out_ && h_out_cap_ >= chunks) return CDC_OK;
     (void)hipHostFree(h_out_);
     h_out_ = nullptr;
     d_hout_ = nullptr;
     h_out_cap_ = 0;
     const size_t want = round_up(chunks + chunks / 8 + 64, 4096);
-    // Coherent: the host reads the chunk list as soon as the kernel's done
-    // word says so, with no stream synchronisation in between; in plain mapped
-    // memory the device's writes did not always reach lines the CPU had read
-    // in the previous call (9 of 27k calls returned a stale last chunk,
+    // Coherent: the small path reads the chunk list as soon as the kernel's
+    // done word says so, with no stream synchronisation in between; in plain
+    // mapped memory the device's writes did not always reach lines the CPU had
+    // read in the previous call (9 of 27k calls returned a stale last chunk,
     // tools/tails_repro.py).
 #ifndef CDC_HOUT_COHERENT
 #define CDC_HOUT_COHERENT 1
 #endif
-    HIP_TRY(placement().host_malloc(reinterpret_cast<void **>(&h_out_), want * sizeof(cdc_chunk_t),
-                                    hipHostMallocMapped | (CDC_HOUT_COHERENT ? hipHostMallocCoherent : 0u)));
+    HIP_TRY(eng_.placement().host_malloc(reinterpret_cast<void **>(&h_out_), want * sizeof(cdc_chunk_t),
+                                         hipHostMallocMapped | (CDC_HOUT_COHERENT ? hipHostMallocCoherent : 0u)));
     HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&d_hout_), h_out_, 0));
     h_out_cap_ = want;
     return CDC_OK;
 }
 
-int Engine::ensure_device_data(size_t len) {
-    if (d_data_bytes_ >= len) return CDC_OK;
-    (void)hipFree(d_data_);
-    d_data_ = nullptr;
-    d_data_bytes_ = 0;
-    const size_t want = round_up(len + len / 8, size_t(1) << 20);
-    HIP_TRY(hipMalloc(&d_data_, want));
-    d_data_bytes_ = want;
+int HostPath::ensure_device_data(size_t len) {
+    if (d_data_.cap >= len) return CDC_OK;
+    HIP_TRY(d_data_.room(round_up(len + len / 8, size_t(1) << 20)));
+    return CDC_OK;
+}
+
+int HostPath::claim_slot(uint32_t &k) {
+    k = ring_next_;
+    ring_next_ = (ring_next_ + 1) % kRingSlots;
+    HIP_TRY(hipEventSynchronize(ring_ev_[k]));  // (an event never recorded is complete)
     return CDC_OK;
 }
 
 // Pageable host bytes -> pinned ring slot -> async H2D (stream s).  Pieces of
 // `piece` bytes (<= kRingSlot); a slot is reused once its previous DMA is done.
-int Engine::upload(const uint8_t *src, size_t len, uint8_t *dst, hipStream_t s, size_t piece) {
+int HostPath::upload(const uint8_t *src, size_t len, uint8_t *dst, hipStream_t s, size_t piece) {
     for (size_t off = 0; off < len;) {
         const size_t n = std::min(piece, len - off);
-        const uint32_t k = ring_next_;
-        ring_next_ = (ring_next_ + 1) % kRingSlots;
-        HIP_TRY(hipEventSynchronize(ring_ev_[k]));  // (an event never recorded is complete)
-        uint8_t *slot = static_cast<uint8_t *>(h_ring_) + (size_t)k * kRingSlot;
-        pool_->copy(slot, src + off, n);
-        HIP_TRY(hipMemcpyAsync(dst + off, slot, n, hipMemcpyHostToDevice, s));
+        uint32_t k;
+        const int rc = claim_slot(k);
+        if (rc) return rc;
+        pool_->copy(slot(k), src + off, n);
+        HIP_TRY(hipMemcpyAsync(dst + off, slot(k), n, hipMemcpyHostToDevice, s));
         HIP_TRY(hipEventRecord(ring_ev_[k], s));
         off += n;
     }
     return CDC_OK;
 }
 
-int64_t Engine::chunk_host(const uint8_t *data, size_t len, cdc_chunk_t *out, size_t cap, uint8_t *digests) {
+// ---- HostPath: the host-mapped chunk list -------------------------------------------
+
+// A chunk list tiles its buffer: offsets contiguous from 0, lengths summing to len.
+bool HostPath::tiles(int64_t count, uint64_t len) const {
+    const volatile cdc_chunk_t *c = h_out_;  // (the device writes it: read afresh each time)
+    uint64_t at = 0;
+    for (int64_t i = 0; i < count; ++i) {
+        if (c[i].offset != at) return false;
+        at += c[i].length;
+    }
+    return at == len;
+}
+
+// Host guard of every read of h_out_: a list that does not tile its buffer is
+// read again after a stream sync (counted: cdc_debug_host_stats' last slot,
+// which the suite asserts stays 0), and refused if it is still wrong.
+int HostPath::check_list(int64_t count, size_t len, const char *who) {
+    if (tiles(count, len)) return CDC_OK;
+    host_.guard_trips += 1;
+    HIP_TRY(hipStreamSynchronize(eng_.own_stream_));
+    if (tiles(count, len)) return CDC_OK;
+    set_error(std::string(who) + ": the chunk list does not tile the buffer (internal error)");
+    return CDC_EDEVICE;
+}
+
+int64_t HostPath::chunk_to_host(const uint8_t *d_buf, size_t len, bool skip_small, const char *who) {
+    const size_t need = eng_.max_chunks(len);
+    const int rc = ensure_host_out(need);
+    if (rc) return rc;
+    const uint64_t l = len;
+    uint64_t first[2] = {0, 0};
+    const int64_t count = eng_.batch_device(1, &d_buf, &l, d_hout_, need, first, eng_.own_stream_, false, skip_small);
+    if (count < 0) return count;
+    // The done word a FastCDC collection spins on says the resolve's last
+    // block is through; the list is read only once the stream itself has
+    // retired (a stale last chunk otherwise: DESIGN.md "Host-visible results").
+    HIP_TRY(hipStreamSynchronize(eng_.own_stream_));
+    const int bad = check_list(count, len, who);
+    return bad ? bad : count;
+}
+
+// ---- HostPath: cdc_chunk_data ---------------------------------------------------------
+
+int64_t HostPath::chunk_host(const uint8_t *data, size_t len, cdc_chunk_t *out, size_t cap, uint8_t *digests) {
     if (len && !data) {
         set_error("cdc_chunk_data: data is NULL");
         return CDC_EINVAL;
@@ -362,17 +419,19 @@ int64_t Engine::chunk_host(const uint8_t *data, size_t len, cdc_chunk_t *out, si
         return CDC_EINVAL;
     }
     if (len == 0) return 0;  // FastCDC iterator yields nothing; FSChunker loop never runs
-    HIP_TRY(hipSetDevice(device_));
-    if (in_flight()) {  // async batches first: the small path reuses host staging block 0
-        const int64_t r = drain_implicit();
+    HIP_TRY(hipSetDevice(eng_.device_));
+    if (eng_.in_flight()) {  // async batches first: the small path reuses host staging block 0
+        const int64_t r = eng_.drain_implicit();
         if (r < 0) return r;
     }
     const double t0 = now_s();
     int rc = ensure_ring();
     if (!rc) rc = ensure_device_data(len);
-    const size_t need = max_chunks(len);
+    const size_t need = eng_.max_chunks(len);
     if (!rc) rc = ensure_host_out(need);
     if (rc) return rc;
+    FastEngine *fast = eng_.fast_.get();
+    hipStream_t own = eng_.own_stream_;
     int64_t count = -1;
     double t1 = t0;
     bool small_tried = false;
@@ -381,102 +440,60 @@ int64_t Engine::chunk_host(const uint8_t *data, size_t len, cdc_chunk_t *out, si
     // reads the bytes over PCIe from a pinned ring slot that this thread fills
     // meanwhile, 128 KiB at a time, each piece announced by a feed word -- the
     // copy overlaps the launch and the reads; no DMA, no second kernel on the
-    // call's critical path (small.hip).  A call the kernel's budgets cannot
-    // take falls through to the regular upload + pipeline.
-    if (fast_ && fast_->small_zero_copy() && !digests && fast_->small_ok(len) && len <= kRingSlot) {
-        const uint32_t k = ring_next_;
-        ring_next_ = (ring_next_ + 1) % kRingSlots;
-        HIP_TRY(hipEventSynchronize(ring_ev_[k]));
-        uint8_t *slot = static_cast<uint8_t *>(h_ring_) + (size_t)k * kRingSlot;
-        uint64_t first[2] = {0, 0};
-        if (fast_->small_feed()) {
-            const FastEngine::SmallFeed feed{data, slot, h_ready_ + (size_t)k * small::kFeedPieces,
-                                             h_ready_dev_ + (size_t)k * small::kFeedPieces, pool_};
-            rc = fast_->run_small(h_ring_dev_ + (size_t)k * kRingSlot, len, d_hout_, need, first, own_stream_,
-                                  placement(), true, &feed);
-            t1 = t0 + fast_->small_copy_s();
-        } else {  // (A/B: the whole copy, then the launch)
-            pool_->copy(slot, data, len);
-            t1 = now_s();
-            rc = fast_->run_small(h_ring_dev_ + (size_t)k * kRingSlot, len, d_hout_, need, first, own_stream_,
-                                  placement(), true);
-        }
-        HIP_TRY(hipEventRecord(ring_ev_[k], own_stream_));  // the slot is free once the kernel retires
-        if (rc < 0) return rc;
-        if (rc == CDC_OK) count = (int64_t)first[1];
-        small_tried = true;
-    }
-    // Small calls (the reference's 1 MiB segments) go through the pinned ring
-    // in 256 KiB pieces, so that the CPU copy of one piece overlaps the DMA of
-    // the previous one; large buffers take HIP's own pageable path, which
-    // stages with several threads (measured 51 vs 31 GiB/s for the single-
-    // thread ring on 1 GiB).
-    if (count >= 0) {
-        // (chunked by the small kernel from the ring slot)
-    } else if (len <= kRingDirect) {
-        // (4 MiB pieces, each copied by the pool and moved by one DMA: one
-        // 1 MiB call is one hand-off and one hipMemcpyAsync)
-        rc = upload(data, len, d_data_, own_stream_, kRingSlot);
+    // call's critical path (small.hip).  It waits for the kernel's done word
+    // only.  A call the kernel's budgets cannot take falls through to the
+    // regular upload + pipeline.
+    if (fast && fast->small_zero_copy() && !digests && fast->small_ok(len) && len <= kRingSlot) {
+        uint32_t k;
+        rc = claim_slot(k);
         if (rc) return rc;
-    } else {
-        HIP_TRY(hipMemcpyAsync(d_data_, data, len, hipMemcpyHostToDevice, own_stream_));
+        uint64_t first[2] = {0, 0};
+        if (fast->small_feed()) {
+            const FastEngine::SmallFeed feed{data, slot(k), h_ready_ + (size_t)k * small::kFeedPieces,
+                                             h_ready_dev_ + (size_t)k * small::kFeedPieces, pool_};
+            rc = fast->run_small(h_ring_dev_ + (size_t)k * kRingSlot, len, d_hout_, need, first, own,
+                                 eng_.placement(), true, &feed);
+            t1 = t0 + fast->small_copy_s();
+        } else {  // (A/B: the whole copy, then the launch)
+            pool_->copy(slot(k), data, len);
+            t1 = now_s();
+            rc = fast->run_small(h_ring_dev_ + (size_t)k * kRingSlot, len, d_hout_, need, first, own,
+                                 eng_.placement(), true);
+        }
+        HIP_TRY(hipEventRecord(ring_ev_[k], own));  // the slot is free once the kernel retires
+        if (rc < 0) return rc;
+        small_tried = true;
+        if (rc == CDC_OK) {
+            count = (int64_t)first[1];
+            rc = check_list(count, len, "cdc_chunk_data");
+            if (rc) return rc;
+        }
     }
     if (count < 0) {
+        // Small calls (the reference's 1 MiB segments) go through the pinned
+        // ring in 4 MiB pieces, each copied by the pool and moved by one DMA
+        // (one 1 MiB call is one hand-off and one hipMemcpyAsync), so that the
+        // CPU copy of one piece overlaps the DMA of the previous one; large
+        // buffers take HIP's own pageable path, which stages with several
+        // threads (measured 51 vs 31 GiB/s for the single-thread ring on 1 GiB).
+        if (len <= kRingDirect) {
+            rc = upload(data, len, d_data_, own, kRingSlot);
+            if (rc) return rc;
+        } else {
+            HIP_TRY(hipMemcpyAsync(d_data_, data, len, hipMemcpyHostToDevice, own));
+        }
         t1 = now_s();
-        const uint8_t *p = d_data_;
-        const uint64_t l = len;
-        uint64_t first[2] = {0, 0};
-        // (small_tried: the small kernel already declined these bytes)
-        count = batch_device(1, &p, &l, reinterpret_cast<cdc_chunk_t *>(d_hout_), need, first, own_stream_, false,
-                             small_tried);
+        count = chunk_to_host(d_data_, len, small_tried, "cdc_chunk_data");
         if (count < 0) return count;
-        // The done word the collection spins on says the resolve's last block
-        // is through; the list is read only once the stream itself has retired
-        // (calls above 4 MiB by default, every call with the small kernel off).
-        HIP_TRY(hipStreamSynchronize(own_stream_));
-    }
-    // Host guard, both branches: a chunk list tiles the call's bytes -- offsets
-    // contiguous from 0, lengths summing to len.  A list that does not is read
-    // again after a stream sync (counted: cdc_debug_host_stats' last slot, which
-    // the suite asserts stays 0), and refused if it is still wrong.
-    auto tiles = [&]() {
-        const volatile cdc_chunk_t *c = h_out_;  // (the device writes it: read afresh each time)
-        uint64_t at = 0;
-        for (int64_t i = 0; i < count; ++i) {
-            if (c[i].offset != at) return false;
-            at += c[i].length;
-        }
-        return at == (uint64_t)len;
-    };
-    if (!tiles()) {
-        host_.guard_trips += 1;
-        HIP_TRY(hipStreamSynchronize(own_stream_));
-        if (!tiles()) {
-            set_error("cdc_chunk_data: the chunk list does not tile the buffer (internal error)");
-            return CDC_EDEVICE;
-        }
     }
     const size_t copy = (size_t)count < cap ? (size_t)count : cap;
     if (digests && copy) {
-        if (d_out_cap_ < (size_t)count) {  // the SHA-256 kernel reads the chunk list from HBM
-            (void)hipFree(d_out_);
-            d_out_ = nullptr;
-            d_out_cap_ = 0;
-            const size_t want = (size_t)count + (size_t)count / 8 + 64;
-            HIP_TRY(hipMalloc(&d_out_, want * sizeof(cdc_chunk_t)));
-            d_out_cap_ = want;
-        }
-        if (d_dig_cap_ < (size_t)count) {
-            (void)hipFree(d_dig_);
-            d_dig_ = nullptr;
-            d_dig_cap_ = 0;
-            const size_t want = (size_t)count + (size_t)count / 8 + 64;
-            HIP_TRY(hipMalloc(&d_dig_, want * 32));
-            d_dig_cap_ = want;
-        }
-        HIP_TRY(hipMemcpyAsync(d_out_, h_out_, (size_t)count * sizeof(cdc_chunk_t), hipMemcpyHostToDevice,
-                               own_stream_));
-        rc = sha256_device(d_data_, d_out_, (size_t)count, d_dig_, own_stream_);
+        // (the SHA-256 kernel reads the chunk list from HBM)
+        const size_t want = (size_t)count + (size_t)count / 8 + 64;
+        if (d_out_.cap < (size_t)count) HIP_TRY(d_out_.room(want));
+        if (d_dig_.cap < (size_t)count * 32) HIP_TRY(d_dig_.room(want * 32));
+        HIP_TRY(hipMemcpyAsync(d_out_, h_out_, (size_t)count * sizeof(cdc_chunk_t), hipMemcpyHostToDevice, own));
+        rc = eng_.sha256_device(d_data_, d_out_, (size_t)count, d_dig_, own);
         if (rc) return rc;
         HIP_TRY(hipMemcpy(digests, d_dig_, copy * 32, hipMemcpyDeviceToHost));
     }
@@ -487,10 +504,10 @@ int64_t Engine::chunk_host(const uint8_t *data, size_t len, cdc_chunk_t *out, si
     return count;
 }
 
-// ---- streaming write path ---------------------------------------------------
+// ---- HostPath: streaming write path -------------------------------------------------
 
-int Engine::write_begin() {
-    HIP_TRY(hipSetDevice(device_));
+int HostPath::write_begin() {
+    HIP_TRY(hipSetDevice(eng_.device_));
     if (wr_.active) {  // (never silently drop a write in progress)
         set_error("cdc_write_begin: a write is already in progress on this handle (cdc_write_finish ends it)");
         return CDC_EINVAL;
@@ -499,11 +516,9 @@ int Engine::write_begin() {
     if (rc) return rc;
     // A window holds the carried chunk (<= max bytes) at offset 0, then the
     // new bytes: its start stays 16-byte aligned for the scan's vector loads.
-    const size_t reserve = round_up(std::max(max_, min_) + 16, 256);  // FSChunker: max_ = 0
-    if (!ws_win_[0]) {
-        for (auto &w : ws_win_) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w), reserve + kWriteWindow + 64));
-        HIP_TRY(hipEventCreateWithFlags(&ws_ev_, hipEventDisableTiming));
-    }
+    const size_t reserve = round_up(std::max(eng_.max_, eng_.min_) + 16, 256);  // FSChunker: max_ = 0
+    for (auto &w : ws_win_) HIP_TRY(w.room(reserve + kWriteWindow + 64));
+    if (!ws_ev_) HIP_TRY(hipEventCreateWithFlags(&ws_ev_, hipEventDisableTiming));
     wr_ = WriteState{};
     wr_.reserve = reserve;
     wr_.active = true;
@@ -513,23 +528,16 @@ int Engine::write_begin() {
 
 // Chunk the current window [0, carry + fill) on the device;
 // all chunks but the last (all of them at the end of the write) are spans.
-int Engine::write_window(bool final) {
+int HostPath::write_window(bool final, const char *who) {
     WriteState &W = wr_;
     const size_t n = W.carry + W.fill;
     if (n == 0) return CDC_OK;
     uint8_t *base = ws_win_[W.cur];
     // The window's uploads ran on the copy stream: the chunking waits for them.
     HIP_TRY(hipEventRecord(copy_done_, copy_stream_));
-    HIP_TRY(hipStreamWaitEvent(own_stream_, copy_done_, 0));
-    const size_t need = max_chunks(n);
-    int rc = ensure_host_out(need);
-    if (rc) return rc;
-    const uint8_t *p = base;
-    const uint64_t l = n;
-    uint64_t first[2] = {0, 0};
+    HIP_TRY(hipStreamWaitEvent(eng_.own_stream_, copy_done_, 0));
     const double tc = now_s();
-    const int64_t c = chunk_batch_device(1, &p, &l, reinterpret_cast<cdc_chunk_t *>(d_hout_), need, first,
-                                         own_stream_);
+    const int64_t c = chunk_to_host(base, n, false, who);
     if (c < 0) return (int)c;
     W.chunk_s += now_s() - tc;
     const cdc_chunk_t *ch = h_out_;
@@ -540,10 +548,10 @@ int Engine::write_window(bool final) {
         // front of the other window (it is <= max bytes: the reserve).
         const size_t r = (size_t)ch[c - 1].length;
         uint8_t *dst = ws_win_[1 - W.cur];
-        HIP_TRY(hipMemcpyAsync(dst, base + ch[c - 1].offset, r, hipMemcpyDeviceToDevice, own_stream_));
+        HIP_TRY(hipMemcpyAsync(dst, base + ch[c - 1].offset, r, hipMemcpyDeviceToDevice, eng_.own_stream_));
         // new uploads into that window wait for the carry copy (same region's
         // neighbourhood; cheap)
-        HIP_TRY(hipEventRecord(ws_ev_, own_stream_));
+        HIP_TRY(hipEventRecord(ws_ev_, eng_.own_stream_));
         HIP_TRY(hipStreamWaitEvent(copy_stream_, ws_ev_, 0));
         W.carry = r;
     } else {
@@ -554,7 +562,7 @@ int Engine::write_window(bool final) {
     return CDC_OK;
 }
 
-int Engine::write_segment(const uint8_t *data, size_t len) {
+int HostPath::write_segment(const uint8_t *data, size_t len) {
     if (!wr_.active) {
         set_error("cdc_write_segment: no write in progress (cdc_write_begin)");
         return CDC_EINVAL;
@@ -569,7 +577,7 @@ int Engine::write_segment(const uint8_t *data, size_t len) {
     }
     // Any failure past this point leaves the window state unknown: the write
     // is marked failed and cdc_write_finish reports an error, never spans.
-    if (hipSetDevice(device_) != hipSuccess) {
+    if (hipSetDevice(eng_.device_) != hipSuccess) {
         wr_.failed = true;
         set_error("cdc_write_segment: hipSetDevice failed");
         return CDC_EDEVICE;
@@ -577,7 +585,7 @@ int Engine::write_segment(const uint8_t *data, size_t len) {
     WriteState &W = wr_;
     while (len) {
         if (W.fill == kWriteWindow) {
-            const int rc = write_window(false);
+            const int rc = write_window(false, "cdc_write_segment");
             if (rc) {
                 W.failed = true;
                 return rc;
@@ -599,8 +607,8 @@ int Engine::write_segment(const uint8_t *data, size_t len) {
     // ends: every segment is chunked as its own buffer, like the reference's
     // loop, instead of a 256 MiB window at a time.  (A segment larger than the
     // window counts as several.)
-    if (algo_ == CDC_ALGO_AE && W.fill) {
-        const int rc = write_window(false);
+    if (eng_.algo_ == CDC_ALGO_AE && W.fill) {
+        const int rc = write_window(false, "cdc_write_segment");
         if (rc) {
             W.failed = true;
             return rc;
@@ -610,7 +618,7 @@ int Engine::write_segment(const uint8_t *data, size_t len) {
     return CDC_OK;
 }
 
-int64_t Engine::write_finish(std::vector<uint64_t> &spans, double *seconds) {
+int64_t HostPath::write_finish(std::vector<uint64_t> &spans, double *seconds) {
     if (!wr_.active) {
         set_error("cdc_write_finish: no write in progress (cdc_write_begin)");
         return CDC_EINVAL;
@@ -620,8 +628,8 @@ int64_t Engine::write_finish(std::vector<uint64_t> &spans, double *seconds) {
         set_error("cdc_write_finish: a cdc_write_segment of this write failed; its spans are unknown");
         return CDC_EDEVICE;
     }
-    HIP_TRY(hipSetDevice(device_));
-    const int rc = write_window(true);  // StorageWriter::flush: the rest is the last span
+    HIP_TRY(hipSetDevice(eng_.device_));
+    const int rc = write_window(true, "cdc_write_finish");  // StorageWriter::flush: the rest is the last span
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(copy_stream_));
     spans.assign(wr_.spans.begin() + (ptrdiff_t)wr_.drained, wr_.spans.end());
@@ -632,7 +640,7 @@ int64_t Engine::write_finish(std::vector<uint64_t> &spans, double *seconds) {
 // Spans final so far (file order), oldest first, that no drain has returned:
 // every chunk of a chunked device window but its last.  The caller may
 // release the bytes those spans cover.
-int64_t Engine::write_drain(uint64_t *out, size_t cap) {
+int64_t HostPath::write_drain(uint64_t *out, size_t cap) {
     if (!wr_.active) {
         set_error("cdc_write_drain: no write in progress (cdc_write_begin)");
         return CDC_EINVAL;
@@ -647,12 +655,38 @@ int64_t Engine::write_drain(uint64_t *out, size_t cap) {
     return (int64_t)k;
 }
 
+int64_t HostPath::fs_write(const uint8_t *data, size_t len, size_t seg_size, std::vector<uint64_t> &spans,
+                           double *seconds) {
+    spans.clear();
+    if (seg_size == 0) {
+        set_error("cdc_fs_write: seg_size must be > 0");
+        return CDC_EINVAL;
+    }
+    if (len && !data) {
+        set_error("cdc_fs_write: data is NULL");
+        return CDC_EINVAL;
+    }
+    // ChunkStorage::write (storage.rs:84-100): StorageWriter::write per
+    // seg_size slice, then flush.
+    int rc = write_begin();
+    if (rc) return rc;  // (e.g. a streaming write in progress: left alone)
+    for (size_t off = 0; !rc && off < len; off += seg_size)
+        rc = write_segment(data + off, std::min(seg_size, len - off));
+    if (rc) {
+        wr_.active = false;
+        return rc;
+    }
+    return write_finish(spans, seconds);
+}
+
+// ---- HostPath: debug entries ----------------------------------------------------------
+
 // JSON: the device's PCI address, NUMA node and link, where the pinned ring
 // landed and how the copy helpers were placed (bench.py host_path.numa).
-int64_t Engine::host_placement_json(char *out, size_t cap) {
+int64_t HostPath::host_placement_json(char *out, size_t cap) {
     int rc = ensure_ring();
     if (rc) return rc;
-    const HostPlacement &p = placement();
+    const HostPlacement &p = eng_.placement();
     std::ostringstream o;
     o << "{\"pci\": \"" << p.pci << "\", \"gpu_node\": " << p.node << ", \"link\": \"" << p.link
       << "\", \"link_max\": \"" << p.link_max << "\", \"numa_placement\": " << (p.enabled ? "true" : "false")
@@ -669,12 +703,14 @@ int64_t Engine::host_placement_json(char *out, size_t cap) {
     return (int64_t)s.size();
 }
 
-int Engine::host_stats(double *v, size_t n) const {
+int HostPath::host_stats(double *v, size_t n) const {
+    const FastEngine *fast = eng_.fast_.get();
     const double s[8] = {(double)host_.calls, host_.upload_s, host_.total_s, wr_.chunk_s, (double)wr_.segments,
-                         fast_ ? (double)fast_->small_calls() : 0.0, fast_ ? (double)fast_->small_fallbacks() : 0.0,
+                         fast ? (double)fast->small_calls() : 0.0, fast ? (double)fast->small_fallbacks() : 0.0,
                          (double)host_.guard_trips};
     for (size_t i = 0; i < n && i < 8; ++i) v[i] = s[i];
     return CDC_OK;
 }
 
 }  // namespace cdc
+

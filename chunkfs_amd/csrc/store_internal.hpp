@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/chunkfs_amd.h"
+#include "host_common.hpp"
 #include "store.hpp"
 
 namespace cdc {
@@ -88,56 +89,6 @@ struct DeviceScratch {
         return e;
     }
 };
-
-// Memory an object keeps between calls: `cap` elements of T on the device, or
-// pinned on the host, freed with its owner (with the owner's device current).
-// room() leaves a buffer that is large enough alone; otherwise it frees it and
-// allocates exactly `count` elements, the contents are not kept.  How much to
-// ask for is the caller's rule.  After a failure the buffer is empty.
-template <typename T, bool kPinned>
-struct Owned {
-    T *p = nullptr;
-    uint64_t cap = 0;
-    Owned() = default;
-    Owned(Owned &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }  // move-only: no copies
-    ~Owned() { drop(); }
-    void drop() {
-        if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
-        p = nullptr, cap = 0;
-    }
-    hipError_t room(uint64_t count) {
-        if (cap >= count) return hipSuccess;
-        drop();
-        void *q = nullptr;
-        const hipError_t e = kPinned ? hipHostMalloc(&q, count * sizeof(T)) : hipMalloc(&q, count * sizeof(T));
-        if (e == hipSuccess) p = static_cast<T *>(q), cap = count;
-        return e;
-    }
-    operator T *() const { return p; }
-    T *operator->() const { return p; }
-};
-template <typename T>
-using DeviceBuf = Owned<T, false>;
-template <typename T>
-using PinnedBuf = Owned<T, true>;
-
-// Buffers that grow together, `cap` what the group holds: nothing to do while
-// cap >= n; else room(count) for each {buffer, count} pair up to the first
-// failure, and cap = to -- or 0 after a failure: the next call allocates again.
-inline hipError_t room_all() { return hipSuccess; }
-template <typename B, typename... R>
-hipError_t room_all(B &buf, uint64_t count, R &&...rest) {
-    const hipError_t e = buf.room(count);
-    return e == hipSuccess ? room_all(rest...) : e;
-}
-template <typename... A>
-hipError_t grow_group(uint64_t &cap, uint64_t n, uint64_t to, A &&...pairs) {
-    if (cap >= n) return hipSuccess;
-    cap = 0;
-    const hipError_t e = room_all(pairs...);
-    if (e == hipSuccess) cap = to;
-    return e;
-}
 
 // Per-item scratch and the two arrays of the scan over it.
 template <typename T>

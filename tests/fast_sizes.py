@@ -163,9 +163,9 @@ def small_eligible(p, n):
 
 
 def write_window_bytes():
-    """Engine::kWriteWindow (engine.hpp): the bytes the streaming write path
+    """HostPath::kWriteWindow (host_path.hpp): the bytes the streaming write path
     chunks at a time; the last chunk of a window is carried into the next."""
-    txt = open(os.path.join(oracle.ROOT, "chunkfs_amd", "csrc", "engine.hpp")).read()
+    txt = open(os.path.join(oracle.ROOT, "chunkfs_amd", "csrc", "host_path.hpp")).read()
     m = re.search(r"kWriteWindow = size_t\((\d+)\) << (\d+);", txt)
     return int(m.group(1)) << int(m.group(2))
 

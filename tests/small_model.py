@@ -475,8 +475,8 @@ def scan_input(sizes, name):
 
 
 def ring_slots():
-    """Engine::kRingSlots (engine.hpp): the pinned slots cdc_chunk_data rotates through."""
-    txt = open(os.path.join(oracle.ROOT, "chunkfs_amd", "csrc", "engine.hpp")).read()
+    """HostPath::kRingSlots (host_path.hpp): the pinned slots cdc_chunk_data rotates through."""
+    txt = open(os.path.join(oracle.ROOT, "chunkfs_amd", "csrc", "host_path.hpp")).read()
     return int(re.search(r"kRingSlots = (\d+);", txt).group(1))
 
 

@@ -1,7 +1,8 @@
 """The seams between the handle (Engine) and its backends (-m gpu): the
 fixed-size path on its own buffers, cdc_last_timing across backends, the
-hashers' scratch (HashEngine) across hashers and regrowth, and the small
-kernel's hand-over to the pipeline.  Every chunk list, every first[] and every
+hashers' scratch (HashEngine) across hashers and regrowth, the small
+kernel's hand-over to the pipeline, and the host path (HostPath) on its own
+buffers.  Every chunk list, every first[] and every
 digest is compared bit for bit with the CPU oracle (no tolerances).
 """
 import hashlib
@@ -254,4 +255,51 @@ def test_small_kernel_hand_over():
             print(f"rep {rep} {name}: small calls, fallbacks, guard trips {got}")
             assert got == (calls, fallbacks, 0), (rep, name)
     assert calls == 16
+    ch.close()
+
+
+# ---- 4. the host path on its own buffers --------------------------------------------
+
+@pytest.mark.parametrize("sizes", [FAST, (64, 256, 1024)])
+def test_host_path_on_its_own_buffers(sizes):
+    """HostPath's buffers on one handle, every call in this order: a 64 KiB
+    cdc_chunk_data that sizes everything small; a write of 5 MiB + 1 byte in
+    1 MiB segments (one short), whose window regrows the host-mapped chunk list
+    after cdc_chunk_data sized it and reads it through the same waiting,
+    checking reader; cdc_chunk_and_hash of 1 MiB, then of 3 MiB (the chunk list
+    in HBM and the digests regrow); 17 MiB (past the 16 MiB ring limit: the
+    pageable copy, the data buffer regrows); 5 MiB (two ring pieces, 4 + 1 MiB);
+    64 KiB again (every buffer larger than it needs); a last write of 1 MiB +
+    17 bytes.  On 4 / 8 / 16 KiB the one-launch kernel takes the calls of up
+    to 4 MiB; on 64 / 256 / 1024 it is off and the chunk counts are large, so
+    every buffer regrows.  The guard never trips."""
+    import chunkfs_amd as c
+    cut = lambda a: oracle.fastcdc(a, *sizes)  # noqa: E731
+    data = oracle.splitmix64_bytes(17 * MIB, 51)
+    ch = c.FastChunker(c.SizeParams(*sizes))
+
+    def chunked(n, step):
+        _same(ch.chunk_array(data[:n]), cut(data[:n]), (sizes, step))
+        assert c.host_stats(ch)["guard_trips"] == 0, (sizes, step)
+
+    def written(a, step):
+        spans, _ = c.write_spans(ch, a, seg_size=MIB)
+        _same(spans, cut(a)[:, 1], (sizes, step))
+        assert c.host_stats(ch)["guard_trips"] == 0, (sizes, step)
+
+    def hashed(a, step):
+        chunks, dig = ch.chunk_and_hash(a)
+        _same(chunks, cut(a), (sizes, step))
+        for (o, n), d in zip(chunks, dig):
+            assert bytes(d) == hashlib.sha256(a[int(o):int(o + n)].tobytes()).digest(), (sizes, step, int(o))
+        assert c.host_stats(ch)["guard_trips"] == 0, (sizes, step)
+
+    chunked(64 << 10, "1: 64 KiB")
+    written(oracle.splitmix64_bytes(5 * MIB + 1, 52), "2: write of 5 MiB + 1")
+    hashed(oracle.splitmix64_bytes(MIB, 53), "3: hash 1 MiB")
+    hashed(oracle.splitmix64_bytes(3 * MIB, 54), "3: hash 3 MiB")
+    chunked(17 * MIB, "4: 17 MiB")
+    chunked(5 * MIB, "5: 5 MiB")
+    chunked(64 << 10, "6: 64 KiB again")
+    written(oracle.splitmix64_bytes(MIB + 17, 55), "7: write of 1 MiB + 17")
     ch.close()

@@ -258,7 +258,7 @@ def test_write_path_streaming_odd_segments():
 
 def test_write_path_carries_a_max_chunk_across_device_windows():
     """The write path chunks one device window (fs.write_window_bytes(), read
-    from engine.hpp: 256 MiB) at a time and carries the window's last chunk to
+    from host_path.hpp: 256 MiB) at a time and carries the window's last chunk to
     the front of the next one (room: max + 16 bytes); segments inside a window
     carry nothing.  So only a write longer than a window reaches the carry, and
     no setting makes the window smaller: this input is window + 20 MiB.  A zero

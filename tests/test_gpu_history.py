@@ -10,7 +10,8 @@ differs from the right one; a mismatch here names that call (harness.diagnose).
 
 Engine state each sequence targets (chunkfs_amd/csrc/engine.hpp; small_ws_,
 the staging blocks hb_, the device slots fs_, the workspace and d_gear_ are
-FastEngine's, fast_engine.hpp):
+FastEngine's, fast_engine.hpp; h_out_, the ring, d_data_ and the write windows
+are HostPath's, host_path.hpp):
 
     S1  h_out_ (the host-mapped chunk list), the pinned ring, d_data_; on the
         default handle also small_ws_ and the feed words
