@@ -628,6 +628,33 @@ class DiffStats:
         return "DiffStats { " + ", ".join(f"{f}: {getattr(self, f)}" for f in self.FIELDS) + " }"
 
 
+class DeltaStats:
+    """cdc_delta_stats_t of one FileSystem.delta, and the script itself: .ops is
+    the (n, 3) uint64 array of (b_off, len, a_off) that tiles [0, size_b), a_off
+    == DeltaStats.LITERAL for a LITERAL op; n_ops their number; bytes_copy and
+    bytes_literal the bytes of either kind; bytes_literal_tables the LITERAL
+    bytes before the edges were searched; spans_matched the spans of B whose
+    slot A names too; regions the LITERAL regions the tables gave.  .literals
+    (literals=True only) is a CUDA uint8 tensor: the LITERAL bytes in op order."""
+
+    LITERAL = _lib.CDC_DELTA_LITERAL
+    FIELDS = ("n_ops", "bytes_copy", "bytes_literal", "bytes_literal_tables", "spans_matched", "regions", "size_a",
+              "size_b", "seconds")
+    __slots__ = FIELDS + ("ops", "literals")
+
+    def __init__(self, **kw):
+        for f in self.FIELDS:
+            setattr(self, f, float(kw.get(f, 0)) if f == "seconds" else int(kw.get(f, 0)))
+        self.ops = np.zeros((0, 3), dtype=np.uint64)
+        self.literals = None
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f in self.FIELDS}
+
+    def __repr__(self):
+        return "DeltaStats { " + ", ".join(f"{f}: {getattr(self, f)}" for f in self.FIELDS) + " }"
+
+
 class PackStats:
     """cdc_pack_stats_t of one FileSystem.pack / unpack: the file's spans, the
     carried chunks, the spans whose chunk the pack does not carry, the unpadded
@@ -1208,6 +1235,73 @@ class FileSystem:
         r = DiffStats(n_ranges=s.ranges, **{f: getattr(s, f) for f in DiffStats.FIELDS[1:]})
         r.ranges = out[:n].cpu().numpy().view(np.uint64).reshape(n, 2)
         return r
+
+    # -- content-aligned delta ----------------------------------------------------------
+    def delta_device(self, a, b, flags, d_ops, cap, stats=None, stream=None):
+        """cdc_files_delta_device, raw: d_ops is a device pointer to cap
+        cdc_delta_op_t, stats a _lib.cdc_delta_stats_t or None.  Returns the
+        number of ops; nothing is written when it exceeds cap."""
+        return check(lib().cdc_files_delta_device(a._fh, b._fh, int(flags), _ptr(d_ops), int(cap),
+                                                  ctypes.byref(stats) if stats is not None else None, _ptr(stream)))
+
+    def _read_ranges(self, handle, ranges, out):
+        """One batch range read: (offset, length, position in `out`) each."""
+        reqs = [(handle, o, n, out.data_ptr() + at) for o, n, at in ranges if n]
+        if reqs:
+            import torch
+            torch.cuda.synchronize(out.device)
+            assert self.pread_batch_device(reqs) == [r[2] for r in reqs]
+
+    def delta(self, a, b, tables_only=False, literals=False, stream=None):
+        """The edit script that builds the file behind `b` (new) out of the one
+        behind `a` (old), aligned by content: DeltaStats, whose .ops is the (n, 3)
+        uint64 array of (b_off, len, a_off) tiling [0, size_b) -- COPY ops name
+        equal bytes of A, LITERAL ops (a_off == DeltaStats.LITERAL) bytes only B
+        has.  The span tables give the alignment; a few kilobytes around each
+        edit are read for the exact edges.  tables_only: no data is read and
+        whole unmatched spans are LITERAL.  literals: .literals holds the LITERAL
+        bytes in op order, what a receiver needs besides .ops (apply_delta)."""
+        import torch
+        dev = f"cuda:{self.device}"
+        flags = _lib.CDC_DELTA_TABLES_ONLY if tables_only else 0
+        s = _lib.cdc_delta_stats_t()
+        cap = 1024
+        while True:
+            out = torch.empty((cap, 3), dtype=torch.int64, device=dev)
+            torch.cuda.synchronize(dev)
+            n = self.delta_device(a, b, flags, out.data_ptr(), cap, s, stream)
+            if n <= cap:
+                break
+            cap = n  # the exact count: the files cannot change in between
+        r = DeltaStats(n_ops=s.ops, **{f: getattr(s, f) for f in DeltaStats.FIELDS[1:]})
+        r.ops = out[:n].cpu().numpy().view(np.uint64).reshape(n, 3)
+        if literals:
+            lit = r.ops[r.ops[:, 2] == DeltaStats.LITERAL]
+            at = np.concatenate([[0], np.cumsum(lit[:, 1])]).astype(np.uint64)
+            r.literals = torch.empty(int(at[-1]), dtype=torch.uint8, device=dev)
+            self._read_ranges(b, [(int(o), int(ln), int(p)) for (o, ln, _), p in zip(lit, at)], r.literals)
+        return r
+
+    def apply_delta(self, a, ops, literals):
+        """The receiver's half: B's bytes as a CUDA uint8 tensor, from the file
+        behind `a`, the ops of a delta and its LITERAL bytes in op order.  The
+        COPY ranges of A are read into place in one batch; the literals are
+        sliced in."""
+        import torch
+        dev = f"cuda:{self.device}"
+        ops = np.asarray(ops, dtype=np.uint64).reshape(-1, 3)
+        size = int(ops[:, 1].sum())
+        out = torch.empty(size, dtype=torch.uint8, device=dev)
+        lits = torch.as_tensor(literals, dtype=torch.uint8).to(dev) if literals is not None else None
+        at = 0
+        for b_off, ln, a_off in ops.tolist():
+            if a_off == DeltaStats.LITERAL:
+                out[b_off:b_off + ln] = lits[at:at + ln]
+                at += ln
+        self._read_ranges(a, [(a_off, ln, b_off) for b_off, ln, a_off in ops.tolist()
+                              if a_off != DeltaStats.LITERAL], out)
+        torch.cuda.synchronize(dev)
+        return out
 
     # -- packs: send and receive ----------------------------------------------------------
     def pack_device(self, handle, since, d_have, d_pack, cap, stats=None, stream=None):

@@ -43,7 +43,7 @@ EXPORTS = [
     "cdc_files_get_to_dedup_ratio", "cdc_file_verify_device", "cdc_store_size_distribution_device",
     "cdc_files_remove", "cdc_files_collect", "cdc_store_retain_device",
     "cdc_file_splice_device",
-    "cdc_files_clone", "cdc_files_diff_device",
+    "cdc_files_clone", "cdc_files_diff_device", "cdc_files_delta_device",
     "cdc_file_pack_device", "cdc_files_unpack_device",
     "cdc_hash_batch_device", "cdc_store_set_hash", "cdc_store_hash",
     "cdc_fill_splitmix64_device", "cdc_version", "cdc_abi_version",
@@ -133,6 +133,21 @@ class cdc_diff_stats_t(ctypes.Structure):
 
 
 CDC_DIFF_TABLES_ONLY = 1
+
+
+class cdc_delta_op_t(ctypes.Structure):
+    _fields_ = [("b_off", ctypes.c_uint64), ("len", ctypes.c_uint64), ("a_off", ctypes.c_uint64)]
+
+
+class cdc_delta_stats_t(ctypes.Structure):
+    _fields_ = [("ops", ctypes.c_uint64), ("bytes_copy", ctypes.c_uint64), ("bytes_literal", ctypes.c_uint64),
+                ("bytes_literal_tables", ctypes.c_uint64), ("spans_matched", ctypes.c_uint64),
+                ("regions", ctypes.c_uint64), ("size_a", ctypes.c_uint64), ("size_b", ctypes.c_uint64),
+                ("seconds", ctypes.c_double)]
+
+
+CDC_DELTA_LITERAL = 0xFFFFFFFFFFFFFFFF
+CDC_DELTA_TABLES_ONLY = 1
 CDC_UNPACK_TRUST = 1
 CDC_HASH_SHA256 = 0
 CDC_HASH_BLAKE2SP = 1
@@ -346,6 +361,8 @@ def lib():
     L.cdc_files_clone.restype = ctypes.c_int64
     L.cdc_files_diff_device.argtypes = [P, P, ctypes.c_uint32, P, sz, ctypes.POINTER(cdc_diff_stats_t), P]
     L.cdc_files_diff_device.restype = ctypes.c_int64
+    L.cdc_files_delta_device.argtypes = [P, P, ctypes.c_uint32, P, sz, ctypes.POINTER(cdc_delta_stats_t), P]
+    L.cdc_files_delta_device.restype = ctypes.c_int64
     L.cdc_file_pack_device.argtypes = [P, P, P, P, sz, ctypes.POINTER(cdc_pack_stats_t), P]
     L.cdc_file_pack_device.restype = ctypes.c_int64
     L.cdc_files_unpack_device.argtypes = [P, ctypes.c_char_p, P, sz, P, ctypes.c_uint32,

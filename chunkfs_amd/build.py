@@ -11,9 +11,9 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libchunkfs_amd.so")
-SOURCES = ["fastcdc.hip", "small.hip", "walk.hip", "util_kernels.hip", "sha256.hip", "blake2sp.hip", "index.hip", "store.hip", "files.hip", "pack.hip", "engine.cpp", "fast_engine.cpp", "walk_engine.cpp", "hash_engine.cpp", "hostpath.cpp", "capi.cpp",
+SOURCES = ["fastcdc.hip", "small.hip", "walk.hip", "util_kernels.hip", "sha256.hip", "blake2sp.hip", "index.hip", "store.hip", "files.hip", "delta.hip", "pack.hip", "engine.cpp", "fast_engine.cpp", "walk_engine.cpp", "hash_engine.cpp", "hostpath.cpp", "capi.cpp",
            "index_host.cpp", "store_host.cpp", "files_host.cpp"]
-HEADERS = ["fastcdc.hpp", "small.hpp", "walk.hpp", "cdc_kernels.hpp", "sha256.hpp", "blake2sp.hpp", "hash_feed.hpp", "index.hpp", "store.hpp", "store_internal.hpp", "files.hpp", "read_plan.hpp", "splice_plan.hpp", "diff_plan.hpp", "pack.hpp", "pack_plan.hpp", "host_common.hpp", "engine.hpp", "fast_engine.hpp", "walk_engine.hpp", "hash_engine.hpp", "host_path.hpp"]
+HEADERS = ["fastcdc.hpp", "small.hpp", "walk.hpp", "cdc_kernels.hpp", "sha256.hpp", "blake2sp.hpp", "hash_feed.hpp", "index.hpp", "store.hpp", "store_internal.hpp", "files.hpp", "read_plan.hpp", "splice_plan.hpp", "diff_plan.hpp", "delta.hpp", "delta_plan.hpp", "pack.hpp", "pack_plan.hpp", "host_common.hpp", "engine.hpp", "fast_engine.hpp", "walk_engine.hpp", "hash_engine.hpp", "host_path.hpp"]
 ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-result"]

@@ -14,6 +14,8 @@
 
 #include "../../include/chunkfs_amd.h"
 #include "../../include/chunkfs_amd_debug.h"
+#include "delta.hpp"
+#include "delta_plan.hpp"
 #include "engine.hpp"
 #include "files.hpp"
 #include "diff_plan.hpp"
@@ -106,6 +108,7 @@ struct HostWords {               // pinned host memory
     word ranges, bytes_differing, bytes_compared, bytes_shared, pieces;  // launch_files_diff
     word pack_chunks, pack_data;      // launch_pack_mark: carried chunks, bytes of the data section
     word pack_external, pack_bytes;   // DeviceWords' copy
+    word delta[6];  // launch_files_delta: ops, bytes_copy, bytes_literal, bytes_literal_tables, spans_matched, regions
 };
 struct DeviceWords {
     word least, zeros;  // launch_files_append's d_stat, preset to {~0, 0}: min(length - 1) over the spans of
@@ -222,6 +225,7 @@ struct cdc_files {
     cdc::ScanScratch<cdc::SpanRec> xspan;  // reads in the scrubbed state: per span, with the piece counts
     DeviceBuf<uint8_t> window;  // cdc_file_splice_device: the window of the new file that is chunked
     DeviceBuf<uint8_t> diff;    // cdc_files_diff_device: one block carved into the DiffScratch arrays
+    DeviceBuf<uint8_t> delta;   // cdc_files_delta_device: one block carved into the DeltaScratch arrays
     PackScratch pack;
     UnpackScratch unpack;
 };
@@ -737,6 +741,54 @@ int grow_diff(cdc_files *fs, uint64_t na, uint64_t nb, uint64_t common, bool tab
     return CDC_OK;
 }
 
+// ---- delta ----------------------------------------------------------------------
+// The delta's scratch for two tables of na and nb > 0 spans, one block as the
+// diff's is.  A run begins at a span of B, so there are at most nb of them; a
+// region adds at most one ragged tile to its whole ones; a region opens at most
+// three ops and a COPY run one, and regions alternate with COPY runs.
+int grow_delta(cdc_files *fs, uint64_t na, uint64_t nb, uint64_t size_b, hipStream_t s, cdc::DeltaScratch *w) {
+    const uint64_t sb = cdc::store_scan_blocks(nb) + 1;
+    size_t sort_bytes = 0;
+    FL_TRY(cdc::launch_retain_sort(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, na, 32, s));
+    const uint64_t words = 4 /* acc */ + 2 * na /* key_in, key */ + nb /* diag */ + nb /* rflag */ +
+                           2 * (nb + 1) /* rb, rd */ + 4 * nb /* tstart, fwd, bwd, hcount */ + 6 * nb /* hb, ha */ +
+                           3 * sb;
+    const uint64_t idx_at = words * 8, sort_at = (idx_at + 2 * na * 4 + 255) & ~255ull;
+    const uint64_t bytes = sort_at + sort_bytes;
+    if (fs->delta.cap < bytes) FL_TRY(fs->delta.room(bytes + bytes / 8));
+    uint64_t *p = reinterpret_cast<uint64_t *>(fs->delta.p);
+    auto take = [&p](uint64_t n) {
+        uint64_t *r = p;
+        p += n;
+        return r;
+    };
+    w->acc = reinterpret_cast<unsigned long long *>(take(4));
+    w->key_in = take(na);
+    w->key = take(na);
+    w->diag = reinterpret_cast<int64_t *>(take(nb));
+    w->rflag = take(nb);
+    w->rb = take(nb + 1);
+    w->rd = reinterpret_cast<int64_t *>(take(nb + 1));
+    w->tstart = take(nb);
+    w->fwd = reinterpret_cast<unsigned long long *>(take(nb));
+    w->bwd = reinterpret_cast<unsigned long long *>(take(nb));
+    w->hcount = take(nb);
+    w->hb = take(3 * nb);
+    w->ha = take(3 * nb);
+    w->bs_r = take(sb);
+    w->bs_t = take(sb);
+    w->bs_h = take(sb);
+    w->n_runs = w->bs_r + sb - 1;
+    w->n_tiles = w->bs_t + sb - 1;
+    w->n_ops = w->bs_h + sb - 1;
+    w->idx_in = reinterpret_cast<uint32_t *>(fs->delta.p + idx_at);
+    w->idx = w->idx_in + na;
+    w->sort_tmp = fs->delta.p + sort_at;
+    w->sort_bytes = sort_bytes;
+    w->max_tiles = size_b / cdc::kDeltaTile + nb;
+    return CDC_OK;
+}
+
 // ---- packs ------------------------------------------------------------------------
 bool scrubbed(const cdc_files *fs) {
     cdc::ScrubView sv;
@@ -1100,6 +1152,67 @@ int64_t cdc_files_diff_device(cdc_fh_t *a, cdc_fh_t *b, uint32_t flags, cdc_chun
     r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (stats) *stats = r;
     return (int64_t)r.ranges;
+}
+
+int64_t cdc_files_delta_device(cdc_fh_t *a, cdc_fh_t *b, uint32_t flags, cdc_delta_op_t *d_ops, size_t cap,
+                               cdc_delta_stats_t *stats, void *hip_stream) {
+    const auto t0 = std::chrono::steady_clock::now();
+    // Everything that can refuse, before any device work.
+    if (flags & ~(uint32_t)CDC_DELTA_TABLES_ONLY)
+        return fail(CDC_EINVAL, "cdc_files_delta_device: unknown flag bits " + std::to_string(flags));
+    if (!a || !b) return fail(CDC_EINVAL, "cdc_files_delta_device: NULL file handle");
+    if (cap && !d_ops) return fail(CDC_EINVAL, "cdc_files_delta_device: NULL destination");
+    if (a->fs && b->fs && a->fs != b->fs)
+        return fail(CDC_EINVAL, "cdc_files_delta_device: the handles belong to two file layers");
+    FileRec *fa = nullptr, *fb = nullptr;
+    int rc = lookup(a, true, &fa);
+    if (rc) return rc;
+    if ((rc = lookup(b, true, &fb)) != CDC_OK) return rc;
+    cdc_files *fs = a->fs;
+    if (scrubbed(fs))
+        return fail(CDC_ENOTSUP, "cdc_files_delta_device: the store holds target-kind containers (scrubbed); "
+                                 "not supported");
+    const bool tables_only = (flags & CDC_DELTA_TABLES_ONLY) != 0;
+    const cdc::StoreView v = cdc::store_view(fs->store);
+    FL_TRY(hipSetDevice(v.device));
+    hipStream_t s = stream_of(fs, hip_stream);
+    cdc_delta_stats_t r{};
+    r.size_a = fa->size;
+    r.size_b = fb->size;
+    if (!fb->size) {
+        // no byte to build: no op
+    } else if (!fa->size) {  // nothing to copy from: one LITERAL
+        r.ops = r.regions = 1;
+        r.bytes_literal = r.bytes_literal_tables = fb->size;
+        if (cap) {
+            const cdc_delta_op_t all{0, fb->size, CDC_DELTA_LITERAL};
+            FL_TRY(hipMemcpyAsync(d_ops, &all, sizeof all, hipMemcpyHostToDevice, s));
+            FL_TRY(hipStreamSynchronize(s));
+        }
+    } else {
+        cdc::DeltaScratch w{};
+        if ((rc = grow_delta(fs, fa->n, fb->n, fb->size, s, &w)) != CDC_OK) return rc;
+        const cdc::DiffSide da{fa->t.off, fa->t.loc, fa->t.slot, fa->n, fa->size};
+        const cdc::DiffSide db{fb->t.off, fb->t.loc, fb->t.slot, fb->n, fb->size};
+        static_assert(sizeof(cdc::DeltaOp) == sizeof(cdc_delta_op_t), "one layout");
+        const hipError_t e = cdc::launch_files_delta(da, db, (uint64_t)(uintptr_t)v.arena, tables_only, w,
+                                                     reinterpret_cast<cdc::DeltaOp *>(d_ops), cap, fs->hw->delta, s);
+        const hipError_t hs = hipStreamSynchronize(s);  // the one wait of the call
+        if (e != hipSuccess || hs != hipSuccess) {
+            cdc::set_error(std::string("cdc_files_delta_device: ") + hipGetErrorString(e != hipSuccess ? e : hs));
+            return CDC_EDEVICE;
+        }
+        const word *h = fs->hw->delta;
+        r.ops = h[0];
+        r.bytes_copy = h[1];
+        r.bytes_literal = h[2];
+        r.bytes_literal_tables = h[3];
+        r.spans_matched = h[4];
+        r.regions = h[5];
+    }
+    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) *stats = r;
+    return (int64_t)r.ops;
 }
 
 int64_t cdc_file_pack_device(cdc_fh_t *fh, cdc_fh_t *since, const uint8_t *d_have, uint8_t *d_pack, size_t cap,

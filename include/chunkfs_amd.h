@@ -47,7 +47,9 @@ extern "C" {
  *    cdc_file_pack_device, cdc_files_unpack_device, cdc_pack_stats_t,
  *    CDC_UNPACK_TRUST; the second hasher -- CDC_HASH_SHA256,
  *    CDC_HASH_BLAKE2SP, cdc_hash_batch_device, cdc_store_set_hash,
- *    cdc_store_hash. */
+ *    cdc_store_hash; the content-aligned delta -- cdc_files_delta_device,
+ *    cdc_delta_op_t, cdc_delta_stats_t, CDC_DELTA_LITERAL,
+ *    CDC_DELTA_TABLES_ONLY. */
 #define CHUNKFS_AMD_ABI_VERSION 6
 
 /* Chunk{offset,length} -- reference src/lib.rs:43-47 (usize fields; u64 here). */
@@ -1031,6 +1033,76 @@ int64_t cdc_files_clone(cdc_files_t *fs, const char *src, const char *dst, void 
 /* Returns the number of runs, or a negative CDC_E* code.  stats is nullable. */
 int64_t cdc_files_diff_device(cdc_fh_t *a, cdc_fh_t *b, uint32_t flags, cdc_chunk_t *d_ranges, size_t cap,
                               cdc_diff_stats_t *stats, void *hip_stream);
+
+/* ---- Content-aligned delta ----------------------------------------------------------
+ * Not in the reference.  cdc_files_diff_device compares position by position, so
+ * one inserted byte makes every later byte differ.  cdc_files_delta_device aligns
+ * by content instead and returns an edit script that builds file B (new) out of
+ * file A (old): an ordered list of ops that tile [0, size_b) exactly.
+ *   COPY    {b_off, len, a_off}              B[b_off, b_off + len) == A[a_off, a_off + len);
+ *   LITERAL {b_off, len, CDC_DELTA_LITERAL}  the bytes come from B.
+ * COPY sources may overlap each other and appear in any order in A.  The store is
+ * content-defined, so after an insert or delete the chunker falls back onto the
+ * old cuts within a few spans and every later span of B names the same store slot
+ * as a span of A at a shifted offset: the tables give the alignment, a few
+ * kilobytes around the edit give the exact edges.
+ *   The rule is deterministic.  Spans of length 0 hold no byte and take no part.
+ *   1. Anchors (tables only).  B's span j matches when some span of A has the same
+ * slot.  Among A's spans with that slot the one taken is the span i that minimises
+ * |off_a[i] - off_b[j]|; on a tie the smaller off_a[i] wins.  Its diagonal is
+ * off_a[i] - off_b[j].  An unchanged region is a diagonal-0 copy, and a run of one
+ * repeated chunk stays on one diagonal.
+ *   2. Runs.  Consecutive matched spans of B with the same diagonal form one COPY;
+ * consecutive unmatched spans form one LITERAL region [l, r).  With
+ * CDC_DELTA_TABLES_ONLY this is the answer, and no arena byte is read.
+ *   3. Edges (exact mode).  Each region is set against its neighbours' diagonals:
+ * dL is the left COPY's diagonal, or 0 when the region begins the file; dR is the
+ * right COPY's diagonal, or size_a - size_b when the region ends the file -- so
+ * two files that share no slot still get their common prefix and suffix.  e is the
+ * largest value <= r - l with B[l + k] == A[l + dL + k] for all k < e; it stops
+ * where the A index leaves [0, size_a).  f is the largest value <= (r - l) - e with
+ * B[r - 1 - k] == A[r - 1 - k + dR] for all k < f, under the same bound: forward
+ * takes precedence.  The region becomes COPY e, LITERAL r - l - e - f, COPY f.
+ *   4. Canonical form.  Ops of length 0 are dropped; adjacent COPYs on one diagonal
+ * are merged (a region that vanishes joins its neighbours); after that no two
+ * LITERALs are adjacent.
+ * Returns the number of ops; d_ops (DEVICE, cap entries) is written only when that
+ * number is <= cap, otherwise nothing is written and stats is still filled
+ * (cdc_files_diff_device's convention).  bytes_copy + bytes_literal == size_b.
+ * bytes_literal_tables is the LITERAL bytes after step 2: it bounds what step 3
+ * reads.  Read-only handles are fine; cursors are not touched; a and b on the same
+ * file give one COPY with a_off == 0, or no op when the file is empty.  With
+ * size_a == 0 the answer is one LITERAL, with size_b == 0 no op, and neither
+ * runs a device pass.  The host waits for the device once.  Refusals, each before
+ * any device work, leaving stats and d_ops untouched:
+ *   CDC_EINVAL    unknown flag bits, a NULL handle, cap > 0 with NULL d_ops,
+ *                 handles of two different layers;
+ *   CDC_ENOTFOUND a removed file, or one whose spans predate a store clear;
+ *   CDC_ENOTSUP   the store holds target-kind containers (it was scrubbed).
+ * Stream convention: cdc_file_write_device's. */
+typedef struct cdc_delta_op {
+    uint64_t b_off; /* where the op's bytes lie in B */
+    uint64_t len;
+    uint64_t a_off; /* COPY: where they lie in A; LITERAL: CDC_DELTA_LITERAL */
+} cdc_delta_op_t;
+
+typedef struct cdc_delta_stats {
+    uint64_t ops;                  /* ops of the whole script, also when it exceeds cap */
+    uint64_t bytes_copy;           /* bytes of the COPY ops */
+    uint64_t bytes_literal;        /* bytes of the LITERAL ops */
+    uint64_t bytes_literal_tables; /* LITERAL bytes after step 2 */
+    uint64_t spans_matched;        /* spans of B with bytes whose slot A names too */
+    uint64_t regions;              /* LITERAL regions after step 2 */
+    uint64_t size_a, size_b;
+    double seconds;                /* wall time of the call */
+} cdc_delta_stats_t;
+
+#define CDC_DELTA_LITERAL (~0ull) /* a_off of a LITERAL op */
+#define CDC_DELTA_TABLES_ONLY 1u
+
+/* Returns the number of ops, or a negative CDC_E* code.  stats is nullable. */
+int64_t cdc_files_delta_device(cdc_fh_t *a, cdc_fh_t *b, uint32_t flags, cdc_delta_op_t *d_ops, size_t cap,
+                               cdc_delta_stats_t *stats, void *hip_stream);
 
 /* ---- Packs: send and receive ----------------------------------------------------------
  * Not in the reference.  A pack is one file of the layer as a self-describing,

@@ -501,6 +501,21 @@ class Files {
         d.ranges = check(cdc_files_diff_device(a.handle(), b.handle(), flags, d_ranges, cap, &d.stats, hip_stream));
         return d;
     }
+    // cdc_files_delta_device: the edit script that builds b (new) out of a (old),
+    // aligned by content: COPY {b_off, len, a_off} and LITERAL {b_off, len,
+    // CDC_DELTA_LITERAL} ops that tile [0, size_b), in d_ops (DEVICE, cap entries;
+    // written only when the count is <= cap), and the stats.
+    // CDC_DELTA_TABLES_ONLY reads no data: whole unmatched spans are LITERAL.
+    struct Delta {
+        int64_t ops;
+        cdc_delta_stats_t stats;
+    };
+    Delta delta(File &a, File &b, uint32_t flags = 0, cdc_delta_op_t *d_ops = nullptr, size_t cap = 0,
+                void *hip_stream = nullptr) {
+        Delta d{};
+        d.ops = check(cdc_files_delta_device(a.handle(), b.handle(), flags, d_ops, cap, &d.stats, hip_stream));
+        return d;
+    }
     // cdc_files_unpack_device: the new file `name` from the len bytes of a pack at
     // d_pack (DEVICE, 16-byte aligned).  The pack is validated before anything is
     // written; hasher (nullable only with CDC_UNPACK_TRUST) checks the carried

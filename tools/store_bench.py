@@ -126,6 +126,20 @@ BLAKE2sp in the same run, each leg on layers of its own per hasher:
 Each reports the median and the min-max per hasher and SHA-256's time over
 BLAKE2sp's; the two conditions of DESIGN.md "Hashers" are evaluated at the end.
 
+The content-aligned delta (skipped with --no-delta, alone with --only-delta), on a
+layer of its own holding the 1 GiB file of (d) and an unrelated one:
+
+  (ah) cdc_files_delta_device of a clone against the original after a 4 KiB
+       overwrite in the middle, exact and with CDC_DELTA_TABLES_ONLY;
+  (ai) the same after a 4 KiB insert; (aj) the same after a 4 KiB delete;
+  (ak) the delta of the two unrelated files;
+  (al) the delta of the file against the same bytes cut by FastCDC 2/4/8 KiB:
+       hardly a slot in common, every byte compared and equal, one COPY.
+
+Beside each, in the same run, cdc_files_diff_device of the same pair -- after the
+insert and the delete it compares the half of the file behind the edit and calls
+it changed -- and for (ak) also read_complete_device plus cdc_file_verify_device.
+
 Prints one JSON line; --out also writes it to a file.
 """
 import argparse
@@ -484,6 +498,85 @@ def snapshot_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med):
     return res
 
 
+def delta_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med):
+    """Legs (ah)-(ak) on a layer of its own holding the file of (d): the delta of a
+    clone against the original after a 4 KiB overwrite, a 4 KiB insert and a 4 KiB
+    delete in the middle, exact and from the tables alone, and the delta of two
+    unrelated files.  Beside each, the parent's way in the same run: the diff of
+    the same pair, and read + verify for the unrelated pair."""
+    import torch
+    from chunkfs_amd import _lib
+
+    other = torch.empty(n, dtype=torch.uint8, device="cuda")
+    fresh = torch.empty(4096, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    _lib.check(L.cdc_fill_splitmix64_device(P(other.data_ptr()), n, a.seed + 11, None))
+    _lib.check(L.cdc_fill_splitmix64_device(P(fresh.data_ptr()), 4096, a.seed + 13, None))
+    fsys = c.FileSystem(store=c.ChunkStore(5 * k + (1 << 15), 3 * n + 80 * k + (64 << 20)))
+    w = fsys.create_file("bench", ch)
+    assert L.cdc_file_write_device(w._fh, ch._h, P(buf.data_ptr()), n, None) == k
+    o = fsys.create_file("other", ch)
+    assert L.cdc_file_write_device(o._fh, ch._h, P(other.data_ptr()), n, None) > 0
+    cap = 1024
+    d_ops = torch.empty((cap, 3), dtype=torch.int64, device="cuda")
+    d_ranges = torch.empty((cap, 2), dtype=torch.int64, device="cuda")
+    st, ds, first = _lib.cdc_delta_stats_t(), _lib.cdc_diff_stats_t(), ctypes.c_uint64(0)
+    torch.cuda.synchronize()
+    res = {}
+
+    def delta_leg(name, x, y, flags):
+        def call():
+            got = L.cdc_files_delta_device(x._fh, y._fh, flags, P(d_ops.data_ptr()), cap, ctypes.byref(st), P(sp))
+            assert 0 <= got <= cap, f"cdc_files_delta_device: {got}"
+
+        t = timed(call)
+        res[name] = dict({f: getattr(st, f) for f, _ in _lib.cdc_delta_stats_t._fields_ if f != "seconds"},
+                         ms=med(t), ms_min_max=[min(t), max(t)])
+        return res[name]
+
+    def diff_leg(name, x, y):
+        def call():
+            assert L.cdc_files_diff_device(x._fh, y._fh, 0, P(d_ranges.data_ptr()), cap, ctypes.byref(ds), P(sp)) >= 0
+
+        t = timed(call)
+        res[name] = {"ms": med(t), "ms_min_max": [min(t), max(t)], "bytes_compared": ds.bytes_compared,
+                     "bytes_differing": ds.bytes_differing}
+
+    mid = n // 2 + 1234
+    for label, rem, ins in (("ah_overwrite", 4096, 4096), ("ai_insert", 0, 4096), ("aj_delete", 4096, 0)):
+        name = "snap_" + label
+        assert L.cdc_files_clone(fsys._h, b"bench", name.encode(), None) == k
+        e = fsys.open_file(name, ch)
+        assert L.cdc_file_splice_device(e._fh, ch._h, mid, rem, P(fresh.data_ptr()) if ins else None, ins, None,
+                                        None) >= 0
+        r = delta_leg(label + "_delta", w, e, 0)
+        if r["bytes_literal"] > ins or r["ops"] != (3 if ins else 2) or r["bytes_literal_tables"] > 16 * 16384:
+            raise SystemExit(f"store_bench: the delta after a 4 KiB edit is not the edit ({label}: {r})")
+        delta_leg(label + "_delta_tables_only", w, e, _lib.CDC_DELTA_TABLES_ONLY)
+        diff_leg(label + "_diff", w, e)
+    r = delta_leg("ak_unrelated_delta", w, o, 0)
+    if r["spans_matched"] or r["bytes_copy"] > 64:
+        raise SystemExit("store_bench: two unrelated files share bytes")
+
+    def read_plus_verify():
+        assert L.cdc_file_read_complete_device(w._fh, P(out.data_ptr()), n, None, P(sp)) == n
+        assert L.cdc_file_verify_device(o._fh, P(out.data_ptr()), n, ctypes.byref(first), P(sp)) == 0
+
+    t = timed(read_plus_verify)
+    res["ak_unrelated_read_plus_verify"] = {"ms": med(t), "ms_min_max": [min(t), max(t)], "first_diff": first.value}
+    diff_leg("ak_unrelated_diff", w, o)
+
+    # (al) the same bytes under other cuts: hardly a slot in common, every byte compared and equal
+    ch2 = c.FastChunker(c.SizeParams(2048, 4096, 8192))
+    o2 = fsys.create_file("recut", ch2)
+    assert L.cdc_file_write_device(o2._fh, ch2._h, P(buf.data_ptr()), n, None) > 0
+    r = delta_leg("al_recut_delta", w, o2, 0)
+    if r["bytes_literal"] or r["ops"] != 1:
+        raise SystemExit(f"store_bench: the delta of equal bytes under other cuts is not one COPY ({r})")
+    diff_leg("al_recut_diff", w, o2)
+    return res
+
+
 def pack_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med):
     """Legs (y)-(ab): the file of (d) packed whole and against a clone after a
     4 KiB overwrite; both packs unpacked into a second layer."""
@@ -728,6 +821,8 @@ def main():
     ap.add_argument("--no-pack", action="store_true", help="skip the pack and unpack legs (y)-(ab)")
     ap.add_argument("--no-hash", action="store_true", help="skip the two-hasher legs (ac)-(ag)")
     ap.add_argument("--only-hash", action="store_true", help="the two-hasher legs (ac)-(ag) alone")
+    ap.add_argument("--no-delta", action="store_true", help="skip the content-aligned delta legs (ah)-(ak)")
+    ap.add_argument("--only-delta", action="store_true", help="the content-aligned delta legs (ah)-(ak) alone")
     ap.add_argument("--collect-iters", type=int, default=3)
     ap.add_argument("--scrub-iters", type=int, default=3)
     ap.add_argument("--scrub-groups", default="4096,64m;65536,256m;1048576,1024m",
@@ -791,6 +886,12 @@ def main():
         return finish({"tool": "store_bench", "bytes": n, "chunks": k, "iters": a.iters, "warmup": a.warmup,
                        "device": torch.cuda.get_device_name(0), "source_digest": build.source_digest(),
                        "hash": hash_legs(a, c, _lib.lib(), ctypes.c_void_p, ch, buf, n, k, sp, timed, med)})
+
+    if a.only_delta:
+        med = lambda v: float(np.median(v))  # noqa: E731
+        return finish({"tool": "store_bench", "bytes": n, "chunks": k, "iters": a.iters, "warmup": a.warmup,
+                       "device": torch.cuda.get_device_name(0), "source_digest": build.source_digest(),
+                       "delta": delta_legs(a, c, _lib.lib(), ctypes.c_void_p, ch, buf, out, n, k, sp, timed, med)})
 
     def do_put():
         got = store.put_batch_device([buf.data_ptr()], [n], first, chunks.data_ptr(), dig.data_ptr(), stream=sp)
@@ -949,6 +1050,8 @@ def main():
         res["pack"] = pack_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med)
     if not a.no_hash:
         res["hash"] = hash_legs(a, c, L, P, ch, buf, n, k, sp, timed, med)
+    if not a.no_delta:
+        res["delta"] = delta_legs(a, c, L, P, ch, buf, out, n, k, sp, timed, med)
     finish(res)
 
 
