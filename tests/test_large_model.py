@@ -4,6 +4,14 @@ piece (restart and prefix stability, tests/large_model.py), for every rule
 verified that way and for tests/ae_model.py; and the verifier itself: it
 accepts the oracle's own list, compares every row exactly once, and rejects
 each planted fault naming the piece that holds it.
+
+And what tests/test_gpu_large_later.py stands on: blake2sp_rows against
+blake2sp_model.oracle, pack_index against pack_model.pack byte for byte, the
+delta closed forms against delta_model.delta on the same edits scaled down (the
+line parametrised), the device-side comparison of a pack's data section on CPU
+tensors, and the power condition: at N_BIG every expectation holds a value
+>= 2^32 in the field its case is named for and changes when that field is cut
+to 32 bits.
 """
 import numpy as np
 import pytest
@@ -315,6 +323,240 @@ def test_sha256_rows_equals_a_plain_loop():
         got = lm.sha256_rows(d, rows, threads)
         assert got.shape == (len(rows), 32) and [bytes(x) for x in got] == want
     assert lm.sha256_rows(d, np.zeros((0, 2), dtype=np.uint64)).shape == (0, 32)
+
+
+# ---- what test_gpu_large_later.py expects -----------------------------------------
+
+def test_blake2sp_rows_equals_the_oracle():
+    import blake2sp_model as bm
+    d = data()
+    edges = [0, 1, 63, 64, 65, 447, 448, 449, 511, 512, 513, 575, 576, 1023, 1024, 1025, 4095, 4096, 4097, 70001]
+    rows = np.concatenate([ref("fast")[:200], np.array([[7 + 3 * i, n] for i, n in enumerate(edges)], dtype=np.uint64),
+                           np.array([[N - 3, 3], [12345, (1 << 20) + 77]], dtype=np.uint64)])
+    want = [bm.oracle(d[int(o):int(o) + int(ln)].tobytes()) for o, ln in rows]
+    for threads in (None, 1, 3):
+        got = lm.blake2sp_rows(d, rows, threads)
+        assert got.shape == (len(rows), 32) and [bytes(x) for x in got] == want
+    assert lm.blake2sp_rows(d, np.zeros((0, 2), dtype=np.uint64)).shape == (0, 32)
+    for msg, hexd in bm.KNOWN.items():
+        assert lm.blake2sp_one(np.frombuffer(msg, dtype=np.uint8)).hex() == hexd
+
+
+def _model_file(content, chunks):
+    import gc_model as gm
+    files = gm.Files()
+    h = files.create("f")
+    if len(chunks):
+        files.append(h, content, np.asarray(chunks, dtype=np.uint64).reshape(-1, 2))
+    return files, h
+
+
+def _pack_tilings():
+    import pack_model as pm
+    d = data()
+    out = {label: v for label, v in pm.shapes().items()}                   # 0 and 1 spans, padding lengths, repeats
+    out["fastcdc"] = (d[:300001], RULES["fast"](d[:300001]))
+    block = d[:4096]
+    out["repeats between"] = (np.concatenate([block, d[5000:5777], block, block, d[9000:9001]]),
+                              pm.tiling([4096, 777, 4096, 4096, 1]))
+    return out
+
+
+@pytest.mark.parametrize("label", ["empty", "one span", "2049 spans", "padding lengths", "length-0 spans",
+                                   "heavy duplication", "fastcdc", "repeats between"])
+def test_pack_index_equals_the_pack_model(label):
+    import pack_model as pm
+    content, chunks = _pack_tilings()[label]
+    files, h = _model_file(content, chunks)
+    blob, st = pm.pack(files, h)
+    digests = np.frombuffer(b"".join(files.hashes(h)), dtype=np.uint8).reshape(-1, 32)
+    x = lm.pack_index(chunks, digests)
+    assert x.layout == pm.layout(len(chunks), x.n_chunks, x.data_bytes)
+    assert x.index.tobytes() == blob[:x.layout["data"]]
+    assert len(blob) == x.layout["total"] == st["pack_bytes"]
+    assert (st["spans"], st["chunks"], st["chunk_bytes"], st["file_size"], st["external_spans"]) == \
+        (len(chunks), x.n_chunks, x.chunk_bytes, x.file_size, 0)
+    # ... and the data section is what the index says: chunk k at chunk_off[k], zeros after it
+    body = np.frombuffer(blob, dtype=np.uint8)[x.layout["data"]:]
+    assert body.size == x.data_bytes
+    for k in range(x.n_chunks):
+        o, ln = (int(v) for v in np.asarray(chunks, dtype=np.uint64).reshape(-1, 2)[int(x.chunk_span[k])])
+        a, b = int(x.chunk_off[k]), int(x.chunk_off[k + 1])
+        assert np.array_equal(body[a:a + ln], content[o:o + ln]) and not body[a + ln:b].any()
+
+
+def test_pack_data_mismatch_compares_every_byte():
+    """The device-side comparison of a pack's data section, here on CPU tensors
+    and in slabs that end inside chunks and inside padding."""
+    import torch
+    import pack_model as pm
+    content, chunks = _pack_tilings()["fastcdc"]
+    chunks = np.concatenate([chunks[:-1], [[int(chunks[-1, 0]), 5]], [[int(chunks[-1, 0]) + 5, int(chunks[-1, 1]) - 5]]])
+    files, h = _model_file(content, chunks.astype(np.uint64))
+    blob, _ = pm.pack(files, h)
+    x = lm.pack_index(chunks, np.frombuffer(b"".join(files.hashes(h)), dtype=np.uint8).reshape(-1, 32))
+    body = np.frombuffer(blob, dtype=np.uint8)[x.layout["data"]:].copy()
+    buf = torch.from_numpy(content.copy())
+    for slab in (1 << 20, 4099, 1000):
+        assert lm.pack_data_mismatch(torch.from_numpy(body), buf, chunks, x.chunk_span, x.chunk_off, slab) is None
+    k = x.n_chunks - 2                                        # the 5-byte chunk: 11 bytes of padding behind it
+    a = int(x.chunk_off[k])
+    assert int(x.chunk_off[k + 1]) - a == 16
+    for at in (0, 4098, 4099, a + 4, a + 5, a + 15, a + 16, body.size - 1):
+        bad = body.copy()
+        bad[at] ^= 1
+        for slab in (1 << 20, 4099):
+            assert lm.pack_data_mismatch(torch.from_numpy(bad), buf, chunks, x.chunk_span, x.chunk_off, slab) == at
+    moved = torch.from_numpy(np.roll(content, 1))             # the right pack, the wrong source
+    assert lm.pack_data_mismatch(torch.from_numpy(body), moved, chunks, x.chunk_span, x.chunk_off) == 0
+
+
+def test_common_prefix_and_suffix():
+    d = data()[:300000]
+    for n in (0, 1, 65535, 65536, 65537, 200001):
+        x = d.copy()
+        x[n] ^= 1
+        assert lm.common_prefix(d, x) == n == lm.common_prefix(x, d[:250000])
+        y = d.copy()
+        y[y.size - 1 - n] ^= 1
+        assert lm.common_suffix(d, y) == n == lm.common_suffix(y[1000:], d)
+    assert lm.common_prefix(d, d[:70000]) == 70000 == lm.common_suffix(d, d[-70000:])
+    assert lm.common_prefix(d, d[:0]) == 0 == lm.common_suffix(d[:0], d)
+
+
+def test_constants_read_from_the_sources():
+    assert lm.csrc_const("kDlMaxBlocks", "delta.hip") == 1 << 18
+    assert lm.csrc_const("kDeltaTile", "delta_plan.hpp") == 4096
+    assert lm.delta_tiles(0) == 0 and lm.delta_tiles(1) == 1 and lm.delta_tiles(4096) == 1 and lm.delta_tiles(4097) == 2
+    assert lm.delta_tiles(lm.LINE + 5) > lm.csrc_const("kDlMaxBlocks", "delta.hip")
+    with pytest.raises(KeyError):
+        lm.csrc_const("kNoSuchConstant", "delta.hip")
+
+
+DELTA_TAIL = (16 << 10) + 99      # what N_BIG has past the line, scaled down
+
+
+def _delta_setup(line):
+    import delta_model as dl
+    n = line + DELTA_TAIL
+    d = dl.ModelDriver("fast")
+    content = dl.rand(7000 + line, n)
+    a = d.file("a", content)
+    return dl, d, content, a, n
+
+
+def _ops_of(r):
+    return [tuple(int(x) for x in o) for o in r["ops"]]
+
+
+@pytest.mark.parametrize("line", [40000, 1 << 16, 70001])
+def test_delta_closed_forms_equal_the_delta_model(line):
+    dl, d, content, a, n = _delta_setup(line)
+    assert lm.DELTA_LIT == dl.LIT
+    # (i) an insert past the line
+    p, ins = line + 99, dl.rand(1, 7)
+    ins[0], ins[-1] = content[p] ^ 1, content[p - 1] ^ 1
+    b = d.clone("a", "ins")
+    d.splice(b, p, 0, ins)
+    r = d.delta(a, b)
+    assert _ops_of(r) == lm.delta_insert(n, p, 7) and r["regions"] == 1 and r["bytes_literal"] == 7
+    t = d.delta(a, b, True)
+    lit = [o for o in t["ops"] if o[2] == dl.LIT]
+    assert len(lit) == 1 and lit[0][0] <= p and p + 7 <= lit[0][0] + lit[0][1] == lit[0][0] + r["bytes_literal_tables"]
+    # (ii), (iii) the head dropped, and put back
+    cut = line + 5
+    e = lm.common_prefix(content[cut:], content)
+    b = d.clone("a", "tail")
+    d.splice(b, 0, cut, None)
+    assert np.array_equal(d.content(b), content[cut:])
+    assert _ops_of(d.delta(a, b)) == lm.delta_drop_head(n, cut, e)
+    r = d.delta(b, a)
+    assert _ops_of(r) == lm.delta_restore_head(n, cut, e) and r["bytes_literal"] == cut - e
+    # (iv) the first bytes once more at the end: every slot of theirs twice, `n` apart
+    import splice_model as spm
+    b = d.clone("a", "dup")
+    head = content[:4096]
+    d.m.append(b, head, spm.chunk("fast", head))
+    twice = [sp.hash for sp in d.m._spans(b)]
+    assert twice.count(twice[0]) == 2
+    assert _ops_of(d.delta(b, b)) == lm.delta_self(n + 4096)
+    # (v) truncated, and grown back
+    b = d.clone("a", "cut")
+    d.splice(b, line + 1, n - line - 1, None)
+    f = lm.common_suffix(content, content[:line + 1])
+    assert _ops_of(d.delta(a, b)) == lm.delta_truncate(n, line + 1)
+    assert _ops_of(d.delta(b, a)) == lm.delta_extend(n, line + 1, f)
+
+
+def test_delta_closed_forms_with_shared_edges():
+    """e and f are not always 0: contents built so that the searches do match some bytes."""
+    import delta_model as dl
+    line = 30000
+    n = line + DELTA_TAIL
+    content = dl.rand(7100, n)
+    cut = line + 5
+    content[cut:cut + 3] = content[:3]                   # A[cut:] opens like A
+    content[cut + 3] = content[3] ^ 1
+    content[n - 2:] = content[line - 1:line + 1]         # A ends like A[:line + 1]
+    content[n - 3] = content[line - 2] ^ 1
+    d = dl.ModelDriver("fast")
+    a = d.file("a", content)
+    assert lm.common_prefix(content[cut:], content) == 3 and lm.common_suffix(content, content[:line + 1]) == 2
+    b = d.clone("a", "tail")
+    d.splice(b, 0, cut, None)
+    assert _ops_of(d.delta(a, b)) == lm.delta_drop_head(n, cut, 3)
+    assert _ops_of(d.delta(b, a)) == lm.delta_restore_head(n, cut, 3)
+    b = d.clone("a", "cut")
+    d.splice(b, line + 1, n - line - 1, None)
+    assert _ops_of(d.delta(b, a)) == lm.delta_extend(n, line + 1, 2)
+
+
+def test_the_large_cases_have_power():
+    """For every case of test_gpu_large_later.py, the expectation at the real
+    N_BIG holds a value >= 2^32 in the field the case is named for, and the same
+    expectation with that field cut to 32 bits is another one: a uint32_t in
+    that place cannot pass."""
+    LINE, N_BIG = lm.LINE, lm.N_BIG
+    LIT = lm.DELTA_LIT
+    # packs: chunk_off, data_bytes, total_bytes and the layout's data offset + chunk_off.  A tiling of N_BIG
+    # with lengths in the 16 / 64 / 256 KiB list's range stands in for the real list (the GPU case asserts
+    # the same on the real one).
+    rng = np.random.default_rng(5)
+    lens = rng.integers(16384, 262145, 40000).astype(np.uint64)
+    lens = lens[:int(np.searchsorted(np.cumsum(lens), N_BIG))]
+    lens = np.append(lens, np.uint64(N_BIG - int(lens.sum())))
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64)
+    rows = np.stack([offs, lens], axis=1)
+    digests = np.arange(len(rows) * 4, dtype="<u8").view(np.uint8).reshape(-1, 32)      # distinct
+    x = lm.pack_index(rows, digests)
+    assert x.n_chunks == len(rows) and x.file_size == N_BIG
+    assert int(x.chunk_off[-1]) == x.data_bytes >= LINE and x.layout["total"] >= LINE
+    assert lm.masked32(x.chunk_off) != [int(v) for v in x.chunk_off]
+    assert lm.masked32([x.data_bytes, x.layout["total"]]) != [x.data_bytes, x.layout["total"]]
+    assert (x.data_bytes // 16384 + x.n_chunks) > 1 << 18              # the copy's tile bound, kStoreTile = 16 KiB
+    # the batch write: the third request's base, in spans and bytes, lies past a 4 GiB request
+    assert 1000 + N_BIG >= LINE
+
+    def differs(ops, field):
+        cut = [tuple(v & 0xFFFFFFFF if (i == field and v != LIT) else v for i, v in enumerate(o)) for o in ops]
+        return cut != ops
+
+    p, k = LINE + 99, 7
+    ins = lm.delta_insert(N_BIG, p, k)
+    assert max(a for _, _, a in ins if a != LIT) >= LINE and differs(ins, 2) and differs(ins, 0)
+    d = LINE + 5
+    drop = lm.delta_drop_head(N_BIG, d)
+    assert all(a >= LINE for _, _, a in drop) and min(lm.delta_diagonals(drop)) >= LINE and differs(drop, 2)
+    back = lm.delta_restore_head(N_BIG, d)
+    assert lm.delta_literal(back) > LINE and min(lm.delta_diagonals(back)) < -LINE
+    assert differs(back, 1) and differs(back, 0)
+    assert lm.delta_literal(back) // 4096 > 1 << 18                    # more tiles than the edge pass has blocks
+    whole = lm.delta_self(N_BIG + (1 << 20))
+    assert whole[0][1] > N_BIG and differs(whole, 1)
+    grow = lm.delta_extend(N_BIG, LINE + 1)
+    assert grow[1][0] == LINE + 1 and differs(grow, 0) and differs(grow, 1)
+    assert lm.delta_truncate(N_BIG, LINE + 1) == [(0, LINE + 1, 0)] and differs(lm.delta_truncate(N_BIG, LINE + 1), 1)
+    assert min(lm.delta_diagonals(lm.delta_extend(N_BIG, LINE + 1, 3))) == LINE + 1 - N_BIG
 
 
 def test_check_tiling():
